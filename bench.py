@@ -26,6 +26,12 @@ workload) and the "effective" rate at the scheme's 72 B per site update (SURVEY 
 that advances two steps can exceed because it moves fewer bytes.  The CPU baseline is the straight
 NumPy transcription of the scheme (oracle/lbm_numpy.py) timed on this host on a bounded sample — it
 is only ever the thing measured BESIDE the product, never part of it.
+
+A plain run does only what the headline needs: set-up, clock settling, warm-up, the K timed steps, the
+line.  `--full` adds every side measurement: the rocprofv3 counter runs of this workload (`--pmc-traffic`),
+the un-fused and the contracted kernels beside the timed one (`--side`) and the CPU baseline
+(`--cpu-steps`); each of the three can also be asked for on its own.  `--dump-outputs DIR` writes what
+the timed steps computed (populations and macroscopic fields after the last step) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -98,7 +104,13 @@ def parse_args():
                          "steps; the exchange grows with it.  Real slabs of the 8-way split of 4096^2 on overlapping windows, slowest slab measured / with the "
                          "modelled exchange: 17.5 / 18.1 us per step at 29, 16.4 / 17.5 at 45, 16.0 / 17.3 at 61, 15.7 / 17.1 at 77 "
                          "(profiles/r05_t_slab_costs_cfg2_overlap.txt, r05_z_halo_deep.txt)")
-    ap.add_argument("--cpu-steps", type=int, default=10, help="steps of the NumPy CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the counter runs (--pmc-traffic 1), the side kernels (--side 1) and the CPU "
+                         "baseline (--cpu-steps 10), each unless given explicitly; without it those default to off (and --settle-ms to 120 in place of 50)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (f: the nine populations, rho, ux, uy; the run's float "
+                         "type): whole arrays up to 50 MB, beyond that the same fixed, seeded sample of sites in every array")
+    ap.add_argument("--cpu-steps", type=int, default=None, help="steps of the NumPy CPU baseline (0 = skip; default 10 with --full, else 0)")
     ap.add_argument("--fuse", type=int, default=-1, choices=[-1, 0, 1, 2],
                     help="two steps per pass over the lattice (csrc/step_march.hpp; fp32; bit-identical): -1 library "
                          "default (on where it pays), 0 off, 1 where it pays, 2 always")
@@ -108,19 +120,20 @@ def parse_args():
     ap.add_argument("--fast-math", type=int, default=-1, choices=[-1, 0, 1],
                     help="the OPT-IN contracted collision (fused multiply-adds, v_rcp): -1 (default) = the bit-exact kernels print the line and the "
                          "contracted ones are timed beside them as roofline.contracted; 0 = skip that; 1 = the whole run uses them (NOT bit-exact)")
-    ap.add_argument("--pmc-traffic", type=int, default=1, choices=[0, 1],
-                    help="1 (default, one GPU only): before the timed run, measure this workload's HBM traffic and vector-ALU activity per launch in this "
+    ap.add_argument("--pmc-traffic", type=int, default=None, choices=[0, 1],
+                    help="1 (default with --full, one GPU only): before the timed run, measure this workload's HBM traffic and vector-ALU activity per launch in this "
                          "session — three short child runs of this script under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` / the SQ group — and use "
                          "them for roofline.traffic / frac / valu_busy_frac; 0, or when rocprofv3 is not available: the entry of profiles/pmc_traffic.json "
                          "(measured in another run), if there is one, and no valu_busy_frac")
-    ap.add_argument("--side", type=int, default=1, choices=[0, 1],
-                    help="1 (default, one GPU): also time the un-fused kernel and (fp32) the opt-in contracted arithmetic for the roofline entry — BEFORE the "
+    ap.add_argument("--side", type=int, default=None, choices=[0, 1],
+                    help="1 (default with --full, one GPU): also time the un-fused kernel and (fp32) the opt-in contracted arithmetic for the roofline entry — BEFORE the "
                          "warm-up, reported as preheat_steps / preheat_ms; 0: nothing runs on the device before the declared warm-up but the plan's own tuning")
-    ap.add_argument("--settle-ms", type=float, default=50.0,
+    ap.add_argument("--settle-ms", type=float, default=None,
                     help="untimed steps on the bench handle IN FRONT of the declared warm-up, this many milliseconds of device work, so that the timed region "
                          "runs at settled clocks: a fresh MI355X process reads 336, 359, 353, 339, 330, 322 ... 299 us per pass over its first 35 ms of "
                          "marching and 295-300 from then on, whatever the flow does (profiles/r05_zz_clock_settling.txt) — a timed region of 20 steps is "
-                         "1.6 ms.  The lattice is put back to its initial state afterwards; counted in preheat_steps / preheat_ms.  0: none")
+                         "1.6 ms.  The lattice is put back to its initial state afterwards; counted in preheat_steps / preheat_ms.  0: none.  Default 50 with "
+                         "--full; 120 without, which stands in for the ~70 ms of side kernels (--side) a plain run no longer puts in front of its warm-up")
     ap.add_argument("--balance", type=int, default=-1, metavar="R",
                     help="slab runs with strong scaling: R rounds of cutting the slabs by MEASURED cost instead of equal widths before the run (every rank "
                          "times its candidate slab alone, airfoil_cfd_tool_amd.distributed.balance_split; the split with the fastest slowest slab is kept, "
@@ -128,6 +141,11 @@ def parse_args():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: nx x ny split over N GPUs; weak: every GPU gets an nx x ny slab")
     args = ap.parse_args()
+    for k, on, off in (("cpu_steps", 10, 0), ("pmc_traffic", 1, 0), ("side", 1, 0), ("settle_ms", 50.0, 120.0)):
+        if getattr(args, k) is None:
+            setattr(args, k, on if args.full else off)
+    if args.dump_outputs and (args.gpus > 1 or args.local_slabs > 0):
+        ap.error("--dump-outputs: one GPU, one lattice (not with --gpus N or --local-slabs)")
     cfg = CONFIGS[args.config]
     args.custom = [k for k in ("nx", "ny", "dtype", "shape", "aoa") if getattr(args, k) is not None and getattr(args, k) != cfg[k]]
     for k in ("nx", "ny", "dtype", "shape", "aoa", "steps", "warmup"):
@@ -178,6 +196,33 @@ def cpu_baseline(mask, steps, tau, u0, dtype):
         "sample": f"{steps} steps of the same {nx}x{ny} {dtype} lattice and mask, oracle/lbm_numpy.py "
                   f"(NumPy {np.__version__}, element-wise => single core; host: {cpu_model()}, {os.cpu_count()} cpus), {dt:.1f} s",
     }
+
+
+DUMP_SEED = 20240611
+DUMP_BYTES = 12 << 22        # 9 populations + rho, ux, uy: 2^22 / element-size sites (50.3 MB, fp32 or fp64)
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the lattice after the last timed step as a caller of the step receives it — the nine populations (f) and the
+    macroscopic fields (rho, ux, uy) — in the run's float type.  Lattices beyond DUMP_BYTES are sampled: the same sites (fixed seed, in
+    ascending order of y * nx + x) in every array, so that two builds given the same arguments can be compared value for value."""
+    import numpy as np
+    f = eng.read_f()
+    rho, ux, uy = eng.read_macro()
+    ny, nx = rho.shape
+    arrays = {"f": f.reshape(9, ny * nx), "rho": rho.reshape(-1), "ux": ux.reshape(-1), "uy": uy.reshape(-1)}
+    n = DUMP_BYTES // (12 * f.itemsize)
+    if ny * nx > n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ny * nx, n, replace=False))
+        arrays = {k: np.ascontiguousarray(v[..., idx]) for k, v in arrays.items()}
+        sample = f"{n} of {ny * nx} sites, numpy default_rng({DUMP_SEED}).choice without replacement, sorted"
+    else:
+        arrays = {"f": f, "rho": rho, "ux": ux, "uy": uy}
+        sample = "all sites"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {"dir": out_dir, "arrays": sorted(arrays), "sites": sample}
 
 
 def baseline_metric():
@@ -720,6 +765,7 @@ def main():
             barrier()
     except Exception as e:      # noqa: BLE001
         die(rank, local_rank, "stepping", e)
+    dumped = dump_outputs(eng, args.dump_outputs) if args.dump_outputs else None
 
     if tune_passes == 0 and bool(eng.get_option("fuse_active")) and eng.get_option("tune_rounds") > 0:
         # (no side measurement ran: the plan was timed inside the warm-up call, before its first pass)
@@ -867,6 +913,8 @@ def main():
         "device_ms": per_rank_ms,
         "roofline": roofline,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank_report is not None:
         out["ranks"] = rank_report
         out["comm_ranks_seen"] = sorted({r_["comm_ranks"] for r_ in rank_report})

@@ -111,3 +111,53 @@ def test_bound_is_mixed_when_the_two_fractions_are_close():
     import bench
     src = open(bench.__file__).read()
     assert '"mixed" if abs(valu_cmp - hbm_cmp) < 0.1' in src and "valu_frac / 0.9" in src
+
+
+def test_side_measurements_only_with_full(bench):
+    """A plain run measures the headline alone; --full switches on the counter runs, the side kernels and the CPU baseline; an explicit value wins."""
+    a = _args(bench, "--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert (a.full, a.pmc_traffic, a.side, a.cpu_steps, a.settle_ms, a.dump_outputs) == (False, 0, 0, 0, 120.0, None)
+    a = _args(bench, "--full", "--steps", "20", "--warmup", "5")
+    assert (a.full, a.pmc_traffic, a.side, a.cpu_steps, a.settle_ms) == (True, 1, 1, 10, 50.0) and a.steps == 20
+    a = _args(bench, "--full", "--pmc-traffic", "0", "--cpu-steps", "1")
+    assert (a.pmc_traffic, a.side, a.cpu_steps) == (0, 1, 1)
+    a = _args(bench, "--side", "1")
+    assert (a.pmc_traffic, a.side, a.cpu_steps) == (0, 1, 0)
+    for bad in (("--gpus", "2"), ("--local-slabs", "4")):
+        with pytest.raises(SystemExit):
+            _args(bench, "--dump-outputs", "out", *bad)
+
+
+class _FakeEngine:
+    def __init__(self, nx, ny, dtype):
+        import numpy as np
+        self.f = np.arange(9 * ny * nx, dtype=dtype).reshape(9, ny, nx)
+
+    def read_f(self):
+        return self.f.copy()
+
+    def read_macro(self):
+        return self.f[0] + 1, self.f[1] * 2, self.f[2] - 3
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_dump_outputs_whole_and_sampled(bench, tmp_path, dtype):
+    """--dump-outputs: whole arrays on a small lattice; on a large one the same seeded sites in every array, within the 64 MB bound."""
+    import numpy as np
+    e = _FakeEngine(96, 40, dtype)
+    d = bench.dump_outputs(e, str(tmp_path / "small"))
+    assert d["arrays"] == ["f", "rho", "ux", "uy"] and d["sites"] == "all sites"
+    assert np.array_equal(np.load(tmp_path / "small" / "f.npy"), e.f)
+    assert np.array_equal(np.load(tmp_path / "small" / "ux.npy"), e.f[1] * 2)
+    e = _FakeEngine(2048, 1100, dtype)                         # 2.25 M sites: more than the budget holds in either precision
+    runs = [bench.dump_outputs(e, str(tmp_path / k)) for k in ("a", "b")]
+    total = 0
+    for name in ("f", "rho", "ux", "uy"):
+        a, b = (np.load(tmp_path / k / (name + ".npy")) for k in ("a", "b"))
+        assert a.dtype == np.dtype(dtype) and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total <= 64e6 and "sites" in runs[0]["sites"]
+    f, rho = np.load(tmp_path / "a" / "f.npy"), np.load(tmp_path / "a" / "rho.npy")
+    idx = (rho - 1).astype(np.int64)                           # rho = f[0] + 1 and f[0] holds the site index
+    assert f.shape == (9, idx.size) and np.all(np.diff(idx) > 0) and idx.size == bench.DUMP_BYTES // (12 * np.dtype(dtype).itemsize)
+    assert np.array_equal(f, e.f.reshape(9, -1)[:, idx])

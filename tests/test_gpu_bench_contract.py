@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _run(*extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "1024", "--ny", "512", "--steps", "20",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--nx", "1024", "--ny", "512", "--steps", "20",
                           "--warmup", "3", "--cpu-steps", "1", *(() if "--pmc-traffic" in extra else ("--pmc-traffic", "0")), *extra],
                          capture_output=True, text=True, timeout=600, check=True)
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -85,7 +85,7 @@ def test_bench_measures_its_traffic_in_the_same_session():
 
 def test_bench_default_frac_is_counter_based_and_below_one():
     """The default workload has a counter entry (profiles/pmc_traffic.json): frac = measured HBM bytes / this run's time <= 1."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-steps", "0", "--pmc-traffic", "0"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--cpu-steps", "0", "--pmc-traffic", "0"],
                          capture_output=True, text=True, timeout=600, check=True)
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
     r = d["roofline"]
