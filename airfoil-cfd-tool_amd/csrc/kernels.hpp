@@ -182,16 +182,18 @@ __global__ __launch_bounds__(256) void k_ranges(const T *__restrict__ macro, con
 // computeForces (html:650-698) seen from the fluid side: every owned fluid cell adds, for each
 // of its 4 face neighbours that is inside the grid and solid, p = rho/3 along the unit vector
 // from the fluid cell into the solid.
+// One 256-thread block's partial sum, block `blk` of `nblk` (grid-stride over the owned sites); thread 0 writes it to *out.
+// Shared by k_forces and the batched k_forces_batch (csrc/polar.hip), so both sum the same sites in the same order.
 template <typename T>
-__global__ __launch_bounds__(256) void k_forces(const T *__restrict__ macro, const uint8_t *__restrict__ mask, Geom g,
-                                                int i_own0, int W, ForcePartial *__restrict__ part)
+__device__ __forceinline__ void forces_block(const T *__restrict__ macro, const uint8_t *__restrict__ mask, const Geom &g,
+                                             int i_own0, int W, int blk, int nblk, ForcePartial *__restrict__ out)
 {
     const uint8_t *m = mask + g.pitch;
     const long mp = (long)g.nxl * g.pitch;
     double fx = 0.0, fy = 0.0;
     long long surf = 0, rev = 0;
     const long total = (long)W * g.ny;
-    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    for (long t = (long)blk * 256 + threadIdx.x; t < total; t += (long)nblk * 256) {
         const int x = (int)(t / g.ny), j = (int)(t % g.ny);
         const int i = i_own0 + x;
         const int gi = i + g.gi0;
@@ -222,8 +224,15 @@ __global__ __launch_bounds__(256) void k_forces(const T *__restrict__ macro, con
         r.fy = shd[1][0] + shd[1][1] + shd[1][2] + shd[1][3];
         r.surf = shl[0][0] + shl[0][1] + shl[0][2] + shl[0][3];
         r.rev = shl[1][0] + shl[1][1] + shl[1][2] + shl[1][3];
-        part[blockIdx.x] = r;
+        *out = r;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_forces(const T *__restrict__ macro, const uint8_t *__restrict__ mask, Geom g,
+                                                int i_own0, int W, ForcePartial *__restrict__ part)
+{
+    forces_block<T>(macro, mask, g, i_own0, W, (int)blockIdx.x, (int)gridDim.x, part + blockIdx.x);
 }
 
 // Diagnostics for the stability net (html:344-350): how many fluid sites of the owned columns sat AT a clamp in the

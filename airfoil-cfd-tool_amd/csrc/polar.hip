@@ -1,0 +1,539 @@
+// polar.hip — C-ABI implementation of libwtpolar.so (see include/wt_polar.h): B independent tunnels of one size
+// ("members") advanced by one launch per step, with the force reduction of every member on the device.
+//
+// Bit identity with a libwindtunnel handle holds by construction: each member keeps wt_create's layout (pitch, pad
+// columns, plane stride), its tiles are classified by the same k_classify, a batched step runs the same step_tile
+// (step_fast.hpp) with tau and U0 rounded to the storage type on the host as wt_step rounds them, and a force sample
+// runs k_forces' block body (forces_block, kernels.hpp) over wt_forces' block count, summed over the blocks in the
+// same order in double.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/wt_polar.h"
+#include "kernels.hpp"
+#include "step_fast.hpp"
+
+using namespace wt;
+
+static thread_local char g_err[512] = "";
+
+static int fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(e_ == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "%s failed: %s (%s:%d)",   \
+                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                              \
+    } while (0)
+
+#define WT_TRY(expr)                \
+    do {                            \
+        int rc_ = (expr);           \
+        if (rc_ != WT_OK) return rc_; \
+    } while (0)
+
+static const int kReduceBlocks = 1024;     // wt_forces' cap on the reduction's block count
+
+// Element strides between consecutive members of each array.  Every stride is rounded to 4 KiB and grown by 17 KiB, as
+// wt_create's plane stride is, so that the members' lattices do not all start on the same HBM channels.
+struct MemberStrides { long lat, macro, mask, tiles; };
+
+static long member_stride(size_t bytes, size_t esz) { return (long)(((bytes + 4095) / 4096 * 4096 + 17408) / esz); }
+
+struct wtp_batch {
+    int nx = 0, ny = 0, dtype = WT_F32, device = 0, members = 0, cap = 0;
+    size_t esz = 4;
+    Geom g{};
+    int tiles_per_col = 0;
+    MemberStrides ms{};
+    void *f[2] = {nullptr, nullptr};     // members' lattices, each laid out as wt_create's
+    int cur = 0;
+    void *macro = nullptr;
+    uint8_t *mask = nullptr;
+    uint8_t *tiles = nullptr;
+    void *params = nullptr;              // [B][2] of T: tau, U0 of the last stepping call
+    std::vector<double> params_host;     // ... as the caller gave them (doubles), to skip unchanged uploads
+    ForcePartial *partials = nullptr;    // [B][nb]
+    unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
+    double *h_fx = nullptr, *h_fy = nullptr;          // history [cap + 1][B]; row cap = wtp_forces' scratch row
+    long long *h_surf = nullptr, *h_rev = nullptr;
+    std::vector<int64_t> h_step;         // step count of each history row held
+    void *stage = nullptr;               // layout conversion (one member's plane, or one mask)
+    size_t stage_bytes = 0;
+    int nb = 0;                          // blocks of one member's force reduction
+    hipStream_t st = nullptr;
+    std::vector<uint8_t> mask_set;
+    bool inited = false;
+    long long steps_done = 0;
+};
+
+// ------------------------------------------------------------------------------------------
+// kernels
+// ------------------------------------------------------------------------------------------
+// One step of every member: blockIdx.y is the member, blockIdx.x * 4 + wave the tile inside it (k_step's grid).  rev walks
+// members and tiles backwards on every other step, as k_step walks its tiles.
+template <typename T, bool EMIT, int LOADMODE>
+__global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                    const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                    int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                    int rev)
+{
+    const int lane = threadIdx.x & 63;
+    const long ntiles = (long)g.nxl * tiles_per_col;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= ntiles) return;
+    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const T tau = params[2 * m], U0 = params[2 * m + 1];
+    step_tile<T, EMIT, LOADMODE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask, tiles + m * ms.tiles,
+                                 tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane);
+}
+
+// wt_forces of every member in one launch: grid (nb, B).  Each block computes k_forces' partial of its block index; the
+// last block of a member to finish (ticket) sums the member's nb partials in block order, in double, as wt_forces does on
+// the host, and writes one history entry.
+template <typename T>
+__global__ __launch_bounds__(256) void k_forces_batch(const T *__restrict__ macro, const uint8_t *__restrict__ mask, Geom g,
+                                                      MemberStrides ms, int nb, ForcePartial *__restrict__ part,
+                                                      unsigned int *__restrict__ tickets, double *__restrict__ fx,
+                                                      double *__restrict__ fy, long long *__restrict__ surf,
+                                                      long long *__restrict__ rev)
+{
+    const long m = blockIdx.y;
+    ForcePartial *p = part + m * nb;
+    forces_block<T>(macro + m * ms.macro, mask + m * ms.mask, g, 0, g.nxl, (int)blockIdx.x, nb, p + blockIdx.x);
+    __shared__ int last;
+    if (threadIdx.x == 0) {
+        __threadfence();                                            // this block's partial is visible device-wide ...
+        last = atomicAdd(&tickets[m], 1u) == (unsigned)(nb - 1);    // ... before it is counted
+    }
+    __syncthreads();
+    if (!last || threadIdx.x != 0) return;
+    __threadfence();
+    const volatile ForcePartial *vp = p;
+    double sx = 0.0, sy = 0.0;
+    long long ns = 0, nr = 0;
+    for (int b = 0; b < nb; b++) { sx += vp[b].fx; sy += vp[b].fy; ns += vp[b].surf; nr += vp[b].rev; }
+    fx[m] = sx; fy[m] = sy; surf[m] = ns; rev[m] = nr;
+    tickets[m] = 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// life cycle
+// ------------------------------------------------------------------------------------------
+template <typename T> static T *fptr(wtp_batch *b, int which, int m) { return reinterpret_cast<T *>(b->f[which]) + (long)m * b->ms.lat; }
+template <typename T> static T *macro_of(wtp_batch *b, int m) { return reinterpret_cast<T *>(b->macro) + (long)m * b->ms.macro; }
+
+static int check_batch(const wtp_batch *b)
+{
+    if (!b) return fail(WT_ERR_ARG, "null batch");
+    return WT_OK;
+}
+
+static int ensure_stage(wtp_batch *b, size_t bytes)
+{
+    if (b->stage_bytes >= bytes) return WT_OK;
+    if (b->stage) { HIP_TRY(hipFree(b->stage)); b->stage = nullptr; b->stage_bytes = 0; }
+    HIP_TRY(hipMalloc(&b->stage, bytes));
+    b->stage_bytes = bytes;
+    return WT_OK;
+}
+
+extern "C" int wtp_destroy(wtp_batch *b)
+{
+    if (!b) return WT_OK;
+    (void)hipSetDevice(b->device);
+    if (b->st) (void)hipStreamSynchronize(b->st);
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets,
+                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage};
+    for (void *p : bufs) if (p) (void)hipFree(p);
+    if (b->st) (void)hipStreamDestroy(b->st);
+    delete b;
+    return WT_OK;
+}
+
+extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_cap, int device, wtp_batch **out)
+{
+    if (!out) return fail(WT_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (nx < 3 || ny < 3) return fail(WT_ERR_ARG, "lattice must be at least 3x3 (got %dx%d)", nx, ny);
+    if ((long long)nx * ny > (1LL << 33)) return fail(WT_ERR_ARG, "lattice too large");
+    if (dtype != WT_F32 && dtype != WT_F64) return fail(WT_ERR_ARG, "dtype must be WT_F32 or WT_F64");
+    if (members < 1 || members > WTP_MAX_MEMBERS) return fail(WT_ERR_ARG, "members must be in [1, %d] (got %d)", WTP_MAX_MEMBERS, members);
+    if (history_cap < 0) return fail(WT_ERR_ARG, "history_cap must be >= 0 (got %d)", history_cap);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return fail(WT_ERR_HIP, "no HIP device available (%s); libwtpolar has no CPU fallback",
+                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    if (device < 0 || device >= ndev) return fail(WT_ERR_ARG, "device %d out of range (0..%d)", device, ndev - 1);
+    HIP_TRY(hipSetDevice(device));
+
+    wtp_batch *b = new (std::nothrow) wtp_batch();
+    if (!b) return fail(WT_ERR_OOM, "host allocation failed");
+    b->nx = nx; b->ny = ny; b->dtype = dtype; b->device = device; b->members = members; b->cap = history_cap;
+    b->esz = dtype == WT_F32 ? 4 : 8;
+    Geom &g = b->g;                              // wt_create's geometry of a whole lattice
+    g.nxl = nx; g.ny = ny; g.gi0 = 0; g.nx_g = nx;
+    g.pitch = ((long)ny + 255) / 256 * 256;
+    g.plane = (((long)(g.nxl + 2) * g.pitch * (long)b->esz + 4095) / 4096 * 4096 + 17408) / (long)b->esz;
+    b->tiles_per_col = (int)(g.pitch / tile_j_of(b->esz));
+    b->ms.lat = member_stride((size_t)9 * g.plane * b->esz, b->esz);
+    b->ms.macro = member_stride((size_t)3 * g.nxl * g.pitch * b->esz, b->esz);
+    b->ms.mask = member_stride((size_t)(g.nxl + 2) * g.pitch, 1);
+    b->ms.tiles = member_stride((size_t)g.nxl * b->tiles_per_col, 1);
+    const long total = (long)nx * ny;
+    b->nb = (int)std::min<long>((total + 255) / 256, kReduceBlocks);
+    b->mask_set.assign((size_t)members, 0);
+
+    auto cleanup = [&](int rc) { wtp_destroy(b); return rc; };
+#define CREATE_TRY(expr)                                                                               \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return cleanup(fail(e_ == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "%s failed: %s",  \
+                                #expr, hipGetErrorString(e_)));                                        \
+    } while (0)
+    const size_t B = (size_t)members;
+    const size_t lat_bytes = B * b->ms.lat * b->esz, macro_bytes = B * b->ms.macro * b->esz;
+    const size_t mask_bytes = B * b->ms.mask, tile_bytes = B * b->ms.tiles;
+    const size_t rows = (size_t)history_cap + 1;
+    CREATE_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+    CREATE_TRY(hipMalloc(&b->f[0], lat_bytes));
+    CREATE_TRY(hipMalloc(&b->f[1], lat_bytes));
+    CREATE_TRY(hipMalloc(&b->macro, macro_bytes));
+    CREATE_TRY(hipMalloc((void **)&b->mask, mask_bytes));
+    CREATE_TRY(hipMalloc((void **)&b->tiles, tile_bytes));
+    CREATE_TRY(hipMalloc(&b->params, B * 2 * b->esz));
+    CREATE_TRY(hipMalloc((void **)&b->partials, B * b->nb * sizeof(ForcePartial)));
+    CREATE_TRY(hipMalloc((void **)&b->tickets, B * sizeof(unsigned int)));
+    CREATE_TRY(hipMalloc((void **)&b->h_fx, rows * B * sizeof(double)));
+    CREATE_TRY(hipMalloc((void **)&b->h_fy, rows * B * sizeof(double)));
+    CREATE_TRY(hipMalloc((void **)&b->h_surf, rows * B * sizeof(long long)));
+    CREATE_TRY(hipMalloc((void **)&b->h_rev, rows * B * sizeof(long long)));
+    CREATE_TRY(hipMemsetAsync(b->f[0], 0, lat_bytes, b->st));
+    CREATE_TRY(hipMemsetAsync(b->f[1], 0, lat_bytes, b->st));
+    CREATE_TRY(hipMemsetAsync(b->macro, 0, macro_bytes, b->st));
+    CREATE_TRY(hipMemsetAsync(b->mask, 0, mask_bytes, b->st));
+    CREATE_TRY(hipMemsetAsync(b->tiles, 0, tile_bytes, b->st));
+    CREATE_TRY(hipMemsetAsync(b->tickets, 0, B * sizeof(unsigned int), b->st));
+    CREATE_TRY(hipStreamSynchronize(b->st));
+#undef CREATE_TRY
+    *out = b;
+    return WT_OK;
+}
+
+extern "C" const char *wtp_last_error(void) { return g_err; }
+
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.1 (gfx950, batched D2Q9 members, column-major SoA)"; }
+
+extern "C" int wtp_sync(wtp_batch *b)
+{
+    WT_TRY(check_batch(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// masks and state
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *masks)
+{
+    WT_TRY(check_batch(b));
+    if (!masks) return fail(WT_ERR_ARG, "masks is null");
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    HIP_TRY(hipSetDevice(b->device));
+    const Geom &g = b->g;
+    const size_t n = (size_t)b->nx * b->ny;
+    WT_TRY(ensure_stage(b, n));
+    std::vector<uint8_t> m01(n);
+    HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old mask
+    for (int k = 0; k < count; k++) {
+        const uint8_t *src = masks + (size_t)k * n;
+        for (size_t q = 0; q < n; q++) m01[q] = src[q] ? 1 : 0;
+        HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
+        uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
+        dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
+        // [NY][NX] rows -> column i at row i + 1 of the padded mask (pad columns and rows past NY stay 0 from wtp_create)
+        hipLaunchKernelGGL(k_rows_to_cols<uint8_t>, grd, blk, 0, b->st, (const uint8_t *)b->stage, mm + g.pitch, 0, b->nx, b->ny,
+                           g.pitch, (long)b->nx);
+        HIP_TRY(hipGetLastError());
+        if (classify_tiles(mm, b->tiles + (long)(first + k) * b->ms.tiles, g, b->tiles_per_col, b->st) != 0)
+            return fail(WT_ERR_HIP, "k_classify launch failed: %s", hipGetErrorString(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(b->st));
+        b->mask_set[(size_t)(first + k)] = 1;
+    }
+    return WT_OK;
+}
+
+template <typename T>
+static int init_impl(wtp_batch *b, const double *u0)
+{
+    for (int m = 0; m < b->members; m++) {
+        // wt_init_equilibrium (html:474-490): JS doubles, rounded to the storage type
+        const double w0 = 4.0 / 9.0, ws = 1.0 / 9.0, wd = 1.0 / 36.0;
+        Init9<T> iv;
+        for (int k = 0; k < 9; k++) {
+            const double w = (k == 0) ? w0 : (k <= 4 ? ws : wd);
+            const double eu = ex_of(k) * u0[m], uu = u0[m] * u0[m];
+            iv.v[k] = (T)(w * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu));
+        }
+        iv.u0 = (T)u0[m];
+        hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m),
+                           b->g, iv);
+        HIP_TRY(hipGetLastError());
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
+{
+    WT_TRY(check_batch(b));
+    if (!u0) return fail(WT_ERR_ARG, "u0 is null");
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(u0[m])) return fail(WT_ERR_ARG, "u0[%d] must be finite", m);
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? init_impl<float>(b, u0) : init_impl<double>(b, u0));
+    b->cur = 0;
+    b->inited = true;
+    b->steps_done = 0;
+    b->h_step.clear();
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// stepping
+// ------------------------------------------------------------------------------------------
+static int check_ready(const wtp_batch *b)
+{
+    if (!b->inited) return fail(WT_ERR_STATE, "wtp_init_equilibrium has not been called");
+    for (int m = 0; m < b->members; m++)
+        if (!b->mask_set[(size_t)m]) return fail(WT_ERR_STATE, "member %d has no mask (wtp_set_masks)", m);
+    return WT_OK;
+}
+
+// tau and U0 of every member, rounded to T exactly as wt_step rounds them; uploaded only when they change
+template <typename T>
+static int upload_params(wtp_batch *b, const double *tau, const double *u0)
+{
+    std::vector<double> want((size_t)b->members * 2);
+    for (int m = 0; m < b->members; m++) { want[2 * (size_t)m] = tau[m]; want[2 * (size_t)m + 1] = u0[m]; }
+    if (want == b->params_host) return WT_OK;
+    std::vector<T> v(want.size());
+    for (size_t q = 0; q < want.size(); q++) v[q] = (T)want[q];
+    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
+    HIP_TRY(hipMemcpy(b->params, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    b->params_host.swap(want);
+    return WT_OK;
+}
+
+template <typename T>
+static int launch_forces(wtp_batch *b, int row)
+{
+    const size_t off = (size_t)row * b->members;
+    hipLaunchKernelGGL(k_forces_batch<T>, dim3((unsigned)b->nb, (unsigned)b->members), dim3(256), 0, b->st,
+                       (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, b->nb, b->partials, b->tickets,
+                       b->h_fx + off, b->h_fy + off, b->h_surf + off, b->h_rev + off);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+template <typename T>
+static int step_impl(wtp_batch *b, int nsteps, int sample_every)
+{
+    const long ntiles = (long)b->g.nxl * b->tiles_per_col;
+    const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)b->members), block(256);
+    for (int s = 0; s < nsteps; s++) {
+        const long long n = b->steps_done + 1;
+        const bool sample = sample_every > 0 && n % sample_every == 0;
+        const bool emit = sample || s + 1 == nsteps;
+        const T *fs = fptr<T>(b, b->cur, 0);
+        T *fd = fptr<T>(b, 1 - b->cur, 0);
+        const int rev = (int)(b->steps_done & 1);
+        if (emit)
+            hipLaunchKernelGGL((k_step_batch<T, true, WT_LOADMODE>), grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), b->mask, b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
+        else
+            hipLaunchKernelGGL((k_step_batch<T, false, WT_LOADMODE>), grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), b->mask, b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
+        HIP_TRY(hipGetLastError());
+        b->cur = 1 - b->cur;
+        b->steps_done = n;
+        if (sample) {
+            WT_TRY(launch_forces<T>(b, (int)b->h_step.size()));
+            b->h_step.push_back(n);
+        }
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const double *u0, int sample_every)
+{
+    WT_TRY(check_batch(b));
+    if (nsteps < 0) return fail(WT_ERR_ARG, "nsteps < 0");
+    if (sample_every < 0) return fail(WT_ERR_ARG, "sample_every < 0");
+    if (!tau || !u0) return fail(WT_ERR_ARG, "tau or u0 is null");
+    for (int m = 0; m < b->members; m++) {
+        if (!(tau[m] > 0.0) || !std::isfinite(tau[m])) return fail(WT_ERR_ARG, "tau[%d] must be positive and finite", m);
+        if (!std::isfinite(u0[m])) return fail(WT_ERR_ARG, "u0[%d] must be finite", m);
+    }
+    WT_TRY(check_ready(b));
+    if (sample_every > 0) {
+        const long long samples = (b->steps_done + nsteps) / sample_every - b->steps_done / sample_every;
+        if ((long long)b->h_step.size() + samples > b->cap)
+            return fail(WT_ERR_STATE, "%lld samples would overflow the history (%zu of %d rows held): read it and wtp_clear_history",
+                        samples, b->h_step.size(), b->cap);
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    if (b->dtype == WT_F32) {
+        WT_TRY(upload_params<float>(b, tau, u0));
+        return step_impl<float>(b, nsteps, sample_every);
+    }
+    WT_TRY(upload_params<double>(b, tau, u0));
+    return step_impl<double>(b, nsteps, sample_every);
+}
+
+// ------------------------------------------------------------------------------------------
+// read-backs
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_history(wtp_batch *b, int first, int count, int64_t *step, double *fx, double *fy, int64_t *surf, int64_t *rev)
+{
+    WT_TRY(check_batch(b));
+    const int held = (int)b->h_step.size();
+    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
+    if (step) for (int r = 0; r < count; r++) step[r] = b->h_step[(size_t)(first + r)];
+    if (n) {
+        if (fx) HIP_TRY(hipMemcpy(fx, b->h_fx + off, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (fy) HIP_TRY(hipMemcpy(fy, b->h_fy + off, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (surf) HIP_TRY(hipMemcpy(surf, b->h_surf + off, n * sizeof(long long), hipMemcpyDeviceToHost));
+        if (rev) HIP_TRY(hipMemcpy(rev, b->h_rev + off, n * sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    return held;
+}
+
+extern "C" int wtp_clear_history(wtp_batch *b)
+{
+    WT_TRY(check_batch(b));
+    b->h_step.clear();                           // (rows are only written by later, stream-ordered reductions)
+    return WT_OK;
+}
+
+extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, int64_t *rev)
+{
+    WT_TRY(check_batch(b));
+    if (!fx || !fy || !surf || !rev) return fail(WT_ERR_ARG, "null output");
+    WT_TRY(check_ready(b));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? launch_forces<float>(b, b->cap) : launch_forces<double>(b, b->cap));     // the scratch row
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t off = (size_t)b->cap * b->members, B = (size_t)b->members;
+    HIP_TRY(hipMemcpy(fx, b->h_fx + off, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fy, b->h_fy + off, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(surf, b->h_surf + off, B * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rev, b->h_rev + off, B * sizeof(long long), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+extern "C" int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_events)
+{
+    WT_TRY(check_batch(b));
+    if (!rho_events || !u_events) return fail(WT_ERR_ARG, "null output");
+    WT_TRY(check_ready(b));
+    HIP_TRY(hipSetDevice(b->device));
+    ClampPartial *dp = reinterpret_cast<ClampPartial *>(b->partials);     // (B * nb ForcePartials hold B * nb ClampPartials)
+    for (int m = 0; m < b->members; m++) {
+        if (b->dtype == WT_F32)
+            hipLaunchKernelGGL(k_clamp_events<float>, dim3(b->nb), dim3(256), 0, b->st, (const float *)macro_of<float>(b, m),
+                               b->mask + (long)m * b->ms.mask, b->g, 0, b->nx, dp + (long)m * b->nb);
+        else
+            hipLaunchKernelGGL(k_clamp_events<double>, dim3(b->nb), dim3(256), 0, b->st, (const double *)macro_of<double>(b, m),
+                               b->mask + (long)m * b->ms.mask, b->g, 0, b->nx, dp + (long)m * b->nb);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<ClampPartial> hp((size_t)b->members * b->nb);
+    HIP_TRY(hipStreamSynchronize(b->st));
+    HIP_TRY(hipMemcpy(hp.data(), dp, hp.size() * sizeof(ClampPartial), hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->members; m++) {
+        long long nr = 0, nu = 0;
+        for (int q = 0; q < b->nb; q++) { nr += hp[(size_t)m * b->nb + q].rho_events; nu += hp[(size_t)m * b->nb + q].u_events; }
+        rho_events[m] = nr; u_events[m] = nu;
+    }
+    return WT_OK;
+}
+
+template <typename T>
+static int read_plane(wtp_batch *b, const T *src_cols, T *host_dst)
+{
+    const Geom &g = b->g;
+    const size_t bytes = (size_t)b->nx * g.ny * sizeof(T);
+    WT_TRY(ensure_stage(b, bytes));
+    dim3 blk(32, 8), grd((g.ny + 31) / 32, (b->nx + 31) / 32);
+    hipLaunchKernelGGL(k_cols_to_rows<T>, grd, blk, 0, b->st, src_cols, reinterpret_cast<T *>(b->stage), 0, b->nx, g.ny, g.pitch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host_dst, b->stage, bytes, hipMemcpyDeviceToHost, b->st));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    return WT_OK;
+}
+
+static int check_member(const wtp_batch *b, int member)
+{
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    if (!b->inited) return fail(WT_ERR_STATE, "no state to read");
+    return WT_OK;
+}
+
+template <typename T>
+static int read_f_impl(wtp_batch *b, int member, void *out)
+{
+    const size_t n = (size_t)b->nx * b->ny;
+    for (int k = 0; k < 9; k++)
+        WT_TRY(read_plane<T>(b, fptr<T>(b, b->cur, member) + k * b->g.plane + b->g.pitch, reinterpret_cast<T *>(out) + k * n));
+    return WT_OK;
+}
+
+extern "C" int wtp_read_f(wtp_batch *b, int member, void *f_out)
+{
+    WT_TRY(check_batch(b));
+    if (!f_out) return fail(WT_ERR_ARG, "f_out is null");
+    WT_TRY(check_member(b, member));
+    HIP_TRY(hipSetDevice(b->device));
+    return b->dtype == WT_F32 ? read_f_impl<float>(b, member, f_out) : read_f_impl<double>(b, member, f_out);
+}
+
+template <typename T>
+static int read_macro_impl(wtp_batch *b, int member, void *rho, void *ux, void *uy)
+{
+    const long mp = (long)b->g.nxl * b->g.pitch;
+    const T *m = macro_of<T>(b, member);
+    void *dst[3] = {rho, ux, uy};
+    for (int a = 0; a < 3; a++)
+        if (dst[a]) WT_TRY(read_plane<T>(b, m + a * mp, reinterpret_cast<T *>(dst[a])));
+    return WT_OK;
+}
+
+extern "C" int wtp_read_macro(wtp_batch *b, int member, void *rho, void *ux, void *uy)
+{
+    WT_TRY(check_batch(b));
+    WT_TRY(check_member(b, member));
+    HIP_TRY(hipSetDevice(b->device));
+    return b->dtype == WT_F32 ? read_macro_impl<float>(b, member, rho, ux, uy) : read_macro_impl<double>(b, member, rho, ux, uy);
+}

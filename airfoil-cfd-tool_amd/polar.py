@@ -1,0 +1,295 @@
+"""Angle-of-attack sweeps on the LBM wind tunnel: many small tunnels in one launch.
+
+The reference's analysis page sweeps the angle of attack (``pages/Airfoil_Analysis.py:758-787``, range -20..20 deg)
+with one XFOIL request per angle (``:930-966``) and tabulates CL, CD, L/D and Cm per angle.  Here the angles of a
+sweep are the members of one batch of ``libwtpolar.so`` (include/wt_polar.h): every member is a whole wind tunnel,
+bit-identical to a :class:`~airfoil_cfd_tool_amd.WindTunnel` with the same inputs, and all of them advance by one
+kernel launch per step.  Lift, drag and separation are sampled on the device into a history that is read once.
+
+* :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
+* :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
+* :func:`sweep_alphas` / :func:`polar_rows` — the page's list of angles and its sweep-table rows.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_void_p
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import geometry as geo
+from ._capi import WT_F32, WT_F64, WT_OK, WTError, _np_dtype
+from .windtunnel import TAU_DEFAULT, U0_DEFAULT, chord_cells, stall_label, tau_from_reynolds
+
+_PKG_DIR = os.path.dirname(os.path.abspath(__file__))
+POLAR_LIB_PATH = os.path.join(_PKG_DIR, "lib", "libwtpolar.so")
+
+EXPORTS = (
+    "wtp_create", "wtp_destroy", "wtp_last_error", "wtp_version", "wtp_set_masks", "wtp_init_equilibrium", "wtp_step",
+    "wtp_history", "wtp_clear_history", "wtp_forces", "wtp_clamp_events", "wtp_read_f", "wtp_read_macro", "wtp_sync",
+)
+
+_lib = None
+
+
+def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
+    """Load libwtpolar.so, importing torch first when it is importable (one HIP runtime per process, as _capi.load_library)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not found: build it with `make lib`. There is no CPU fallback for the batched kernels.")
+    try:
+        import torch  # noqa: F401  (side effect: loads torch's libamdhip64 first)
+    except Exception:  # pragma: no cover
+        pass
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    B = c_void_p
+    dp, ip = POINTER(c_double), POINTER(c_int64)
+    sig = {
+        "wtp_create": ([c_int, c_int, c_int, c_int, c_int, c_int, POINTER(B)], c_int),
+        "wtp_destroy": ([B], c_int),
+        "wtp_last_error": ([], c_char_p),
+        "wtp_version": ([], c_char_p),
+        "wtp_set_masks": ([B, c_int, c_int, c_void_p], c_int),
+        "wtp_init_equilibrium": ([B, dp], c_int),
+        "wtp_step": ([B, c_int, dp, dp, c_int], c_int),
+        "wtp_history": ([B, c_int, c_int, ip, dp, dp, ip, ip], c_int),
+        "wtp_clear_history": ([B], c_int),
+        "wtp_forces": ([B, dp, dp, ip, ip], c_int),
+        "wtp_clamp_events": ([B, ip, ip], c_int),
+        "wtp_read_f": ([B, c_int, c_void_p], c_int),
+        "wtp_read_macro": ([B, c_int, c_void_p, c_void_p, c_void_p], c_int),
+        "wtp_sync": ([B], c_int),
+    }
+    for name, (argtypes, restype) in sig.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    _lib = lib
+    return lib
+
+
+def _check(rc: int) -> int:
+    if rc < WT_OK:
+        raise WTError(rc, load_polar_library().wtp_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+def _f64(a, n: int) -> np.ndarray:
+    """One value or [n] values -> a contiguous float64 [n]."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,)))
+
+
+def _dp(a: np.ndarray):
+    return a.ctypes.data_as(POINTER(c_double))
+
+
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(POINTER(c_int64))
+
+
+class PolarEngine:
+    """One libwtpolar batch: `members` whole tunnels of nx x ny, each with its own mask, tau and U0."""
+
+    def __init__(self, nx: int, ny: int, members: int, dtype="float32", history_cap: int = 0, device: int = 0):
+        self._lib = load_polar_library()
+        self.dtype = _np_dtype(dtype)
+        self.nx, self.ny, self.members, self.history_cap = int(nx), int(ny), int(members), int(history_cap)
+        self._b = c_void_p()
+        code = WT_F32 if self.dtype == np.float32 else WT_F64
+        _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
+
+    def close(self) -> None:
+        if getattr(self, "_b", None) is not None and self._b:
+            self._lib.wtp_destroy(self._b)
+            self._b = c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_masks(self, masks, first: int = 0) -> None:
+        """masks [count][NY][NX] (or one [NY][NX]) for members first .. first+count-1; flow kept."""
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.ndim == 2:
+            m = m[None]
+        if m.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"masks must have shape [count][NY][NX] = [count]{(self.ny, self.nx)}, got {m.shape}")
+        _check(self._lib.wtp_set_masks(self._b, int(first), int(m.shape[0]), m.ctypes.data_as(c_void_p)))
+
+    def init_equilibrium(self, u0) -> None:
+        """u0: one value or [B]."""
+        v = _f64(u0, self.members)
+        _check(self._lib.wtp_init_equilibrium(self._b, _dp(v)))
+
+    def step(self, nsteps: int, tau, u0, sample_every: int = 0) -> None:
+        """Enqueue nsteps steps of every member; tau, u0: one value or [B]."""
+        t, u = _f64(tau, self.members), _f64(u0, self.members)
+        _check(self._lib.wtp_step(self._b, int(nsteps), _dp(t), _dp(u), int(sample_every)))
+
+    def history(self) -> Dict[str, np.ndarray]:
+        """Every row held: step [R], fx / fy [R][B] float64, surf / rev [R][B] int64."""
+        rows = _check(self._lib.wtp_history(self._b, 0, 0, None, None, None, None, None))
+        B = self.members
+        out = {"step": np.empty(rows, np.int64), "fx": np.empty((rows, B)), "fy": np.empty((rows, B)),
+               "surf": np.empty((rows, B), np.int64), "rev": np.empty((rows, B), np.int64)}
+        _check(self._lib.wtp_history(self._b, 0, rows, _ip(out["step"]), _dp(out["fx"]), _dp(out["fy"]), _ip(out["surf"]),
+                                     _ip(out["rev"])))
+        return out
+
+    def clear_history(self) -> None:
+        _check(self._lib.wtp_clear_history(self._b))
+
+    def forces(self):
+        """(fx, fy, surf, rev), [B] each, of the last emitted state (wt_forces per member)."""
+        B = self.members
+        fx, fy, surf, rev = np.empty(B), np.empty(B), np.empty(B, np.int64), np.empty(B, np.int64)
+        _check(self._lib.wtp_forces(self._b, _dp(fx), _dp(fy), _ip(surf), _ip(rev)))
+        return fx, fy, surf, rev
+
+    def clamp_events(self):
+        """(density events, speed events), [B] each."""
+        a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
+        _check(self._lib.wtp_clamp_events(self._b, _ip(a), _ip(b)))
+        return a, b
+
+    def read_f(self, member: int) -> np.ndarray:
+        f = np.empty((9, self.ny, self.nx), dtype=self.dtype)
+        _check(self._lib.wtp_read_f(self._b, int(member), f.ctypes.data_as(c_void_p)))
+        return f
+
+    def read_macro(self, member: int):
+        rho, ux, uy = (np.empty((self.ny, self.nx), dtype=self.dtype) for _ in range(3))
+        _check(self._lib.wtp_read_macro(self._b, int(member), rho.ctypes.data_as(c_void_p), ux.ctypes.data_as(c_void_p),
+                                        uy.ctypes.data_as(c_void_p)))
+        return rho, ux, uy
+
+    def sync(self) -> None:
+        _check(self._lib.wtp_sync(self._b))
+
+
+# ---- statistics ------------------------------------------------------------------------------
+@dataclass
+class PolarPoint:
+    """One angle of a sweep: time statistics of the sampled forces (WindTunnel.compute_forces' raw values)."""
+    alpha: float
+    cl_mean: float
+    cl_std: float
+    cd_mean: float
+    cd_std: float
+    sep_frac: float              # mean rev / surf
+    separation: str              # stall_label(sep_frac)
+    samples: int                 # samples with a body surface (surf > 0)
+    finite: bool                 # every sample finite
+    clamp_events: Tuple[int, int]
+    history: Dict[str, np.ndarray] = field(repr=False, default_factory=dict)   # step, fx, fy, surf, rev of this angle
+
+    @property
+    def converged(self) -> bool:
+        return self.finite and self.samples > 0 and self.clamp_events == (0, 0)
+
+
+@dataclass
+class PolarResult:
+    points: List[PolarPoint]
+    nx: int
+    ny: int
+    tau: float
+    u0: float
+    warmup_steps: int
+    sample_every: int
+
+
+def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
+    """WindTunnel.compute_forces' raw values per sample: CL = fy/q, CD = fx/q, separation rev/surf, q = U0^2/2 * chord_cells(nx);
+    samples without a body surface (surf == 0) are dropped, as compute_forces returns None for them."""
+    fx, fy = np.asarray(fx, np.float64), np.asarray(fy, np.float64)
+    surf, rev = np.asarray(surf, np.int64), np.asarray(rev, np.int64)
+    keep = surf != 0
+    q = 0.5 * u0 * u0 * chord_cells(nx)
+    return fy[keep] / q, fx[keep] / q, rev[keep] / surf[keep]
+
+
+def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0)) -> PolarPoint:
+    """Statistics of one angle's force history."""
+    cl, cd, sep = raw_coefficients(fx, fy, surf, rev, u0, nx)
+    finite = bool(np.all(np.isfinite(np.asarray(fx, np.float64))) and np.all(np.isfinite(np.asarray(fy, np.float64))))
+    n = int(cl.size)
+    nan = float("nan")
+    hist = {"step": np.asarray(step, np.int64), "fx": np.asarray(fx, np.float64), "fy": np.asarray(fy, np.float64),
+            "surf": np.asarray(surf, np.int64), "rev": np.asarray(rev, np.int64)}
+    sep_mean = float(sep.mean()) if n else 0.0
+    return PolarPoint(alpha=float(alpha), cl_mean=float(cl.mean()) if n else nan, cl_std=float(cl.std()) if n else nan,
+                      cd_mean=float(cd.mean()) if n else nan, cd_std=float(cd.std()) if n else nan, sep_frac=sep_mean,
+                      separation=stall_label(sep_mean), samples=n, finite=finite,
+                      clamp_events=(int(clamp_events[0]), int(clamp_events[1])), history=hist)
+
+
+# ---- the sweep -------------------------------------------------------------------------------
+def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
+              u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
+              samples: int = 256, sample_every: int = 12, device: int = 0) -> PolarResult:
+    """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
+    samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
+    win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58."""
+    alphas = [float(a) for a in alphas]
+    if not alphas:
+        raise ValueError("no angles")
+    if tau is not None and re is not None:
+        raise ValueError("give tau or re, not both")
+    if samples < 1 or sample_every < 1:
+        raise ValueError("samples and sample_every must be >= 1")
+    nx, ny, u0 = int(nx), int(ny), float(u0)
+    tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
+    if warmup_steps is None:
+        warmup_steps = int(math.ceil(2 * nx / u0))
+    warmup_steps = int(warmup_steps)
+    user = geo.round_coords(coords) if coords is not None and len(coords) else []
+    masks = np.stack([geo.build_geometry(nx, ny, a, user, shape).mask for a in alphas])
+    with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device) as eng:
+        eng.set_masks(masks)
+        eng.init_equilibrium(u0)
+        if warmup_steps:
+            eng.step(warmup_steps, tau, u0)
+        # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
+        eng.step(samples * sample_every, tau, u0, sample_every=sample_every)
+        h = eng.history()
+        rho_ev, u_ev = eng.clamp_events()
+    points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]))
+              for m, a in enumerate(alphas)]
+    return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every))
+
+
+def sweep_alphas(start: float, end: float, step: float) -> List[float]:
+    """The page's angles of a sweep (pages/Airfoil_Analysis.py:930-932): rounded to 2 decimals, end included up to 1e-9."""
+    return [round(start + i * step, 2)
+            for i in range(int(round((end - start) / step)) + 1)
+            if round(start + i * step, 2) <= end + 1e-9]
+
+
+def polar_rows(result: PolarResult) -> List[dict]:
+    """The page's sweep table (pages/Airfoil_Analysis.py:950-966), one row per angle.  The LBM computes no moment: Cm is "—".
+    A point converged when every sample is finite and the stability net held no site at a bound; a failed one shows "—"
+    throughout, as the page's failed rows do."""
+    rows = []
+    for p in result.points:
+        if p.converged:
+            ld = p.cl_mean / p.cd_mean if p.cd_mean != 0 else None
+            rows.append({"α (°)": p.alpha, "CL": round(p.cl_mean, 4), "CD": round(p.cd_mean, 5),
+                         "L/D": round(ld, 2) if ld is not None else "—", "Cm": "—", "Status": "✅ Converged"})
+        else:
+            rows.append({"α (°)": p.alpha, "CL": "—", "CD": "—", "L/D": "—", "Cm": "—", "Status": "❌ Failed"})
+    return rows

@@ -1,0 +1,152 @@
+"""Batched angle-of-attack sweeps (libwtpolar.so, polar.py): what needs no GPU."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+WT_ERR_ARG = -1
+
+
+def _declared_polar_exports():
+    with open(os.path.join(ROOT, "include", "wt_polar.h")) as fh:
+        txt = fh.read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(wtp_[a-z_0-9]+)\s*\(", txt)))
+
+
+def test_dynamic_symbol_table_is_the_polar_header(pkg):
+    from airfoil_cfd_tool_amd.polar import EXPORTS, POLAR_LIB_PATH
+    out = subprocess.run(["nm", "-D", "--defined-only", POLAR_LIB_PATH], check=True, capture_output=True, text=True).stdout
+    syms = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    assert syms == _declared_polar_exports(), sorted(set(syms) ^ set(_declared_polar_exports()))
+    assert sorted(EXPORTS) == syms
+    assert b"libwtpolar" in pkg.polar.load_polar_library().wtp_version()
+
+
+@pytest.mark.parametrize("nx,ny,dtype,members,cap,needle", [
+    (2, 64, 0, 4, 8, b"3x3"),
+    (64, 64, 0, 0, 8, b"members"),
+    (64, 64, 0, 1025, 8, b"members"),
+    (64, 64, 7, 4, 8, b"dtype"),
+    (64, 64, 0, 4, -1, b"history_cap"),
+])
+def test_create_argument_errors_without_a_gpu(pkg, nx, ny, dtype, members, cap, needle):
+    lib = pkg.polar.load_polar_library()
+    b = ctypes.c_void_p()
+    assert lib.wtp_create(nx, ny, dtype, members, cap, 0, ctypes.byref(b)) == WT_ERR_ARG
+    assert needle in lib.wtp_last_error()
+    assert not b
+
+
+def test_null_batch_is_an_argument_error(pkg):
+    lib = pkg.polar.load_polar_library()
+    assert lib.wtp_destroy(None) == 0
+    assert lib.wtp_sync(None) == WT_ERR_ARG
+    assert lib.wtp_step(None, 1, None, None, 0) == WT_ERR_ARG
+    assert lib.wtp_clear_history(None) == WT_ERR_ARG
+
+
+def _page_alphas(alpha_start, alpha_end, alpha_step):
+    # pages/Airfoil_Analysis.py:930-932, verbatim
+    return [round(alpha_start + i * alpha_step, 2)
+            for i in range(int(round((alpha_end - alpha_start) / alpha_step)) + 1)
+            if round(alpha_start + i * alpha_step, 2) <= alpha_end + 1e-9]
+
+
+@pytest.mark.parametrize("start,end,step", [(-5, 15, 1), (-20, 20, 0.5), (0, 0, 1), (-2.5, 7.5, 2.5), (1, 4, 1.5),
+                                            (-5.0, 15.0, 3.5), (-20.0, -19.5, 0.5)])
+def test_sweep_alphas_is_the_pages_list(pkg, start, end, step):
+    got = pkg.sweep_alphas(start, end, step)
+    assert got == _page_alphas(start, end, step)
+    assert [type(a) for a in got] == [type(a) for a in _page_alphas(start, end, step)]
+
+
+def _synthetic_history(rng, n):
+    fx = rng.normal(0.3, 0.05, n)
+    fy = rng.normal(2.0, 0.3, n)
+    surf = rng.integers(150, 170, n)
+    surf[3] = 0                                   # a sample without a body surface: compute_forces returns None for it
+    rev = rng.integers(0, 40, n)
+    return np.arange(1, n + 1) * 12, fx, fy, surf, rev
+
+
+def test_statistics_follow_compute_forces_sample_by_sample(pkg):
+    from airfoil_cfd_tool_amd.polar import polar_point, raw_coefficients
+    rng = np.random.default_rng(7)
+    step, fx, fy, surf, rev = _synthetic_history(rng, 40)
+    u0, nx = 0.05, 320
+    raw = []
+    for a, b, c, d in zip(fx, fy, surf, rev):      # WindTunnel.compute_forces itself, fed one sample at a time
+        stub = types.SimpleNamespace(_forces=lambda a=a, b=b, c=c, d=d: (float(a), float(b), int(c), int(d)), u0=u0, nx=nx,
+                                     cl_smooth=None, cd_smooth=None, sep_frac=0.0)
+        r = pkg.WindTunnel.compute_forces(stub)
+        if r is not None:
+            raw.append(r)
+    cl, cd, sep = raw_coefficients(fx, fy, surf, rev, u0, nx)
+    assert len(raw) == len(cl) == 39
+    assert [r[0] for r in raw] == list(cl) and [r[1] for r in raw] == list(cd) and [r[2] for r in raw] == list(sep)
+    p = polar_point(4.0, step, fx, fy, surf, rev, u0, nx, (0, 0))
+    ref_cl, ref_cd, ref_sep = (np.array([r[k] for r in raw]) for k in range(3))
+    assert p.cl_mean == ref_cl.mean() and p.cl_std == ref_cl.std()
+    assert p.cd_mean == ref_cd.mean() and p.cd_std == ref_cd.std()
+    assert p.sep_frac == ref_sep.mean() and p.separation == pkg.stall_label(ref_sep.mean())
+    assert p.samples == 39 and p.finite and p.converged
+
+
+def _result(points):
+    from airfoil_cfd_tool_amd.polar import PolarResult
+    return PolarResult(points=points, nx=320, ny=160, tau=0.58, u0=0.06, warmup_steps=0, sample_every=12)
+
+
+def test_polar_rows_are_the_pages_rows(pkg):
+    from airfoil_cfd_tool_amd.polar import PolarPoint
+    ok = PolarPoint(alpha=4.0, cl_mean=0.712345678, cl_std=0.01, cd_mean=0.0412345678, cd_std=0.001, sep_frac=0.02,
+                    separation="Attached", samples=10, finite=True, clamp_events=(0, 0))
+    clamped = PolarPoint(alpha=16.5, cl_mean=1.1, cl_std=0.2, cd_mean=0.2, cd_std=0.02, sep_frac=0.4, separation="STALL ≈ 40% sep",
+                         samples=10, finite=True, clamp_events=(0, 3))
+    nonfinite = PolarPoint(alpha=20.0, cl_mean=float("nan"), cl_std=float("nan"), cd_mean=float("nan"), cd_std=float("nan"),
+                           sep_frac=0.0, separation="Attached", samples=10, finite=False, clamp_events=(0, 0))
+    rows = pkg.polar_rows(_result([ok, clamped, nonfinite]))
+    assert list(rows[0]) == ["α (°)", "CL", "CD", "L/D", "Cm", "Status"]
+    assert rows[0] == {"α (°)": 4.0, "CL": 0.7123, "CD": 0.04123, "L/D": round(0.712345678 / 0.0412345678, 2), "Cm": "—",
+                       "Status": "✅ Converged"}
+    assert rows[0]["L/D"] == 17.28
+    for r, a in zip(rows[1:], (16.5, 20.0)):
+        assert r == {"α (°)": a, "CL": "—", "CD": "—", "L/D": "—", "Cm": "—", "Status": "❌ Failed"}
+
+
+def test_importing_the_package_does_not_load_the_polar_library():
+    """libwtpolar.so is loaded by the first PolarEngine, not at import: a box without it still imports the package."""
+    code = ("import sys; sys.path.insert(0, %r); import airfoil_cfd_tool_amd as a; "
+            "print(a.polar._lib is None, a.sweep_alphas(0, 2, 1))") % ROOT
+    out = subprocess.run([sys.executable, "-c", code], check=True, capture_output=True, text=True).stdout
+    assert out.strip() == "True [0, 1, 2]"
+
+
+@pytest.fixture(scope="module")
+def polar_isa():
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("hipcc not present")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_store_hazard as chk
+    return chk, chk.build(os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "polar.hip"))
+
+
+def test_batched_kernels_have_no_scratch_and_no_store_hazard(polar_isa):
+    chk, files = polar_isa
+    assert files
+    seen = []
+    for f in files:
+        for name, r in chk.resources(f).items():
+            if "k_step_batch" in name or "k_forces_batch" in name:
+                seen.append(name)
+                assert r.get("private_seg_size", 0) == 0, (name, r)
+        assert chk.check(f)[1] == []
+    assert sum("k_step_batch" in n for n in seen) == 4 and sum("k_forces_batch" in n for n in seen) == 2, seen

@@ -90,9 +90,10 @@ def resources(path):
     return out
 
 
-def build():
+def build(src=None):
+    """Compile `src` (default: csrc/windtunnel.hip) for gfx950 with --save-temps; returns the device .s files."""
     tmp = tempfile.mkdtemp(prefix="wt_isa_")
-    src = os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "windtunnel.hip")
+    src = src or os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "windtunnel.hip")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "--save-temps",
            "-c", src, "-o", os.path.join(tmp, "wt.o")]
     subprocess.run(cmd, cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

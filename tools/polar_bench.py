@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Batched sweeps (libwtpolar.so) against the same member-steps on sequential single handles: one JSON line per (lattice, B).
+
+    python tools/polar_bench.py [--sizes 320x160,1024x512] [--members 1,8,32,64] [--steps 200] [--warmup 50]
+
+Per line: us per batched step and member-steps per second (host clock around wtp_step + wtp_sync, after a warm-up), aggregate
+GLUPS, algorithmic bytes per step (72 B per site fp32, + 12 B per site on the emitting last step of a call) over the time as a
+fraction of 8 TB/s, and the same member-steps taken by B libwindtunnel handles stepped one after another (library defaults),
+timed in the same process.  Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import airfoil_cfd_tool_amd as pkg       # noqa: E402
+
+PEAK_BPS = 8.0e12
+TAU, U0 = 0.58, 0.06
+
+
+def _masks(nx, ny, b):
+    alphas = np.linspace(-4.0, 12.0, b) if b > 1 else np.array([6.0])
+    return np.stack([pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412").mask for a in alphas])
+
+
+def bench_batch(nx, ny, b, steps, warmup, masks):
+    with pkg.PolarEngine(nx, ny, b) as eng:
+        eng.set_masks(masks)
+        eng.init_equilibrium(U0)
+        eng.step(warmup, TAU, U0)
+        eng.sync()
+        t0 = time.perf_counter()
+        eng.step(steps, TAU, U0)
+        eng.sync()
+        return time.perf_counter() - t0
+
+
+def bench_sequential(nx, ny, b, steps, warmup, masks):
+    hs = []
+    try:
+        for m in range(b):
+            e = pkg.Engine(nx, ny)
+            hs.append(e)
+            e.set_mask(masks[m])
+            e.init_equilibrium(U0)
+        for e in hs:
+            e.step(warmup, TAU, U0)
+        for e in hs:
+            e.sync()
+        t0 = time.perf_counter()
+        for e in hs:
+            e.step(steps, TAU, U0)
+        for e in hs:
+            e.sync()
+        return time.perf_counter() - t0
+    finally:
+        for e in hs:
+            e.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="320x160,1024x512")
+    ap.add_argument("--members", default="1,8,32,64")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--no-sequential", action="store_true", help="time the batch only")
+    a = ap.parse_args()
+    for size in a.sizes.split(","):
+        nx, ny = (int(v) for v in size.split("x"))
+        for b in (int(v) for v in a.members.split(",")):
+            masks = _masks(nx, ny, b)
+            sites = nx * ny
+            t = bench_batch(nx, ny, b, a.steps, a.warmup, masks)
+            us = t / a.steps * 1e6
+            ms_per_s = b * a.steps / t
+            bytes_step = b * sites * (72 + 12 / a.steps)
+            line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
+                    "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
+                    "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
+            if not a.no_sequential:
+                ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
+                line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
+                line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
+                line["speedup_vs_sequential"] = round(ts / t, 2)
+            print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
