@@ -1,43 +1,19 @@
-// step_march.hpp — TWO lattice steps per launch over the WHOLE lattice, body included.
+// step_march.hpp — what every marching kernel (k_march3, step_march3.hpp / step_chain.hpp) shares: the classes of the window tiles, the
+// bounce codes, the unit and parameter records, the vector and buffer helpers, the collision of S sites per lane, step 1 of a column and
+// the host-side unit planners.
 //
-// Templated on the element type T and the sites per lane S (vector of S * sizeof(T) bytes per lane and direction):
-//   <float, 4>  16-byte vectors, 256-row windows — wide fp32 lattices (the bench configuration);
-//   <double, 2> 16-byte vectors, 128-row windows — fp64 lattices;
-//   <float, 2>   8-byte vectors, 128-row windows — narrow fp32 lattices (column slabs), where 256-row windows give too
-//               few units to fill the chip.
-// Below, "256 rows" stands for WIN = 64 * S.
-//
-// A wave owns a WINDOW of 256 rows (j, the fast axis) and marches along a CHUNK of columns (i).
-// Per iteration it (1) requests the 9 streamed input vectors of column c+2 (software prefetch),
-// (2) runs step 1 (STEP_FS main(), html:283-360) for column c+1 on the vectors requested one
-// iteration earlier, (3) runs step 2 for column c from the step-1 populations of columns c-1, c, c+1,
-// which never leave the register file (the +-1 shifts along j are lane shuffles), (4) stores 9 vectors.
-// HBM words per TWO site updates: 9 (L+2)/L + 9 instead of 18 + 18.
-//
-// Windows are 256 rows tall and 256 rows apart, so every access of a wave is one whole, 1-KiB-aligned
-// kilobyte (measured with the arithmetic removed: a 252-row window pitch — overlapping windows that
-// recompute their seam rows — costs 13-20 % of the pass time in line straddles and partial-line stores).
-// What step 2 of a window's first and last row needs from the rows just outside the window — the step-1
-// populations 2,5,6 of the row below and 4,7,8 of the row above — comes from a small table H that
-// k_halo_rows fills before each pass (two rows per window seam, per-site code with every branch of
-// STEP_FS); a wave fetches its six values per column with one dword load, one iteration ahead.
-//
-// The whole lattice is marched by ONE kernel (BODY = true; the BODY = false instantiation — plain fluid only —
-// exists for tools/kmarch, where it measured no faster).  Round 1 sent everything near the body through a
-// third lattice in two single-step passes; here each window-tile (column x, window w) has a class
-//     (k_classify_windows, wave ballots):
-//     FAST = no solid site in its 3 x 258 neighbourhood, SOLID = every own site solid, GENERAL = the rest;
-//     a unit reads the classes of its columns once (one byte per lane, two ballots -> two 64-bit scalars)
-//     and dispatches per column on a scalar bit test.  GENERAL tiles read one dword of solid flags and
-//     one dword of BOUNCE CODES per lane (bit k-1 = the upstream neighbour of direction k is solid;
-//     k_bounce_codes, once per mask upload) in place of the reference's nine mask texel reads
-//     (html:324-334); the sites' own populations (step 1: nine aligned 16-B loads, step 2: the step-1
-//     vectors of column c kept in registers) supply the bounced values.  The inlet (html:314-322) and
-//     outlet (html:301-312) columns are marched too: the outlet column NX-1 is emitted while column
-//     NX-2 is processed (its step-2 value is the step-1 state of NX-2).
-// Addressing: buffer instructions — one resource descriptor per lattice in scalar registers, ONE
-// per-lane byte offset for all 18 streams, the plane/column part of every address is a scalar add.
+// A wave owns a WINDOW of 64 S rows (j, the fast axis; S sites per lane, one 8-byte vector per lane and direction — fp32 S = 2, fp64 S = 1)
+// and marches along a UNIT of columns (i), advancing several lattice steps per pass with the intermediate levels held in registers.
+// Every window-tile (column x, window w) has a class (k_classify_windows, wave ballots):
+//     FAST = no solid site in its 3 x (64 S + 2) neighbourhood, SOLID = every own site solid, GENERAL = the rest;
+//     a unit reads the classes of its columns once and dispatches per column on a scalar bit test.  GENERAL tiles read one word of solid
+//     flags and one word of BOUNCE CODES per lane (bit k-1 = the upstream neighbour of direction k is solid; k_bounce_codes, once per mask
+//     upload) in place of the reference's nine mask texel reads (html:324-334); the sites' own populations supply the bounced values.
+//     The inlet (html:314-322) and outlet (html:301-312) columns are marched too: the outlet column NX-1 is emitted with column NX-2.
+// Addressing: buffer instructions — one resource descriptor per lattice in scalar registers, ONE per-lane byte offset for all 18 streams,
+// the plane/column part of every address is a scalar add.
 // Every site is computed by exactly the arithmetic of k_step: results are bit-identical.
+// (Round 2's two-step kernel lived here too; it was retired once k_march3 ran passes of every length on its own tables — DESIGN.md §7a.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,7 +30,7 @@
 
 namespace wt {
 
-static constexpr int MARCH_MAX_CHUNK = 60;       // two-step kernel: class bytes of columns ia-1 .. ib+1 must fit one wave (one ballot)
+static constexpr int MARCH_MAX_CHUNK = 60;       // two-step tables: the unit length of round 2's two-step kernel (one ballot of class bits), kept so that their plans stay as they were
 static constexpr int MARCH3_MAX_CHUNK = 124;     // three / four steps per pass: two ballots (ClassMask), columns ia-PAD .. ib+PAD-1 <= 128
 
 // classes of up to 128 consecutive columns of a window, one bit each (lane l of the first ballot <-> the first column + l, of the second + 64 + l)
@@ -129,28 +105,8 @@ __global__ __launch_bounds__(256) void k_bounce_codes(const uint8_t *__restrict_
     }
 }
 
-// seam_plain[(b - 1) * nxl + x] = 1 <=> both sites next to seam b in column x (rows 256b-1 and 256b) are plain interior
-// fluid: not solid, no solid neighbour, not on an inlet / outlet column or the top row.  The halo kernels then read one
-// coalesced byte instead of four scattered mask / code bytes per thread.
-__global__ __launch_bounds__(256) void k_seam_flags(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ bcode, uint8_t *__restrict__ seam_plain,
-                                                    Geom g, int nwin, int win)
-{
-    const long total = (long)(nwin - 1) * g.nxl;
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
-    const int x = (int)(t % g.nxl);
-    const int b = 1 + (int)(t / g.nxl);
-    const int j = win * b - 1;
-    const uint8_t *m = mask + g.pitch;
-    const long c = (long)x * g.pitch + j;
-    const int gi = x + g.gi0;
-    bool plain = false;
-    if (j + 1 < g.ny - 1 && gi > 0 && gi < g.nx_g - 1) plain = bcode[c] == 0 && bcode[c + 1] == 0 && m[c] == 0 && m[c + 1] == 0;
-    seam_plain[t] = plain ? 1 : 0;
-}
-
 // ------------------------------------------------------------------------------------------------
-// once per pass: the halo table
+// once per pass: the halo kernels' fall-back (k_halo3 / k_halo4, step_march3.hpp)
 // ------------------------------------------------------------------------------------------------
 // One lattice site, step 1 only, every branch of STEP_FS main() (html:283-360) in the reference's order —
 // the arithmetic of site_general (kernels.hpp) with the relaxation of collide_t.
@@ -179,100 +135,6 @@ __device__ __forceinline__ void site_step1(const T *__restrict__ s, const uint8_
     }
 }
 
-// H[(b * (nxl+2) + x + 1) * 8 + ...], seam b = 1 .. nwin-1 lies between rows WIN*b-1 and WIN*b:
-//   [0..2] = step-1 populations 2,5,6 of row WIN*b-1 (they move up into window b),
-//   [4..6] = step-1 populations 4,7,8 of row WIN*b   (they move down into window b-1).
-// One thread per (seam, column) computes both rows.  Plain fluid sites (no solid neighbour, interior column — the
-// seam flags say so) take nine 4-element loads: rows WIN*b-2 .. WIN*b+1 of each direction's upstream column hold every
-// input of the two sites; anything else falls back to site_step1.  The loads are a gather (neighbouring threads are
-// one column = pitch elements apart); that, not the arithmetic, is this kernel's cost.
-template <typename T, int FD>
-__global__ __launch_bounds__(256) void k_halo_rows(const T *__restrict__ fs, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ seam_plain,
-                                                   T *__restrict__ halo, Geom g, int nwin, int win, FastDiv fdv, T tau, T U0)
-{
-    const long total = (long)(nwin - 1) * g.nxl;
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= total) return;
-    // neighbouring threads take the seams of ONE column, one window apart (neighbouring columns, a pitch apart, measured
-    // the same: the kernel is bound by the rate of scattered 64-byte fetches, ~130 MB of them per 4096^2 fp32 lattice)
-    const int b = 1 + (int)(t % (nwin - 1));
-    const int x = (int)(t / (nwin - 1));
-    const int j = win * b - 1;                       // rows j (below the seam) and j + 1 (above it)
-    if (j >= g.ny) return;
-    const T *s = fs + g.pitch;
-    const uint8_t *m = mask + g.pitch;
-    const long c = (long)x * g.pitch + j;
-    T lo[9], hi[9];
-    const bool two = (j + 1 < g.ny);
-    const bool plain = seam_plain[(long)(b - 1) * g.nxl + x] != 0;
-    if (plain) {
-        typedef T q4u __attribute__((ext_vector_type(4), aligned(sizeof(T))));
-        T a[9], d[9], rho, ux, uy;
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const q4u q = *reinterpret_cast<const q4u *>(s + k * g.plane + c - (long)ex_of(k) * g.pitch - 1);     // rows j-1 .. j+2
-            a[k] = q[1 - ey_of(k)];      // input of row j
-            d[k] = q[2 - ey_of(k)];      // input of row j+1
-        }
-        collide_t<T, FD>(a, fdv, tau, lo, rho, ux, uy);
-        collide_t<T, FD>(d, fdv, tau, hi, rho, ux, uy);
-    } else {
-        site_step1<T, FD>(s, m, g, x, j, fdv, tau, U0, lo);
-        if (two) site_step1<T, FD>(s, m, g, x, j + 1, fdv, tau, U0, hi);
-        else {
-#pragma unroll
-            for (int k = 0; k < 9; k++) hi[k] = T(0);
-        }
-    }
-    typedef T t4 __attribute__((ext_vector_type(4)));
-    t4 *rec = reinterpret_cast<t4 *>(halo + ((long)b * (g.nxl + 2) + x + 1) * 8);
-    rec[0] = t4{lo[2], lo[5], lo[6], T(0)};
-    rec[1] = t4{hi[4], hi[7], hi[8], T(0)};
-}
-
-// The same table from the seam buffer S that the PREVIOUS marching pass wrote beside the lattice it produced (valid
-// only then: the library tracks it).  One thread per (seam, column, SIDE): side 0 = the row below the seam (its step-1
-// populations 2,5,6 move up), side 1 = the row above it (4,7,8 move down) — twice the threads of k_halo_rows, because
-// this kernel is latency-bound (a 4096^2 lattice has only 61 440 (seam, column) pairs).  Neighbouring threads read
-// neighbouring 48-element records: coalesced, 13 MB instead of a 130 MB gather.  Sites near the body / on the inlet and
-// outlet columns fall back to site_step1 on the lattice.
-template <typename T, int FD>
-__global__ __launch_bounds__(256) void k_halo_from_seams(const T *__restrict__ fs, const T *__restrict__ seams, const uint8_t *__restrict__ mask,
-                                                         const uint8_t *__restrict__ seam_plain, T *__restrict__ halo, Geom g, int nwin, int win,
-                                                         FastDiv fdv, T tau, T U0)
-{
-    const long total = (long)(nwin - 1) * g.nxl;
-    const long t2 = (long)blockIdx.x * 256 + threadIdx.x;
-    const int side = (int)(t2 & 1);
-    const long t = t2 >> 1;
-    if (t >= total) return;
-    const int x = (int)(t % g.nxl);
-    const int b = 1 + (int)(t / g.nxl);
-    const int j = win * b - 1 + side;                // side 0: row win*b-1, side 1: row win*b
-    T o[9];
-    if (j >= g.ny) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) o[k] = T(0);
-    } else if (seam_plain[t] != 0) {
-        T a[9], rho, ux, uy;
-        const T *rec = seams + ((long)b * (g.nxl + 2) + x + 1) * 48;
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            // record of the upstream column: slot k = {row win*b-2, row win*b-1 | +24: row win*b, row win*b+1}; the input of
-            // row r for direction k is row r - ey_k
-            const T *r = rec - (long)ex_of(k) * 48 + 2 * k;
-            const int q = 1 + side - ey_of(k);       // 0..3 over the four rows around the seam
-            a[k] = r[(q >> 1) * 24 + (q & 1)];
-        }
-        collide_t<T, FD>(a, fdv, tau, o, rho, ux, uy);
-    } else {
-        site_step1<T, FD>(fs + g.pitch, mask + g.pitch, g, x, j, fdv, tau, U0, o);
-    }
-    typedef T t4 __attribute__((ext_vector_type(4)));
-    t4 *out = reinterpret_cast<t4 *>(halo + ((long)b * (g.nxl + 2) + x + 1) * 8);
-    out[side] = side ? t4{o[4], o[7], o[8], T(0)} : t4{o[2], o[5], o[6], T(0)};
-}
-
 // ------------------------------------------------------------------------------------------------
 // units
 // ------------------------------------------------------------------------------------------------
@@ -287,9 +149,8 @@ struct MarchParams {
     const uint8_t *mask;       // padded byte mask (column -1 first)
     const uint8_t *bcode;      // bounce codes, column 0 first
     const uint8_t *wcls;       // window-tile classes [nwin][nxl + 2]
-    const T *halo;             // H[nwin + 1][nxl + 2][8], see k_halo_rows
-    const T *hlines;           // k_march3 (step_march3.hpp): the halo lines HL[nwin + 1][nxl + 2][32], levels 0 .. depth-1 of every (seam, column)
-    T *seams;                  // S[nwin + 1][nxl + 2][2][24]: the rows around every window seam of the DESTINATION lattice, see k_halo_from_seams
+    const T *hlines;           // the halo lines HL[nwin + 1][nxl + 2][32] (step_march3.hpp), levels 0 .. depth-1 of every (seam, column)
+    T *seams;                  // S3[nwin + 1][nxl + 2][M3_SREC]: the rows around every window seam of the DESTINATION lattice (step_march3.hpp)
     const MarchUnit *units;
     int nunits;
     Geom g;
@@ -330,28 +191,7 @@ __device__ __forceinline__ float wave_down(float x) { return __int_as_float(dpp_
 __device__ __forceinline__ double wave_up(double x) { return __hiloint2double(dpp_wave_up(__double2hiint(x)), dpp_wave_up(__double2loint(x))); }
 __device__ __forceinline__ double wave_down(double x) { return __hiloint2double(dpp_wave_down(__double2hiint(x)), dpp_wave_down(__double2loint(x))); }
 
-// value at j-1 / j+1 taken from the neighbouring lane
-// (lane 0 / lane 63 take the value of the row outside the window from the halo table: `edge`, wave-uniform)
-template <typename T, int S> __device__ __forceinline__ MV<T, S> m_below(const MV<T, S> &r, int lane, T edge)
-{
-    MV<T, S> o;
-    const T n = wave_up(r.v[S - 1]);
-    o.v[0] = lane == 0 ? edge : n;
-#pragma unroll
-    for (int v = 1; v < S; v++) o.v[v] = r.v[v - 1];
-    return o;
-}
-template <typename T, int S> __device__ __forceinline__ MV<T, S> m_above(const MV<T, S> &r, int lane, T edge)
-{
-    MV<T, S> o;
-    const T n = wave_down(r.v[0]);
-#pragma unroll
-    for (int v = 0; v < S - 1; v++) o.v[v] = r.v[v + 1];
-    o.v[S - 1] = lane == 63 ? edge : n;
-    return o;
-}
-
-// The same with the row outside the window taken straight out of the column's halo register `hv` (step_march3.hpp: lanes 0..15 hold the words that
+// The values at rows j-1 / j+1 of a lane's sites (shifted by one lane), the row outside the window taken straight out of the column's halo register `hv` (step_march3.hpp: lanes 0..15 hold the words that
 // come from below, lanes 48..63 those from above) by a ROW shift — lane N into lane 0 (resp. lane 48 + P into lane 63) — and the wave shift then leaving
 // that lane alone: two data-parallel-primitive moves per direction instead of a v_readlane, a move and a select (the kernel is bound by the number of
 // vector instructions it issues, and the six wave-uniform edge values of every stage no longer pass through scalar registers).
@@ -440,43 +280,23 @@ __device__ __forceinline__ MV<T, S> bload(__amdgpu_buffer_rsrc_t r, unsigned vof
     }
     return o;
 }
-// returns the raw data registers of the store, for store_data_fence()
 template <typename T, int S>
-__device__ __forceinline__ typename RawOf<S * sizeof(T)>::type bstore(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const MV<T, S> &v)
+__device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const MV<T, S> &v)
 {
     typename RawOf<S * sizeof(T)>::type x;
     __builtin_memcpy(&x, &v, S * sizeof(T));
     if constexpr (S * sizeof(T) == 16) __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, WT_STORE_AUX);
     else __builtin_amdgcn_raw_buffer_store_b64(x, r, voff, soff, WT_STORE_AUX);
-    return x;
-}
-// two elements (one seam slot)
-template <typename T>
-__device__ __forceinline__ typename RawOf<2 * sizeof(T)>::type bstore2(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, T a, T b)
-{
-    typename RawOf<2 * sizeof(T)>::type x;
-    const T ab[2] = {a, b};
-    __builtin_memcpy(&x, ab, 2 * sizeof(T));
-    if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b64(x, r, voff, soff, 0);
-    return x;
 }
 // STORE-DATA HAZARD (measured on MI355X, ROCm 7.2): a buffer_store_dwordx4 whose soffset is an SGPR reads its data
 // VGPRs a little after it issues.  A VALU instruction right behind it that overwrites one of them can win that race for
 // the last lanes of each 16-lane group when the memory pipe is backed up — the store then writes the NEW register
 // contents (seen as 4-lane groups of wrong macro values at the outlet column of a 16384 x 4096 lattice, nowhere else
 // and not on every run).  hipcc pads this hazard only for stores WITHOUT a register soffset (LLVM GCNHazardRecognizer::
-// createsVALUHazard), so the pad is ours: the asm keeps every data tuple of a store group live up to this point and
-// its `s_nop 1` gives the two wait states after the group's last store.  tools/check_store_hazard.py verifies the
-// generated ISA (run by tests/test_build_hazards.py).  (8-byte stores have no such hazard; the fence is harmless there.)
-template <typename R>
-__device__ __forceinline__ void store_data_fence(const R (&d)[12], int n)
-{
-    if (n == 12)
-        asm volatile("s_nop 1" ::"v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]), "v"(d[8]), "v"(d[9]), "v"(d[10]), "v"(d[11]));
-    else
-        asm volatile("s_nop 1" ::"v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]), "v"(d[8]));
-}
+// createsVALUHazard), so the pad is ours: the asm keeps the data tuples of a pair of 16-byte stores (the seam records,
+// step_march3.hpp seam3_flush) live up to this point and its `s_nop 1` gives the two wait states after the second.
+// tools/check_store_hazard.py verifies the generated ISA (run by tests/test_build_hazards.py).  (8-byte stores — the
+// lattice's — have no such hazard; the fence is empty for them.)
 template <typename R>
 __device__ __forceinline__ void store_data_fence2(const R &a, const R &b)
 {
@@ -488,9 +308,6 @@ struct MarchAddr {
     __amdgpu_buffer_rsrc_t rs, rd, rm;   // source lattice, destination lattice, macro planes
     unsigned voff;                       // j0 * sizeof(T)
     unsigned voff_st;                    // the same for stores; lanes beyond the last row: out of range (dropped by the buffer check)
-    __amdgpu_buffer_rsrc_t rseam;        // seam buffer S
-    unsigned voff_lo, voff_hi;           // lanes 0..11: byte offsets of their slot in the two half records this window writes; other lanes: out of range
-    T *lds_w, *lds_r;                    // this lane's LDS address for staging (write) and for the transposed read-back
     int lane;
     unsigned P4, pitch4, mp4;            // plane / column / macro-plane strides in bytes
     char *own_lds;                       // k_march3, general (BODY) units: this wave's two LDS buffers for a column's own populations (own_prefetch); else null
@@ -504,22 +321,7 @@ __device__ __forceinline__ unsigned lat_off(const MarchAddr<T, S> &a, int k, int
     return (unsigned)k * a.P4 + (unsigned)(col + 1) * a.pitch4 + (unsigned)(dj * (int)sizeof(T));
 }
 
-// the nine streamed (pulled) input vectors of column `col`
-template <typename T, int S>
-__device__ __forceinline__ void march_load_stream(const MarchAddr<T, S> &a, int col, MV<T, S> (&fin)[9])
-{
-    fin[0] = bload<T, S>(a.rs, a.voff, lat_off(a, 0, col, 0));
-    fin[1] = bload<T, S>(a.rs, a.voff, lat_off(a, 1, col - 1, 0));
-    fin[3] = bload<T, S>(a.rs, a.voff, lat_off(a, 3, col + 1, 0));
-    fin[2] = bload<T, S>(a.rs, a.voff, lat_off(a, 2, col, -1));
-    fin[5] = bload<T, S>(a.rs, a.voff, lat_off(a, 5, col - 1, -1));
-    fin[6] = bload<T, S>(a.rs, a.voff, lat_off(a, 6, col + 1, -1));
-    fin[4] = bload<T, S>(a.rs, a.voff, lat_off(a, 4, col, 1));
-    fin[7] = bload<T, S>(a.rs, a.voff, lat_off(a, 7, col + 1, 1));
-    fin[8] = bload<T, S>(a.rs, a.voff, lat_off(a, 8, col - 1, 1));
-}
-
-// The same nine inputs WITHOUT the row shift (k_march3): every load is the window's own 64 S rows of the upstream column — 4 whole 128-byte
+// The nine streamed (pulled) input vectors of column `col`, loaded WITHOUT the row shift: every load is the window's own 64 S rows of the upstream column — 4 whole 128-byte
 // lines (fp32) instead of 5, the fifth being a line of the neighbouring window that its wave fetches as well.  The shift by one row happens
 // in registers (march_align_in), the row outside the window comes from the column's halo line (level-0 words, step_march3.hpp).
 // Measured before: 46.7 line requests per column and window against 36 + 1 (profiles/r04_u_fetch_calibration.txt).
@@ -838,76 +640,6 @@ __device__ __forceinline__ void march_outlet_macro(const MV<T, S> (&q9)[9], MV<T
     }
 }
 
-// store the window's rows of column `col`.  No branch: lanes beyond the last row carry an out-of-range offset and
-// the buffer range check drops their stores.  (A divergent `if (row < NY)` around the stores makes hipcc's waitcnt
-// pass merge the "stored" and "not stored" paths and drain vmcnt to 0 at the loop tail — every iteration then waits
-// for its own nine stores to complete before the next one starts.)
-template <bool EMIT, typename T, int S>
-__device__ __forceinline__ void march_store(const MarchAddr<T, S> &a, int col, const MV<T, S> (&out)[9], const MV<T, S> (&mac)[3])
-{
-    typename RawOf<S * sizeof(T)>::type d[12];
-#pragma unroll
-    for (int k = 0; k < 9; k++) d[k] = bstore<T, S>(a.rd, a.voff_st, lat_off(a, k, col, 0), out[k]);
-    if (EMIT) {
-        const unsigned mo = (unsigned)col * a.pitch4;
-#pragma unroll
-        for (int q = 0; q < 3; q++) d[9 + q] = bstore<T, S>(a.rm, a.voff_st, (unsigned)q * a.mp4 + mo, mac[q]);
-    }
-    store_data_fence(d, EMIT ? 12 : 9);
-    // The two rows on either side of the window seams go, once more, into the seam buffer S (lane 0 holds rows 0,1 — above
-    // seam w; lane 63 the window's last two rows — below seam w+1).  They pass through LDS so that 12 lanes write each half
-    // record as contiguous, sector-aligned bytes (whole memory sectors: two-lane stores straight from lanes 0 / 63 cost more
-    // than the table saves — partial sectors are read-modify-written).  Software-pipelined: this call only STAGES the
-    // values (one LDS write per direction, every lane, no branch: lanes 1..62 hit a scratch slot); seam_fetch() at the
-    // top of the next iteration reads them back transposed and seam_flush() stores them beside that iteration's stores,
-    // so no LDS latency is exposed.  The next pass builds its halo table from S with coalesced loads
-    // (k_halo_from_seams) instead of a gather (k_halo_rows).
-    typedef T t2 __attribute__((ext_vector_type(2)));
-    const bool top = a.lane == 63;
-#pragma unroll
-    for (int k = 0; k < 9; k++)
-        *reinterpret_cast<t2 *>(a.lds_w + 2 * k) = t2{top ? out[k].v[S - 2] : out[k].v[0], top ? out[k].v[S - 1] : out[k].v[1]};
-}
-
-// seam values staged by the previous march_store, transposed: lane k < 9 gets direction k's pair of rows
-template <typename T> struct SeamPair { T below[2], above[2]; };
-template <typename T, int S>
-__device__ __forceinline__ SeamPair<T> seam_fetch(const MarchAddr<T, S> &a)
-{
-    typedef T t2 __attribute__((ext_vector_type(2)));
-    SeamPair<T> r;
-    const t2 b = *reinterpret_cast<const t2 *>(a.lds_r);          // the window's last two rows (staged by lane 63)
-    const t2 t = *reinterpret_cast<const t2 *>(a.lds_r + 24);     // rows 0,1                   (staged by lane 0)
-    r.below[0] = b[0]; r.below[1] = b[1]; r.above[0] = t[0]; r.above[1] = t[1];
-    return r;
-}
-template <typename T, int S>
-__device__ __forceinline__ void seam_flush(const MarchAddr<T, S> &a, int col, const SeamPair<T> &r)
-{
-    const unsigned so = (unsigned)(col + 1) * (unsigned)(48 * sizeof(T));
-    const auto d0 = bstore2<T>(a.rseam, a.voff_hi, so, r.below[0], r.below[1]);        // -> seam w+1, half 0
-    const auto d1 = bstore2<T>(a.rseam, a.voff_lo, so, r.above[0], r.above[1]);        // -> seam w,   half 1
-    store_data_fence2(d0, d1);
-}
-
-// wave-uniform value of lane l of a halo-table word
-template <typename T> __device__ __forceinline__ T readlane_t(T x, int l)
-{
-    if constexpr (sizeof(T) == 4) return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), l));
-    else {
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)__double2loint(x), l), hi = __builtin_amdgcn_readlane((unsigned)__double2hiint(x), l);
-        return __hiloint2double((int)hi, (int)lo);
-    }
-}
-template <typename T> __device__ __forceinline__ T halo_load(__amdgpu_buffer_rsrc_t rh, unsigned hoff, unsigned soff)
-{
-    if constexpr (sizeof(T) == 4) return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rh, hoff, soff, 0));
-    else {
-        const u2v x = __builtin_amdgcn_raw_buffer_load_b64(rh, hoff, soff, 0);
-        return __hiloint2double((int)x.y, (int)x.x);
-    }
-}
-
 // march_load_aligned's inputs of one column -> the streamed (pulled) inputs: populations 2,5,6 come from one row below, 4,7,8 from one row above;
 // `hv` = the column's halo words, level 0 in lanes 12..14 (from below) and 60..62 (from above)
 template <bool OVL = false, typename T, int S>
@@ -920,7 +652,11 @@ __device__ __forceinline__ void march_align_in(MV<T, S> (&in)[9], int lane, T hv
 template <bool OVL, typename T> __device__ __forceinline__ T halo_load_x(__amdgpu_buffer_rsrc_t rh, unsigned hoff, unsigned soff)
 {
     if constexpr (OVL) return T(0);
-    else return halo_load<T>(rh, hoff, soff);
+    else if constexpr (sizeof(T) == 4) return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rh, hoff, soff, 0));
+    else {
+        const u2v x = __builtin_amdgcn_raw_buffer_load_b64(rh, hoff, soff, 0);
+        return __hiloint2double((int)x.y, (int)x.x);
+    }
 }
 
 // ---- a general column's OWN populations, prefetched into LDS (round 5) ----
@@ -959,7 +695,7 @@ __device__ __forceinline__ MV<T, S> own_read(const char *buf, int k, int lane)
 
 // Step 1 of column x -> G (all nine directions).  `in` holds the streamed inputs of column x (modified in place).
 // OWN_LDS: the column's own populations (general columns only) are in the LDS buffer `own_buf`, requested by own_prefetch — one iteration ago in the
-// units' loops, just now for a unit's first columns; false (the two-step kernel): they are loaded here.
+// units' loops, just now for a unit's first columns; false (the two-step passes, march_unit3_d2): they are loaded here.
 // `pre` (optional): the column's solid flags and bounce codes {solid4, code4}, fetched ahead by the caller (SiteBytes below)
 template <bool BODY, int FD, typename T, int S, bool OWN_LDS = false>
 __device__ __forceinline__ void march_step1(const MarchParams<T> &p, const MarchAddr<T, S> &a, int x, int j0, bool far_win, bool nonfast, bool allsolid,
@@ -1011,185 +747,12 @@ __device__ __forceinline__ void march_step1(const MarchParams<T> &p, const March
     if (far_win) march_far_rows<T, S, false>(j0, p.g.ny, p.U0, feq0, G, mac);
 }
 
-// One unit: marched columns [ia, ib) of window w.  BODY = false: the unit's footprint is plain interior fluid — no
-// class tests, no mask, no inlet / outlet logic, fewer live registers (no spills); BODY = true: everything.
-template <bool BODY, bool EMIT, int FD, typename T, int S>
-__device__ __forceinline__ void march_unit(const MarchParams<T> &p, MarchAddr<T, S> &a, __amdgpu_buffer_rsrc_t rh, unsigned hoff, int ia, int ib, int uflags,
-                                           int j0, int lane, bool far_win, unsigned long long nonfast_m, unsigned long long solid_m,
-                                           const T (&feq0)[9])
-{
-    typedef MV<T, S> V;
-    const Geom &g = p.g;
-    constexpr unsigned HREC = 8 * sizeof(T);     // bytes of one halo-table record
-#define NONFAST(x) (BODY && ((nonfast_m >> ((x) - ia + 1)) & 1ULL) != 0)
-#define ALLSOLID(x) (BODY && ((solid_m >> ((x) - ia + 1)) & 1ULL) != 0)
-#define STEP1(x, in, G) march_step1<BODY, FD, T, S>(p, a, (x), j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G)
-
-    V G158m[3];                  // step-1 populations 1,5,8 of column c-1
-    V Gc[9];                     // step-1 populations of column c (BODY = false: only 0,2,4 and 1,5,8 stay live)
-    V in[9], G[9], mac[3];
-    if (!BODY || ia + g.gi0 > 0) {        // column ia-1 exists (ia = 0 on the inlet side: its step 2 is the far field)
-        march_load_stream(a, ia - 1, in);
-        STEP1(ia - 1, in, G);
-        G158m[0] = G[1]; G158m[1] = G[5]; G158m[2] = G[8];
-    } else {
-        G158m[0] = mv_splat<T, S>(feq0[1]); G158m[1] = mv_splat<T, S>(feq0[5]); G158m[2] = mv_splat<T, S>(feq0[8]);
-    }
-    march_load_stream(a, ia, in);
-    STEP1(ia, in, Gc);
-    march_load_stream(a, ia + 1, in);
-    T hv = halo_load<T>(rh, hoff, (unsigned)ia * HREC);
-    int seam_col = -1;           // column whose seam rows are staged in LDS (-1: none yet; the flush then lands on the pad record)
-#pragma unroll 1
-    for (int c = ia; c < ib; c++) {
-        V nxt[9];
-        march_load_stream(a, (c + 2 <= ib) ? c + 2 : c + 1, nxt);             // prefetch (last one: harmless re-load)
-        const T hv_next = halo_load<T>(rh, hoff, (unsigned)(c + 1) * HREC);
-        const SeamPair<T> sp = seam_fetch(a);                                 // staged by the previous iteration's march_store
-        STEP1(c + 1, in, G);                                                  // step 1 of column c+1
-        const T hb2 = readlane_t(hv, 0), hb5 = readlane_t(hv, 1), hb6 = readlane_t(hv, 2), ha4 = readlane_t(hv, 3), ha7 = readlane_t(hv, 4),
-                ha8 = readlane_t(hv, 5);
-        // ---- step 2 of column c
-        V fin[9], out[9];
-        fin[0] = Gc[0]; fin[1] = G158m[0]; fin[3] = G[3];
-        fin[2] = m_below(Gc[2], lane, hb2); fin[5] = m_below(G158m[1], lane, hb5); fin[6] = m_below(G[6], lane, hb6);
-        fin[4] = m_above(Gc[4], lane, ha4); fin[8] = m_above(G158m[2], lane, ha8); fin[7] = m_above(G[7], lane, ha7);
-        bool plain = true;
-        if (BODY) {
-            const int gi = c + g.gi0;
-            const bool nf = NONFAST(c);
-            if (__builtin_expect(gi <= 0 || nf, 0)) {
-                plain = false;
-                auto ownc = [&](int k) { return Gc[k]; };
-                uint32_t solid4 = 0, code4 = 0;
-                if (nf) {
-                    solid4 = load_site_bytes<S>(p.mask + (long)(c + 1) * g.pitch + j0);
-                    code4 = load_site_bytes<S>(p.bcode + (long)c * g.pitch + j0);
-                }
-                const bool any_solid = __ballot(solid4 != 0) != 0ULL;
-                if (gi <= 0) {
-#pragma unroll
-                    for (int k = 0; k < 9; k++) out[k] = mv_splat<T, S>(feq0[k]);
-                    if (EMIT) { mac[0] = mv_splat<T, S>(T(1)); mac[1] = mv_splat<T, S>(p.U0); mac[2] = mv_splat<T, S>(T(0)); }
-                } else if (ALLSOLID(c)) {
-#pragma unroll
-                    for (int k = 0; k < 9; k++) out[k] = Gc[k];        // every site is overwritten by march_solid below
-                    if (EMIT) { mac[0] = mv_splat<T, S>(T(1)); mac[1] = mv_splat<T, S>(T(0)); mac[2] = mv_splat<T, S>(T(0)); }
-                } else {
-                    march_bounce<T, S>(fin, code4, ownc);
-                    march_collide_general<T, S, FD, EMIT>(fin, solid4, j0, g.ny, p.fdv, p.tau, p.U0, feq0, out, mac);
-                }
-                if (any_solid && (gi <= 0 || ALLSOLID(c))) march_solid<T, S, EMIT>(out, mac, solid4, ownc);
-            }
-        }
-        if (plain) {
-            march_collide<T, S, FD, EMIT>(fin, p.fdv, p.tau, out, mac);
-            if (far_win) march_far_rows<T, S, EMIT>(j0, g.ny, p.U0, feq0, out, mac);
-        }
-        march_store<EMIT>(a, c, out, mac);
-        seam_flush(a, seam_col, sp);
-        seam_col = c;
-        if (BODY && __builtin_expect((uflags & MU_OUTLET_AFTER) && c + 1 == ib, 0)) {
-            // outlet column NX-1 (html:301-312): its step-2 value is the step-1 state of column NX-2 (= Gc), its own
-            // step-1 state (solid sites only) is G
-            uint32_t solid4 = 0;
-            if (NONFAST(c + 1)) solid4 = load_site_bytes<S>(p.mask + (long)(c + 2) * g.pitch + j0);
-            auto ownp = [&](int k) { return G[k]; };
-#pragma unroll
-            for (int k = 0; k < 9; k++) out[k] = Gc[k];
-            if (EMIT) march_outlet_macro(Gc, mac);
-            if (__ballot(solid4 != 0) != 0ULL) march_solid<T, S, EMIT>(out, mac, solid4, ownp);
-            seam_flush(a, seam_col, seam_fetch(a));          // column c's seam rows, before the staging area is reused
-            march_store<EMIT>(a, c + 1, out, mac);
-            seam_col = c + 1;
-        }
-        G158m[0] = Gc[1]; G158m[1] = Gc[5]; G158m[2] = Gc[8];
-#pragma unroll
-        for (int k = 0; k < 9; k++) { Gc[k] = G[k]; in[k] = nxt[k]; }
-        hv = hv_next;
-    }
-    seam_flush(a, seam_col, seam_fetch(a));
-#undef NONFAST
-#undef ALLSOLID
-#undef STEP1
-}
-
-template <typename T, int S, bool EMIT, int FD>
-__global__ __launch_bounds__(256, 2) void k_march(MarchParams<T> p)
-{
-    constexpr int WIN = 64 * S;
-    constexpr unsigned EB = sizeof(T);
-    const Geom &g = p.g;
-    const int lane = threadIdx.x & 63;
-    int u = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (u >= p.nunits) return;
-    if (p.rev & 1) u = p.nunits - 1 - u;
-    const MarchUnit un = p.units[u];
-    const int ia = __builtin_amdgcn_readfirstlane(un.ia), ib = __builtin_amdgcn_readfirstlane(un.ib);
-    const int w = __builtin_amdgcn_readfirstlane(un.w), uflags = __builtin_amdgcn_readfirstlane(un.flags);
-    if (ib <= ia) return;                                          // padding unit (keeps the block -> XCD pattern of the list)
-    const int row0 = w * WIN;
-    const int j0 = row0 + lane * S;
-    const bool far_win = (w == 0) || (row0 + WIN >= g.ny);         // the window holds row 0 or row NY-1
-    MarchAddr<T, S> a;
-    a.rs = march_rsrc(p.fs, p.lat_bytes);
-    a.rd = march_rsrc(p.fd, p.lat_bytes);
-    a.rm = march_rsrc(p.macro, (unsigned)(3u * (unsigned)g.nxl * (unsigned)g.pitch * EB));
-    a.voff = (unsigned)((j0 < g.ny) ? j0 : row0) * EB;           // lanes beyond the last row re-read the window's first rows (cached) and store nothing
-    a.voff_st = (j0 < g.ny) ? (unsigned)j0 * EB : p.lat_bytes;    // >= num_records of both the lattice and the macro buffer
-    a.P4 = (unsigned)g.plane * EB; a.pitch4 = (unsigned)g.pitch * EB; a.mp4 = (unsigned)g.nxl * (unsigned)g.pitch * EB;
-    a.own_lds = nullptr; a.voff_dma = 0;                          // (the LDS prefetch of a general column's own populations belongs to k_march3)
-    // halo table: lanes 0..5 fetch, for step 2 of column c, {G2(c), G5(c-1), G6(c+1)} of the row below the window
-    // (seam w) and {G4(c), G7(c+1), G8(c-1)} of the row above it (seam w+1); record = 8 elements per (seam, column)
-    const __amdgpu_buffer_rsrc_t rh = march_rsrc(p.halo, (unsigned)((unsigned)(p.nwin_total + 1) * (unsigned)(g.nxl + 2) * 8u * EB));
-    unsigned hoff;
-    {
-        const int hl = lane < 6 ? lane : 0;
-        const int dx = (hl == 1 || hl == 5) ? -1 : ((hl == 2 || hl == 4) ? 1 : 0);
-        const int slot = hl < 3 ? hl : hl + 1;
-        const int seam = hl < 3 ? w : w + 1;
-        hoff = (unsigned)((seam * (g.nxl + 2) + 1 + dx) * 8 + slot) * EB;
-    }
-    {
-        // S record of (seam b, column x) = 48 elements: half 0 = rows WIN*b-2, WIN*b-1 (written by window b-1), half 1 = rows
-        // WIN*b, WIN*b+1 (written by window b); a half = 12 slots of 2 elements, slot k < 9 = direction k
-        // per wave: below[24] (lane 63 stages pairs 0..8, slots 9..11 stay zero), above[24] (lane 0), then a scratch area
-        // the other 62 lanes stage into (an LDS write per lane is cheaper than a branch around two-lane writes)
-        __shared__ T seam_lds[4][48 + 160];
-        T *wl = &seam_lds[threadIdx.x >> 6][0];
-        a.lane = lane;
-        a.lds_w = lane == 63 ? wl : (lane == 0 ? wl + 24 : wl + 48 + 2 * lane);
-        a.lds_r = wl + 2 * (lane < 12 ? lane : 0);
-        if (lane < 48) wl[lane] = T(0);
-        const unsigned sbytes = (unsigned)(p.nwin_total + 1) * (unsigned)(g.nxl + 2) * 48u * EB;
-        a.rseam = march_rsrc(p.seams, sbytes);
-        const unsigned rec = (unsigned)(g.nxl + 2) * 48u * EB;
-        a.voff_lo = lane < 12 ? (unsigned)w * rec + 24u * EB + (unsigned)lane * 2u * EB : sbytes;
-        a.voff_hi = lane < 12 ? (unsigned)(w + 1) * rec + (unsigned)lane * 2u * EB : sbytes;
-    }
-    T feq0[9];
-    feq_all<T>(T(1), p.U0, T(0), feq0);                           // far-field populations (html:314-322)
-
-    // classes of columns ia-1 .. ib (lane l <-> column ia-1+l): two 64-bit scalars
-    unsigned long long nonfast_m, solid_m;
-    {
-        const int n = ib - ia + 2;
-        uint8_t cls = WC_FAST;
-        if (lane < n) cls = p.wcls[(long)w * (g.nxl + 2) + ia + lane];
-        nonfast_m = __ballot(cls != WC_FAST);
-        solid_m = __ballot(cls == WC_SOLID);
-    }
-    // a unit whose whole footprint (columns ia-1 .. ib) is plain interior fluid takes the lean loop
-    const bool lean = nonfast_m == 0ULL && ia + g.gi0 >= 2 && ib + g.gi0 <= g.nx_g - 2 && !(uflags & MU_OUTLET_AFTER) && !(p.rev & 2);
-    if (lean) march_unit<false, EMIT, FD, T, S>(p, a, rh, hoff, ia, ib, uflags, j0, lane, far_win, 0ULL, 0ULL, feq0);
-    else march_unit<true, EMIT, FD, T, S>(p, a, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side: the unit lists of one mask
 // ------------------------------------------------------------------------------------------------
-// Marched column range of a handle: global edges are part of the march (inlet column 0; outlet column
-// emitted with NX-2), local slab edges are not (their ghost columns lose two columns of validity per pass).
+// Marched column range of a handle: global edges are part of the march (inlet column 0; outlet column emitted with NX-2), local slab edges are
+// not (their ghost columns lose two columns of validity per two-step pass).  The range of two-step tables; march_range3 (step_march3.hpp) gives
+// that of any depth.
 struct MarchRange { int i_begin, i_end, outlet_after; };
 static inline MarchRange march_range(const Geom &g)
 {
@@ -1238,7 +801,7 @@ static inline MarchPlan build_march_plan(const uint8_t *wcls, const Geom &g, int
         if (target_units < nwin) target_units = nwin;
         target = total / (double)target_units;
     }
-    if (target > (double)max_len) target = (double)max_len;      // a unit's class bytes must fit one wave
+    if (target > (double)max_len) target = (double)max_len;      // the kernel's unit length limit (MARCH_MAX_CHUNK / MARCH3_MAX_CHUNK)
     if (target < 1.0) target = 1.0;
     pl.chunk = (int)(target + 0.5);
     for (int w = 0; w < nwin; w++) {

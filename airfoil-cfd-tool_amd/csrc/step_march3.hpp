@@ -1,9 +1,9 @@
-// step_march3.hpp — THREE or FOUR lattice steps per pass: 8-byte vectors per lane and direction —
+// step_march3.hpp — TWO, THREE or FOUR lattice steps per pass: 8-byte vectors per lane and direction —
 //   <float, 2>  fp32, 2 sites per lane, 128-row windows (the fp32 default);
 //   <double, 1> fp64, 1 site per lane, 64-row windows.
 // Below, "128 rows" stands for WIN = 64 * S.
 //
-// Why: the SQ counters of the two-step kernel (profiles/r02_c_sq_counters.txt) show its vector-memory issue stalled on a
+// Why: the SQ counters of round 2's two-step kernel (since retired; profiles/r02_c_sq_counters.txt) show its vector-memory issue stalled on a
 // full texture-addresser command FIFO for about as many cycles as the kernel runs, with the vector ALU 30 % busy — it is
 // bound by the per-CU load/store path (~10 B/clk/CU of L1-miss traffic, the same limit k_step sits on), not by
 // arithmetic.  The lever left is bytes per step: a pass that advances T steps moves 9 (L + 2(T-1))/L + 9 words
@@ -369,7 +369,7 @@ __device__ unsigned long long g_m3_stamps[8];
 
 template <typename T, int S>
 struct March3Addr {
-    MarchAddr<T, S> a;                   // lattice / macro descriptors and offsets (its seam fields are unused here)
+    MarchAddr<T, S> a;                   // lattice / macro descriptors and offsets
     __amdgpu_buffer_rsrc_t rs3;          // seam buffer S3
     unsigned voff_lo, voff_hi;           // lanes 0 .. 10 sizeof(T)/4 - 1: byte offsets of their 16-byte chunk in the two half records this window writes
     T *lds_w;                            // where this lane stages its S rows of direction 0 (direction k: + 4 k elements)
@@ -433,11 +433,11 @@ __device__ __forceinline__ void march3_store(const March3Addr<T, S> &m, unsigned
 {
     const MarchAddr<T, S> &a = m.a;
 #pragma unroll
-    for (int k = 0; k < 9; k++) (void)bstore<T, S>(a.rd, voff_st, lat_off(a, k, col, 0), out[k]);
+    for (int k = 0; k < 9; k++) bstore<T, S>(a.rd, voff_st, lat_off(a, k, col, 0), out[k]);
     if (EMIT) {
         const unsigned mo = (unsigned)col * a.pitch4;
 #pragma unroll
-        for (int q = 0; q < 3; q++) (void)bstore<T, S>(a.rm, voff_st, (unsigned)q * a.mp4 + mo, mac[q]);
+        for (int q = 0; q < 3; q++) bstore<T, S>(a.rm, voff_st, (unsigned)q * a.mp4 + mo, mac[q]);
     }
     if constexpr (!OVL) {            // (overlapping windows keep no seam buffer)
 #pragma unroll
@@ -815,8 +815,8 @@ __device__ __forceinline__ void march_unit4(const MarchParams<T> &p, March3Addr<
 #undef LCOL
 }
 
-// The same machinery stopped after level 2: TWO steps per pass on the tables of the three-step plan (units, classes, halo lines, seam
-// buffer S3), for the one or two steps a step count leaves over after its three-step passes.
+// The same machinery stopped after level 2: TWO steps per pass on the tables of the plan (units, classes, halo lines, seam buffer S3) — the
+// two steps a step count leaves over after its three- / four-step passes, and every pass of a two-step plan (fuse_depth = 2).
 template <bool BODY, bool EMIT, int FD, typename T, int S>
 __device__ __forceinline__ void march_unit3_d2(const MarchParams<T> &p, March3Addr<T, S> &m, __amdgpu_buffer_rsrc_t rh, unsigned hoff, int ia, int ib,
                                                int uflags, int j0, int lane, bool far_win, ClassMask nonfast_m, ClassMask solid_m,
@@ -890,8 +890,8 @@ __device__ __forceinline__ void march_unit3_d2(const MarchParams<T> &p, March3Ad
 #undef STEP1
 }
 
-// Marched column range of a three-step pass: global edges as in march_range; a local slab edge loses THREE columns of
-// validity per pass, and level 2 of column 1 would need column -2: the two columns next to a local edge are left alone.
+// Marched column range of a `depth`-step plan: global edges as in march_range (march_range3(g, 2) is march_range(g)); a local slab edge loses
+// `depth` columns of validity per pass, and level 2 of column 1 would need column -2 (depth 3): the depth - 1 columns next to a local edge are left alone.
 static inline MarchRange march_range3(const Geom &g, int depth = 3)
 {
     MarchRange r;

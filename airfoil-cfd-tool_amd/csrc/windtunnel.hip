@@ -118,18 +118,18 @@ struct wt_handle {
     int transport = TR_NONE;
     ncclComm_t comm = nullptr;
     wt_handle *peer_l = nullptr, *peer_r = nullptr;   // TR_LOCAL
-    // two-steps-per-launch mode (step_march.hpp)
+    // several steps per pass (step_march.hpp, step_march3.hpp, step_chain.hpp)
     bool fuse = false;
     int fuse_sites = 0;                  // option: sites per lane of the marching kernel (0 = automatic; 2 or 4)
     int fuse_depth = 0;                  // option: steps per pass (0 = automatic; 2 or 3)
-    int march_depth = 0;                 // steps per pass the plan's tables are built for (3 / 4: step_march3.hpp; 2: step_march.hpp)
+    int march_depth = 0;                 // steps per pass the plan's tables are built for (2, 3 or 4; step_march3.hpp)
     int pass_cap = 0;                    // longest pass actually taken on those tables (0 = march_depth): fp64 with fuse_depth = 2
     int tau_cap = 0;                     // fp32, set per stepping call: 3 when the fast division by tau is not proved for this tau (IEEE division:
                                          // the four-step kernel would spill registers and is not built for it), else 0
-    void *hlines = nullptr;              // depth 3 / 4: the halo lines of k_march3 (step_march3.hpp), one 32-element line per (window, column)
+    void *hlines = nullptr;              // the halo lines of k_march3 (step_march3.hpp), one 32-element line per (window, column)
     long long passes = 0;
     long long single_steps = 0;          // k_step launches of whole steps (option "single_steps"): what a fused plan falls back to
-    long long march_table_bytes = 0;     // wcls + halo_tab + seams + seam_plain (part of device_bytes)
+    long long march_table_bytes = 0;     // wcls + hlines + seams + seam_plain (part of device_bytes)
     int march_s = 0;                     // sites per lane in use (4: fp32 256-row windows; 2: fp64, or fp32 on narrow lattices)
     bool fuse_force = false;             // fuse_steps = 2: also when the lattice is too small for it to pay
     int fuse_chunk = 0;                  // cost limit of a unit (columns); 0 = whole resident rounds of units (build_march_plan)
@@ -137,8 +137,7 @@ struct wt_handle {
     int fuse_chunk_used = 0;
     uint8_t *bcode = nullptr;            // bounce codes, (nxl+2) * pitch
     uint8_t *wcls = nullptr;             // window-tile classes, nwin * (nxl+2)
-    void *halo_tab = nullptr;            // halo table of the two-step marching kernel, (nwin+1) * (nxl+2) * 8 elements (depth 3 / 4: hlines)
-    void *seams = nullptr;               // seam rows written by a marching pass beside its output lattice, (nwin+1) * (nxl+2) * 48 elements
+    void *seams = nullptr;               // seam rows written by a marching pass beside its output lattice, (nwin+1) * (nxl+2) * M3_SREC elements
     uint8_t *seam_plain = nullptr;       // per (seam, column): both sites next to the seam are plain interior fluid, (nwin-1) * nxl
     bool seams_valid = false;            // `seams` describes lattice f[cur] (set by a marching pass, cleared by everything else that writes f)
     MarchUnit *d_units = nullptr;
@@ -354,7 +353,7 @@ static int create_impl(int nx_g, int ny, int dtype, int device, int rank, int nr
     CREATE_TRY(hipStreamSynchronize(h->s_compute));
 #undef CREATE_TRY
     {
-        // Two steps per pass (step_march.hpp): on by default, engaging only where the plan has enough units to pay
+        // Several steps per pass (step_march3.hpp): on by default, engaging only where the plan has enough units to pay
         // (fuse_steps = 1: whole lattices from about 1000 x 4096 up; one-GPU measurements of slab-sized lattices:
         // 2080 columns 98 -> 79 us per step, 1056 columns 53 -> 47, 544 columns no gain and left on the single-step
         // kernel).  Slabs march between ghost refreshes, the refresh step itself stays a single step with the exchange
@@ -408,7 +407,7 @@ extern "C" int wt_destroy(wt_handle *h)
     if (h->stage) (void)hipFree(h->stage);
     if (h->bcode) (void)hipFree(h->bcode);
     if (h->wcls) (void)hipFree(h->wcls);
-    if (h->halo_tab) (void)hipFree(h->halo_tab);
+    if (h->hlines) (void)hipFree(h->hlines);
     if (h->seams) (void)hipFree(h->seams);
     if (h->seam_plain) (void)hipFree(h->seam_plain);
     if (h->d_units) (void)hipFree(h->d_units);
@@ -495,7 +494,7 @@ extern "C" int wt_sync(wt_handle *h)
 }
 
 // ------------------------------------------------------------------------------------------
-// two-steps-per-launch plan (step_march.hpp)
+// several-steps-per-pass plan (step_march.hpp, step_march3.hpp)
 // ------------------------------------------------------------------------------------------
 // whole lattices and column slabs alike (a slab plans over its LOCAL columns, ghosts included); the
 // marching kernels address a lattice through one 32-bit buffer descriptor
@@ -526,7 +525,6 @@ static inline int eff_depth(const wt_handle *h)
 static void free_march_tables(wt_handle *h)
 {
     if (h->wcls) { (void)hipFree(h->wcls); h->wcls = nullptr; }
-    if (h->halo_tab) { (void)hipFree(h->halo_tab); h->halo_tab = nullptr; }
     if (h->seams) { (void)hipFree(h->seams); h->seams = nullptr; }
     if (h->seam_plain) { (void)hipFree(h->seam_plain); h->seam_plain = nullptr; }
     if (h->hlines) { (void)hipFree(h->hlines); h->hlines = nullptr; }
@@ -548,7 +546,7 @@ static void cut_units(wt_handle *h, const float *colw, MarchPlan *out, const Mar
     const Geom &g = h->g;
     const int depth = h->march_depth, win = 64 * h->march_s - (h->ovl ? 8 : 0);      // (the planners want the rows from window to window: the window count)
     const long target = h->plan_target;
-    const MarchRange r = range ? *range : (depth >= 3 ? march_range3(g, depth) : march_range(g));
+    const MarchRange r = range ? *range : march_range3(g, depth);
     // four steps per pass: class masks cover ib - ia + 6 columns, and the last unit of a window marches at least two
     // cost of a column that is not plain fluid, in plain columns: 1 + alpha; `over`: columns a unit iterates over beyond its own (pipeline
     // fill and drain of a `depth`-step pass); `tail`: the outlet column's extra stages — see build_march_plan_timed
@@ -661,21 +659,15 @@ static int build_fuse_plan(wt_handle *h, int sites, long target, int depth)
     if (h->n_win != nwin || h->march_s != sites || h->march_depth != depth) free_march_tables(h);
     long long added = 0;
     if (!h->wcls) { HIP_TRY(hipMalloc((void **)&h->wcls, wbytes)); added += (long long)wbytes; }
-    if (depth < 3 && !h->halo_tab) {      // the two-step kernel's table (k_halo_rows / k_halo_from_seams)
-        const size_t hbytes = (size_t)(nwin + 1) * (g.nxl + 2) * 8 * eb;
-        HIP_TRY(hipMalloc(&h->halo_tab, hbytes));
-        HIP_TRY(hipMemsetAsync(h->halo_tab, 0, hbytes, h->s_compute));
-        added += (long long)hbytes;
-    }
     if (!h->seams) {
-        const size_t sbytes = (size_t)(nwin + 1) * (g.nxl + 2) * (depth >= 3 ? M3_SREC : 48) * eb;
+        const size_t sbytes = (size_t)(nwin + 1) * (g.nxl + 2) * M3_SREC * eb;
         HIP_TRY(hipMalloc(&h->seams, sbytes));
         HIP_TRY(hipMemsetAsync(h->seams, 0, sbytes, h->s_compute));
         h->seams_valid = false;
         added += (long long)sbytes;
     }
     if (!h->seam_plain && nwin > 1) { HIP_TRY(hipMalloc((void **)&h->seam_plain, (size_t)(nwin - 1) * g.nxl)); added += (long long)(nwin - 1) * g.nxl; }
-    if (depth >= 3 && !h->hlines) {       // k_march3's halo lines: zeroed once — the slots nobody writes (the lattice's first / last column, the
+    if (!h->hlines) {                     // k_march3's halo lines: zeroed once — the slots nobody writes (the lattice's first / last column, the
         const size_t hbytes = (size_t)(nwin + 1) * (g.nxl + 2) * M3_HL * eb;       // bottom / top window) must stay finite don't-cares
         HIP_TRY(hipMalloc(&h->hlines, hbytes));
         HIP_TRY(hipMemsetAsync(h->hlines, 0, hbytes, h->s_compute));
@@ -700,11 +692,8 @@ static int build_fuse_plan(wt_handle *h, int sites, long target, int depth)
         if (depth == 4)
             hipLaunchKernelGGL(k_seam_flags4, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
                                h->seam_plain, g, nwin, win);
-        else if (depth == 3)
+        else            // (k_halo3: the flags of two- and three-step tables)
             hipLaunchKernelGGL(k_seam_flags3, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
-                               h->seam_plain, g, nwin, win);
-        else
-            hipLaunchKernelGGL(k_seam_flags, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
                                h->seam_plain, g, nwin, win);
     }
     HIP_TRY(hipGetLastError());
@@ -718,7 +707,7 @@ static int build_fuse_plan(wt_handle *h, int sites, long target, int depth)
     MarchPlan pl;
     cut_units(h, nullptr, &pl);
     WT_TRY(upload_units(h, pl));
-    const MarchRange r = depth >= 3 ? march_range3(g, depth) : march_range(g);
+    const MarchRange r = march_range3(g, depth);
     for (int w = 0; w < nwin; w++)
         for (int x = r.i_begin; x < r.i_end; x++) h->nonfast_tiles += h->host_wcls[(size_t)w * (g.nxl + 2) + x + 1] != WC_FAST;
     return WT_OK;
@@ -741,10 +730,9 @@ static long march_target_units(const wt_handle *h, int sites, long slots, bool f
 
 // Steps per pass.  Every marching kernel holds 8-byte vectors per lane and direction (fp32: 2 sites per lane, 128-row windows; fp64: 1
 // site, 64-row windows).  THREE steps per pass (step_march3.hpp) where eligible, FOUR where the units are long; fuse_depth = 2 selects two
-// steps per pass: fp32 the two-step kernel of step_march.hpp on its own (smaller) tables — also the automatic choice for lattices too
-// narrow for three steps to pay —, fp64 two-step passes of the three-step kernel on its tables.  (Round 2 also shipped 16-byte-vector
-// instantiations of the two-step kernel — fp32 with 4 sites per lane, fp64 with 2; they spilled registers, were never the automatic
-// choice on any lattice and are gone.)  The choice depends on the geometry only, so a mask change rebuilds the tables in place.
+// steps per pass: fp32 on tables built for two steps (solo units that leave one column next to a local slab edge) — also the choice for
+// lattices too narrow for three steps —, fp64 on the three-step tables.  Every depth runs k_march3 (round 2's separate two-step kernel is
+// retired: DESIGN.md §7a).  The choice depends on the geometry only, so a mask change rebuilds the tables in place.
 static int rebuild_fuse_plan(wt_handle *h)
 {
     h->fuse_ready = false;
@@ -777,8 +765,8 @@ static int rebuild_fuse_plan(wt_handle *h)
         // 18.5 / - / 15.3 / 17.1; 1024x512, 1 per unit: 13.6 / - / 13.4 / 16.1; 512x256, 0 per unit: 9.9 / - / 11.1 / 13.5) follow the body columns.
         // fp32: three steps per pass from one column per unit up, four from eight — from five for the slabs of a split, which are mostly plain
         // and are cut by cost (the widest, plain ones set the pace); fp64: four from 12, three from four; single steps below.
-        // (Round 2's rule — two steps per pass below eight columns per unit — predates the chain blocks: the two-step kernel is never the
-        // best choice any more and runs only when fuse_depth = 2 asks for it.)
+        // (Round 2's rule — two steps per pass below eight columns per unit — predates the chain blocks: two-step tables are never the
+        // best choice any more and are built only when fuse_depth = 2 asks for them.)
         const long tiles3 = (long)(plan_nxl - 4) * march_nwin(h->g.ny, 64 * s3);
         const bool f32 = h->dtype == WT_F32;
         const long cpu = tiles3 / slots;
@@ -791,7 +779,7 @@ static int rebuild_fuse_plan(wt_handle *h)
         if (!force && h->fuse_chunk <= 0 && cpu < (f32 ? min3 : 4)) return WT_OK;
         int depth = h->fuse_depth == 4 || (h->fuse_depth == 0 && cpu >= (f32 ? min4 : 12)) ? 4 : 3;
         // The units of a depth-D plan leave the D-1 columns next to a local slab edge unwritten: those must all be GHOST columns, so a slab
-        // with fewer than D-1 of them plans shallower (halo 2: three steps per pass at most; halo 1: the two-step kernel, whose units leave one).
+        // with fewer than D-1 of them plans shallower (halo 2: three steps per pass at most; halo 1: two-step tables, whose units leave one).
         if (h->nranks > 1 && h->halo < depth - 1) depth = h->halo + 1;
         if (depth < 3) { if (f32) goto two_step; return WT_OK; }
         const MarchRange r = march_range3(h->g, depth);
@@ -1376,68 +1364,6 @@ static inline FastDiv fastdiv_params(const wt_handle *h, double tau)
     return f;
 }
 
-template <typename T, int S, bool EMIT, int FD>
-static void launch_march(const MarchParams<T> &p, hipStream_t st)
-{
-    if (p.nunits <= 0) return;
-    hipLaunchKernelGGL((k_march<T, S, EMIT, FD>), dim3((unsigned)((p.nunits + 3) / 4)), dim3(256), 0, st, p);
-}
-
-// Two steps in one pass over the lattice (step_march.hpp).  A = f[cur] (time t), B = f[1-cur] (receives time t+2).
-template <typename T, int S, int FD>
-static int step_pair_fused_t(wt_handle *h, double tau, double u0, bool emit)
-{
-    const Geom &g = h->g;
-    MarchParams<T> p;
-    p.fs = fptr<T>(h, h->cur);
-    p.fd = fptr<T>(h, 1 - h->cur);
-    p.macro = reinterpret_cast<T *>(h->macro);
-    p.mask = h->mask; p.bcode = h->bcode; p.wcls = h->wcls;
-    p.halo = reinterpret_cast<const T *>(h->halo_tab); p.seams = reinterpret_cast<T *>(h->seams);
-    p.g = g;
-    p.lat_bytes = (unsigned)((size_t)9 * g.plane * sizeof(T));
-    p.nwin_total = h->n_win;
-    p.fdv = fastdiv_params(h, tau);
-    p.tau = (T)tau;
-    p.U0 = (T)u0;
-    p.rev = (int)((h->steps_done >> 1) & 1);
-    {
-        static const int rev_mode = exp_env("WT_MARCH_REV") ? atoi(exp_env("WT_MARCH_REV")) : 2;     // experiments: 0 / 1 = fixed order
-        if (rev_mode == 0 || rev_mode == 1) p.rev = rev_mode;
-    }
-    hipStream_t st = h->s_compute;
-    if (h->n_win > 1) {        // the step-1 populations that cross the window seams
-        const long nth = (long)(h->n_win - 1) * g.nxl;
-        const dim3 grid((unsigned)((nth + 255) / 256)), block(256);
-        const uint8_t *mk = h->mask, *sp = h->seam_plain;
-        T *ht = reinterpret_cast<T *>(h->halo_tab);
-        if (h->seams_valid)     // the previous pass left the seam rows of this lattice in `seams`: coalesced loads
-            hipLaunchKernelGGL((k_halo_from_seams<T, FD>), dim3((unsigned)((2 * nth + 255) / 256)), block, 0, st, p.fs, (const T *)p.seams, mk, sp, ht, g, h->n_win, 64 * S, p.fdv, p.tau, p.U0);
-        else                    // gather from the lattice (first pass after a single step, an upload, a ghost refresh)
-            hipLaunchKernelGGL((k_halo_rows<T, FD>), grid, block, 0, st, p.fs, mk, sp, ht, g, h->n_win, 64 * S, p.fdv, p.tau, p.U0);
-    }
-    p.units = h->d_units; p.nunits = h->n_units;
-    if (emit) launch_march<T, S, true, FD>(p, st);
-    else launch_march<T, S, false, FD>(p, st);
-    HIP_TRY(hipGetLastError());
-    h->cur = 1 - h->cur;
-    h->steps_done += 2;
-    h->passes += 1;
-    h->passes_total += 1;
-    h->seams_valid = true;                       // the pass wrote the seam rows of the lattice it produced
-    if (h->nranks > 1) h->ghost_valid -= 2;      // two columns of ghost validity consumed
-    return WT_OK;
-}
-
-static int step_pair_fused(wt_handle *h, double tau, double u0, bool emit)
-{
-    if (h->dtype != WT_F32 || h->march_s != 2) return fail(WT_ERR_STATE, "internal: the two-step kernel runs fp32 handles with 2 sites per lane only");
-    if (h->fast_math) return step_pair_fused_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit);
-    bool fd = false;
-    WT_TRY(fastdiv_for(h, (float)tau, &fd));
-    return fd ? step_pair_fused_t<float, 2, 1>(h, tau, u0, emit) : step_pair_fused_t<float, 2, 0>(h, tau, u0, emit);
-}
-
 static inline bool tune_due(const wt_handle *h, int nsteps)
 {
     return !h->plan_tuned && nsteps >= 2 && h->fuse_ready && (!h->tune_deferred || h->passes_total - h->passes_at_mask >= TUNE_LIVE_PASSES);
@@ -1502,7 +1428,7 @@ static void march3_params(wt_handle *h, double tau, double u0, MarchParams<T> &p
     p.fd = fptr<T>(h, 1 - h->cur);
     p.macro = reinterpret_cast<T *>(h->macro);
     p.mask = h->mask; p.bcode = h->bcode; p.wcls = h->wcls;
-    p.halo = nullptr; p.hlines = reinterpret_cast<const T *>(h->hlines);
+    p.hlines = reinterpret_cast<const T *>(h->hlines);
     p.seams = reinterpret_cast<T *>(h->seams);
     p.g = g;
     p.lat_bytes = (unsigned)((size_t)9 * g.plane * sizeof(T));
@@ -1577,7 +1503,7 @@ static int launch_march3(const MarchParams<T> &p, int depth, bool emit, bool two
     return WT_OK;
 }
 
-// Three steps in one pass (step_march3.hpp), or two on the same tables (depth = 2: what a step count leaves over).
+// `depth` steps in one pass (step_march3.hpp): the plan's own depth, or a shorter pass on the same tables (what a step count leaves over).
 // A = f[cur] (time t), B = f[1-cur] (receives time t + depth).
 template <typename T, int S, int FD>
 static int step_triple_fused_t(wt_handle *h, double tau, double u0, bool emit, int depth, bool two_op = false)
@@ -1590,8 +1516,8 @@ static int step_triple_fused_t(wt_handle *h, double tau, double u0, bool emit, i
 #endif
     hipStream_t st = h->s_compute;
     launch_halo_lines<T, S, FD>(h, p, h->seams_valid ? 1 : 0, 0, -1, st);
-    if (h->nranks > 1 && h->trim && !h->clk_on) {
-        // ghost columns that will still be exact after this pass: the others are not marched (trim_plan_for)
+    if (h->nranks > 1 && h->trim && !h->clk_on && h->march_depth >= 3) {
+        // ghost columns that will still be exact after this pass: the others are not marched (trim_plan_for; not on two-step plans)
         const int v_full = h->halo - (h->march_depth - 1), v_after = std::max(0, std::min(h->ghost_valid - depth, v_full));
         if (v_after < v_full) {
             const MarchUnit *tu = nullptr;
@@ -1744,7 +1670,7 @@ static int renew_strips_t(wt_handle *h, double tau, double u0, bool emit, int de
 static inline int fuse_pick(int depth, int avail)
 {
     if (avail < 2) return 0;
-    if (depth <= 2) return 2;                                   // the two-step kernel (step_march.hpp) has no shorter pass
+    if (depth <= 2) return 2;                                   // a two-step plan has no shorter pass
     if (avail >= depth) return (avail - depth == 1) ? depth - 1 : depth;
     return avail;
 }
@@ -1760,14 +1686,11 @@ static inline int fuse_stride(const wt_handle *h, int left)
 
 static int step_fused(wt_handle *h, double tau, double u0, bool emit, int k)
 {
-    if (h->march_depth >= 3) {
-        if (h->dtype != WT_F32) return step_triple_fused_t<double, 1, 1>(h, tau, u0, emit, k);      // (FD 1: the guarded four-operation division, switched by fdv.on64)
-        if (h->fast_math) return step_triple_fused_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit, k);
-        bool fd = false, fd2 = false;
-        WT_TRY(fastdiv_for(h, (float)tau, &fd, &fd2));
-        return fd ? step_triple_fused_t<float, 2, 1>(h, tau, u0, emit, k, fd2) : step_triple_fused_t<float, 2, 0>(h, tau, u0, emit, k);
-    }
-    return step_pair_fused(h, tau, u0, emit);
+    if (h->dtype != WT_F32) return step_triple_fused_t<double, 1, 1>(h, tau, u0, emit, k);      // (FD 1: the guarded four-operation division, switched by fdv.on64)
+    if (h->fast_math) return step_triple_fused_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit, k);
+    bool fd = false, fd2 = false;
+    WT_TRY(fastdiv_for(h, (float)tau, &fd, &fd2));
+    return fd ? step_triple_fused_t<float, 2, 1>(h, tau, u0, emit, k, fd2) : step_triple_fused_t<float, 2, 0>(h, tau, u0, emit, k);
 }
 
 // refresh = 2: is the next thing a slab does a fused renewal — a pass of k > 0 steps with the exchange beside its interior columns?
@@ -2144,7 +2067,7 @@ extern "C" int wt_plan_steps(wt_handle *h, int nsteps, double tau, int *seq, int
         int code;
         if (k > 0) {
             code = k;
-            if (h->nranks > 1) h->ghost_valid = std::max(0, std::min(h->ghost_valid - k, h->march_depth >= 3 ? h->halo - (h->march_depth - 1) : h->ghost_valid - k));
+            if (h->nranks > 1) h->ghost_valid = std::max(0, std::min(h->ghost_valid - k, h->halo - (h->march_depth - 1)));
             s += k;
         } else {
             const bool refresh = needs_halo(h);

@@ -99,8 +99,8 @@ WT_API const char *wt_version(void);
 
 /* Tuning knobs (no counterpart in the reference).  Every setting but "fast_math" gives bit-identical results.
  *   "fuse_steps" (0 / 1 = where it pays / 2 = always): advance SEVERAL steps per pass over the lattice — marching kernels that keep
- *       the intermediate steps in registers, body / inlet / outlet included (csrc/step_march.hpp: two steps, csrc/step_march3.hpp:
- *       three and four, csrc/step_chain.hpp: the same with workgroups whose units share their edge columns).  fp32 (even NY) and
+ *       the intermediate steps in registers, body / inlet / outlet included (csrc/step_march3.hpp: two, three and four steps,
+ *       csrc/step_chain.hpp: the same with workgroups whose units share their edge columns; csrc/step_march.hpp: what they share).  fp32 (even NY) and
  *       fp64 handles, whole lattices and slabs, with at least 8 local columns and a lattice below 4 GiB.  Default 1 (environment
  *       WT_FUSE2=0|1|2 overrides at wt_create); handles that are not eligible, or too small for it to pay, stay on k_step.
  *   "fuse_depth" (0 = automatic / 2 / 3 / 4): steps per pass.  Automatic, by columns per resident unit: fp32 3 from one, 4 from eight

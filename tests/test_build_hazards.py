@@ -1,5 +1,5 @@
 """The generated gfx950 ISA must not contain the buffer-store data hazard hipcc leaves unpadded
-(store_data_fence() in csrc/step_march.hpp; tools/check_store_hazard.py)."""
+(store_data_fence2() in csrc/step_march.hpp; tools/check_store_hazard.py)."""
 import os
 import subprocess
 import sys

@@ -1,4 +1,4 @@
-"""GPU: the two-steps-per-launch mode (csrc/step_march.hpp) must be bit-identical to the ordinary
+"""GPU: the several-steps-per-pass mode (k_march3, csrc/step_march3.hpp) must be bit-identical to the ordinary
 single-step path and to the oracle: plain units (register-resident step 1 -> step 2), body units
 (window-tile classes, bounce codes, inlet / outlet columns inside the march), odd/even step counts,
 macro emission, mask changes, chunk sizes, the proved fast division by tau and its IEEE fallback; every
@@ -151,12 +151,16 @@ def test_fused_not_available(pkg):
         e.step(5, 0.58, 0.06)
         assert e.get_option("fuse_active") == 1.0 and e.get_option("fuse_depth") == 2 and e.get_option("fuse_sites") == 1
         assert e.get_option("single_steps") == 1.0      # 7 = 3 + 2 + 2, then 5 = 2 + 2 + 1
+    narrow = np.zeros((64, 12), np.uint8); narrow[28:36, 5:7] = 1
     with pkg.Engine(12, 64) as e:                   # fewer than 16 columns: two steps per pass at most
         with pytest.raises(pkg.WTError):
             e.set_option("fuse_depth", 3)
         e.set_option("fuse_steps", 2)
-        e.set_mask(np.zeros((64, 12), np.uint8)); e.init_equilibrium(0.06); e.step(5, 0.58, 0.06)
+        e.set_mask(narrow); e.init_equilibrium(0.06); e.step(5, 0.58, 0.06)
         assert e.get_option("fuse_active") == 1.0 and e.get_option("fuse_depth") == 2
+        f1, m1 = e.read_f(), e.read_macro()
+    f0, m0, _ = _run(pkg, narrow, [5], 0.58, 0.06, False)
+    assert bits_equal(f0, f1) and all(bits_equal(a, b) for a, b in zip(m0, m1))
     with pkg.Engine(256, 129) as e:                 # odd NY: no vector width divides it
         with pytest.raises(pkg.WTError):
             e.set_option("fuse_steps", 2)
@@ -220,10 +224,10 @@ def test_long_run_fused_equals_single_step_and_stays_finite(pkg):
     (2, 2, 512, 256, [9], "float32", 2, 3),              # halo 2: never three exact ghost columns -> single steps only
     (8, 16, 4096, 256, [50], "float32", 0, 0),           # automatic choice
     (2, 2, 2304, 4096, [9, 6], "float32", 0, 0),         # wide slabs would plan four steps per pass, but two ghost columns allow three at most
-    (2, 1, 2304, 4096, [5], "float32", 0, 0),            # one ghost column: the two-step kernel's tables (its units leave one column), no fused pass fits
+    (2, 1, 2304, 4096, [5], "float32", 0, 0),            # one ghost column: two-step tables (their units leave one column), no fused pass fits
 ])
 def test_fused_slabs_equal_single_lattice(pkg, nranks, halo, nx, ny, chunks, dtype, sites, depth):
-    """Two-steps-per-launch on column slabs (in-process transport): a pair needs two exact ghost
+    """Fused passes on column slabs (in-process transport): a pair needs two exact ghost
     columns, refresh steps stay single; results equal the plain single lattice bit for bit."""
     mask = _body(pkg, nx, ny, "naca2412", 7.0)
     f0, m0, _ = _run(pkg, mask, chunks, 0.58, 0.06, False, dtype=dtype)

@@ -1,5 +1,5 @@
 """GPU: seeded random lattices, masks and parameters against the C oracle, with and without the
-two-steps-per-launch mode.  Random speckle/blocks masks hit tile-class and window-seam corner cases
+several-steps-per-pass mode.  Random speckle/blocks masks hit tile-class and window-seam corner cases
 that airfoil shapes do not."""
 import numpy as np
 import pytest

@@ -1,7 +1,7 @@
 // kstorehazard.hip — is there a store-data hazard behind buffer_store_dwordx4 with an SGPR soffset on gfx950?
 //
 // Round 2 saw wrong macro values in 4-lane groups at the outlet column of a 16384 x 4096 lattice, not on every run, and attributed them to a
-// buffer_store_dwordx4 whose data VGPRs were overwritten by the next VALU instruction (store_data_fence() in csrc/step_march.hpp; LLVM pads
+// buffer_store_dwordx4 whose data VGPRs were overwritten by the next VALU instruction (store_data_fence2() in csrc/step_march.hpp; LLVM pads
 // that overwrite only for stores WITHOUT a register soffset).  This micro-kernel isolates the claim: every wave stores {a,a,a,a} tuples with
 //     buffer_store_dwordx4 v[10:13], voff, rsrc, SOFF offen        (SOFF: an SGPR, or the immediate 0)
 // and overwrites v11 and v13 with b in the very next instructions (PAD wait states in between); thousands of waves do that back to back so that

@@ -7,12 +7,11 @@ run, one --pmc WRITE_SIZE run) into the files kept under profiles/:
     pmc_traffic.json           the entry bench.py reports as roofline.traffic (+ where and when it was measured)
 
     python tools/summarize_profile.py <tag> <key> <trace.db> <fetch.db> <write.db>
-        key, e.g. 4096x4096_float32_march3  (bench.py: "<nx>x<ny>_<dtype>" + "_march" / "_march3" for the two- / three-steps-per-pass kernel)
+        key, e.g. 4096x4096_float32_march3  (bench.py: "<nx>x<ny>_<dtype>" + "_march" / "_march3" / "_march4" for two / three / four steps per pass)
 
 HBM bytes follow MI355X_MICROARCH.md §HBM: FETCH_SIZE (KB) x 1024 x 2 on gfx950 (the counter tallies 128-B requests
 at 64 B for wide coalesced reads), WRITE_SIZE (KB) x 1024; the two counters do not fit one pass, hence two runs.
-One "launch" of the marching path = k_march<false, FD> (non-emitting pass) + the k_halo_from_seams launch before it
-(the first pass after an init / a single step builds its halo table with k_halo_rows instead: once per run, not counted).
+One "launch" of the marching path = k_march3<T, S, depth, false, FD> (non-emitting pass) + the k_halo3 / k_halo4 launch before it.
 """
 import csv
 import datetime
@@ -59,21 +58,16 @@ def main():
             v = dur[k]
             w.writerow([k, len(v), sum(v), f"{sum(v) / len(v):.1f}", f"{100.0 * sum(v) / total:.2f}", min(v), max(v)])
     fe, wr = counters(fetch_db), counters(write_db)
-    march = "_march" in key
-    march3 = key.endswith("_march3")
-    march4 = key.endswith("_march4")
+    depth = 4 if key.endswith("_march4") else 3 if key.endswith("_march3") else 2 if "_march" in key else 0
+    halo = "wt::k_halo4<" if depth == 4 else "wt::k_halo3<"
     rows = []
     fetch_kb = write_kb = 0.0
     for k in sorted(set(fe) | set(wr)):
         f = fe.get(k, {}).get("FETCH_SIZE")
         wv = wr.get(k, {}).get("WRITE_SIZE")
         rows.append([k, f, wv])
-        if march4:
-            use = ((k.startswith("wt::k_march3<") and ",4,false," in k) or k.startswith("wt::k_halo4<"))
-        elif march3:
-            use = ((k.startswith("wt::k_march3<") and ",3,false," in k) or k.startswith("wt::k_halo3<"))
-        elif march:
-            use = ((k.startswith("wt::k_march<") and ",false," in k) or k.startswith("wt::k_halo_from_seams"))
+        if depth:
+            use = (k.startswith("wt::k_march3<") and f",{depth},false," in k) or k.startswith(halo)
         else:
             use = k.startswith("wt::k_step<") and ",false," in k
         if use:
@@ -90,9 +84,7 @@ def main():
     data = json.load(open(path)) if os.path.exists(path) else {}
     data[key] = {
         "hbm_bytes_per_launch": fetch + write, "fetch_bytes_corrected": fetch, "write_bytes": write,
-        "kernel": ("one pass = wt::k_halo4 + wt::k_march3<T,S,4,false,FD> (FOUR steps)" if march4 else
-                   "one pass = wt::k_halo3 + wt::k_march3<T,S,3,false,FD> (THREE steps)" if march3 else
-                   "one pass = wt::k_halo_from_seams + wt::k_march<T,S,false,FD> (TWO steps)" if march else "wt::k_step<float,false,...> (non-emitting step)"),
+        "kernel": (f"one pass = {halo[:-1]} + wt::k_march3<T,S,{depth},false,FD> ({['', '', 'TWO', 'THREE', 'FOUR'][depth]} steps)" if depth else "wt::k_step<float,false,...> (non-emitting step)"),
         "measured": datetime.date.today().isoformat() + ", rocprofv3 --pmc on one MI355X box of the gpurun pool, `python bench.py` default workload, "
                     "separate passes for FETCH_SIZE and WRITE_SIZE (not the run that prints the bench line)",
         "source": f"profiles/{tag}_pmc_traffic.csv: FETCH_SIZE KB x1024 x2 (gfx950 correction, MI355X_MICROARCH.md HBM section) + WRITE_SIZE KB x1024",
