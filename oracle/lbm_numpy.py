@@ -229,6 +229,123 @@ def field_scalar(mode, rho, ux, uy, solid, u0, max_s, cp_min, cp_max, vort_scale
     return t
 
 
+# html:371-388 colour stops (0..255), html:389-393 vortColor, html:397 solid colour
+SPEED_STOPS = ((5, 5, 20), (0, 20, 120), (0, 60, 200), (0, 140, 220), (0, 220, 220),
+               (0, 210, 140), (80, 200, 0), (220, 210, 0), (255, 120, 0), (220, 20, 0))
+CP_STOPS = ((20, 50, 160), (40, 110, 210), (100, 175, 235), (190, 220, 245),
+            (248, 248, 248), (248, 214, 140), (240, 150, 60), (205, 50, 25))
+VORT_BASE, VORT_NEG, VORT_POS = (0.06, 0.07, 0.11), (0.15, 0.5, 0.98), (0.98, 0.28, 0.18)
+SOLID_RGB = (0.039, 0.043, 0.078)
+
+
+def _lerp_stops(t, stops, T):
+    """clamp(t,0,1), f = t*nseg, stop index floor(f) (taken in double) kept in [0, nseg-1], mix(a,b,u) = a*(1-u)+b*u."""
+    st = np.asarray(stops, dtype=T) / T(255.0)
+    nseg = len(stops) - 1
+    t = np.where(t < T(0.0), T(0.0), t)
+    t = np.where(T(1.0) < t, T(1.0), t).astype(T)
+    f = t * T(nseg)
+    with np.errstate(invalid="ignore"):
+        i = np.clip(np.floor(f.astype(np.float64)), 0, nseg - 1)
+    i = np.nan_to_num(i).astype(np.int64)
+    u = (f - i.astype(T))[..., None]
+    return st[i] * (T(1.0) - u) + st[i + 1] * u
+
+
+def render_rgb(mode, t, solid):
+    """RENDER_FS colour of the scalar `t` (field_scalar's output), evaluated in t's dtype: the speed (mode 0) and Cp
+    (mode 1) colour maps, vortColor (mode 2, t clamped to [-1, 1]), the flat solid colour on solids.  [NY][NX][3]."""
+    T = t.dtype.type
+    if mode == 0:
+        rgb = _lerp_stops(t, SPEED_STOPS, T)
+    elif mode == 1:
+        rgb = _lerp_stops(t, CP_STOPS, T)
+    elif mode == 2:
+        tc = np.where(t < T(-1.0), T(-1.0), t)
+        tc = np.where(T(1.0) < tc, T(1.0), tc).astype(T)
+        neg = (tc < T(0.0))[..., None]
+        a = np.where(tc < T(0.0), -tc, tc)[..., None]
+        col = np.where(neg, np.asarray(VORT_NEG, T), np.asarray(VORT_POS, T))
+        rgb = np.asarray(VORT_BASE, T) * (T(1.0) - a) + col * a
+    else:
+        raise ValueError("mode must be 0 (speed), 1 (cp) or 2 (vort)")
+    rgb = rgb.astype(T)
+    rgb[solid != 0] = np.asarray(SOLID_RGB, T)
+    return rgb
+
+
+def render_rgba8(mode, t, solid):
+    """render_rgb quantised like a GL RGBA8 framebuffer: (int)(clamp(c,0,1)*255 + 0.5) in double, alpha 255."""
+    c = np.clip(render_rgb(mode, t, solid).astype(np.float64), 0.0, 1.0)
+    out = np.full(c.shape[:-1] + (4,), 255, np.uint8)
+    out[..., :3] = (c * 255.0 + 0.5).astype(np.int64)
+    return out
+
+
+def sample_uv(ux, uy, solid, u0, window, wx, wy):
+    """html:616-639 sampleUV for arrays of world points, in doubles: Ufield = Float32Array(ux/U0) (likewise V), solids
+    skipped, bilinear weights of the four corners (ix,iy), (ix+1,iy), (ix,iy+1), (ix+1,iy+1) renormalised over the
+    corners that count.  ix is kept in [0, NX-2] (iy in [0, NY-2]) while tx = fx - ix is not clamped.
+    Returns (u, v, ok); u = v = 0 where not ok (outside the window, or no corner counted)."""
+    ny, nx = ux.shape
+    dx0, dx1, dy0, dy1 = (float(v) for v in window)
+    wx = np.asarray(wx, np.float64)
+    wy = np.asarray(wy, np.float64)
+    inside = ~((wx < dx0) | (wx > dx1) | (wy < dy0) | (wy > dy1))
+    with np.errstate(all="ignore"):
+        fx = np.where(inside, (wx - dx0) / (dx1 - dx0) * nx - 0.5, 0.0)
+        fy = np.where(inside, (wy - dy0) / (dy1 - dy0) * ny - 0.5, 0.0)
+    ix = np.clip(np.floor(fx), 0, nx - 2).astype(np.int64)
+    iy = np.clip(np.floor(fy), 0, ny - 2).astype(np.int64)
+    tx, ty = fx - ix, fy - iy
+    ws = ((1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty)
+    U = (ux.astype(np.float64) / float(u0)).astype(np.float32).astype(np.float64)
+    V = (uy.astype(np.float64) / float(u0)).astype(np.float32).astype(np.float64)
+    su, wu, sv, wv = (np.zeros(wx.shape) for _ in range(4))
+    for w, cx, cy in zip(ws, (ix, ix + 1, ix, ix + 1), (iy, iy, iy + 1, iy + 1)):
+        fluid = solid[cy, cx] == 0
+        Uc, Vc = U[cy, cx], V[cy, cx]
+        use = fluid & np.isfinite(Uc)
+        su, wu = np.where(use, su + Uc * w, su), np.where(use, wu + w, wu)
+        use = fluid & np.isfinite(Vc)
+        sv, wv = np.where(use, sv + Vc * w, sv), np.where(use, wv + w, wv)
+    ok = inside & (wu > 0) & (wv > 0)
+    with np.errstate(all="ignore"):
+        u = np.where(ok, su / wu, 0.0)
+        v = np.where(ok, sv / wv, 0.0)
+    return u, v, ok
+
+
+def advect(ux, uy, solid, u0, window, x, y, dt_frame):
+    """html:758-771 advect(): a midpoint step of kBase = 0.00105*dt_frame, shortened so that no particle moves more than
+    0.05 (dtEff = 0.05 / max(speed, 1e-6)); the first sample stands in when the midpoint has none.
+    Returns (x_new, y_new, speed, ok); a particle without a first sample keeps its position, speed 0."""
+    x = np.asarray(x, np.float64)
+    y = np.asarray(y, np.float64)
+    u1, v1, ok = sample_uv(ux, uy, solid, u0, window, x, y)
+    k_base = 0.00105 * dt_frame
+    speed1 = np.hypot(u1, v1)
+    dt_eff = np.where(speed1 * k_base > 0.05, 0.05 / np.fmax(speed1, 1e-6), k_base)
+    midx = x + u1 * dt_eff * 0.5
+    midy = y + v1 * dt_eff * 0.5
+    u2, v2, ok2 = sample_uv(ux, uy, solid, u0, window, midx, midy)
+    u2, v2 = np.where(ok2, u2, u1), np.where(ok2, v2, v1)
+    xn = np.where(ok, x + u2 * dt_eff, x)
+    yn = np.where(ok, y + v2 * dt_eff, y)
+    return xn, yn, np.where(ok, np.hypot(u2, v2), 0.0), ok
+
+
+def clamp_events(rho, ux, uy, solid):
+    """Fluid sites at the stability net (html:344-350): (stored rho equal to 0.5 or 2.0 in its own precision, stored
+    |u|^2 >= 0.35^2 (1 - 1e-6) in double)."""
+    fluid = solid == 0
+    T = rho.dtype.type
+    u = ux.astype(np.float64)
+    v = uy.astype(np.float64)
+    return (int(((rho == T(RHO_MIN)) | (rho == T(RHO_MAX)))[fluid].sum()),
+            int(((u * u + v * v) >= U_MAX * U_MAX * (1 - 1e-6))[fluid].sum()))
+
+
 def compute_forces_raw(rho, ux, solid):
     """html:650-699 computeForces, raw sums: for every solid cell and each of its
     4 face neighbours that is inside the grid and fluid: p=rho_fluid/3 (double),

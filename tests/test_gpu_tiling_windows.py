@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
+from lbm_numpy import clamp_events
 
 pytestmark = pytest.mark.gpu
 
@@ -101,11 +102,8 @@ def _case(seed):
 
 
 def _clamp_counts(mask, macro):
-    """wt_clamp_events counted on the oracle's macro state (html:344-350), as in test_gpu_fused.py."""
-    fluid = mask == 0
-    rho, ux, uy = (a.astype(np.float64) for a in macro)
-    return (int(((macro[0] == macro[0].dtype.type(0.5)) | (macro[0] == macro[0].dtype.type(2.0)))[fluid].sum()),
-            int(((ux * ux + uy * uy) >= 0.35 * 0.35 * (1 - 1e-6))[fluid].sum()))
+    """wt_clamp_events counted on the oracle's macro state (html:344-350)."""
+    return clamp_events(*macro, mask)
 
 
 def _assert_same(f, macro, ref_f, ref_m, what):

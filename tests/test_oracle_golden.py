@@ -114,36 +114,44 @@ def test_known_answers_from_survey():
 
 
 def test_field_scalar_vs_reference_render_shader(oracle_np):
-    """RENDER_FS executed on the golden macro field: recolour the oracle's scalar t with the
-    shader's colour maps (html:371-393, restated here for the test) and compare RGB."""
+    """RENDER_FS executed on the golden macro field: the oracle's scalar t recoloured by the oracle's colour maps
+    (render_rgb, html:371-397) against the shader's RGB, and render_rgba8 against that RGB quantised like a GL RGBA8
+    framebuffer (round to nearest), byte for byte, solids included."""
     g = np.load(os.path.join(GOLDEN, "run_64x32_naca0012_a0_f32.npz"))
     nx, ny = int(g["nx"]), int(g["ny"])
     mask = _mask_from_spans(g["mask0_spans"], nx, ny)
     rgb = g["render_rgb"]                       # [mode][ny][nx][3]
+    want8 = np.floor(rgb.astype(np.float64) * 255.0 + 0.5).astype(np.uint8)
     mx, cmin, cmax = (float(v) for v in g["ranges"])
-    F = np.float32
-
-    def lerp_stops(t, stops):
-        stops = (np.asarray(stops, dtype=F) / F(255.0)).astype(F)
-        t = np.minimum(np.maximum(t, F(0)), F(1))
-        n = len(stops) - 1
-        f = (t * F(n)).astype(F)
-        i = np.clip(np.floor(f).astype(np.int64), 0, n - 1)
-        u = (f - i.astype(F)).astype(F)[..., None]
-        return (stops[i] * (F(1) - u) + stops[i + 1] * u).astype(F)
-
-    SPEED = [[5, 5, 20], [0, 20, 120], [0, 60, 200], [0, 140, 220], [0, 220, 220], [0, 210, 140], [80, 200, 0], [220, 210, 0], [255, 120, 0], [220, 20, 0]]
-    CP = [[20, 50, 160], [40, 110, 210], [100, 175, 235], [190, 220, 245], [248, 248, 248], [248, 214, 140], [240, 150, 60], [205, 50, 25]]
     fluid = mask == 0
-    for mode, stops in ((0, SPEED), (1, CP)):
+    assert (~fluid).any()
+    for mode in (0, 1, 2):
         t = oracle_np.field_scalar(mode, g["rho"], g["ux"], g["uy"], mask, float(g["u0"]), mx, cmin, cmax)
-        col = lerp_stops(t[fluid], stops)
-        np.testing.assert_allclose(col, rgb[mode][fluid], rtol=0, atol=2e-6)
-    t = oracle_np.field_scalar(2, g["rho"], g["ux"], g["uy"], mask, float(g["u0"]), mx, cmin, cmax)[fluid]
-    t = np.clip(t, F(-1), F(1))
-    base = np.asarray([0.06, 0.07, 0.11], F)
-    neg, pos = np.asarray([0.15, 0.5, 0.98], F), np.asarray([0.98, 0.28, 0.18], F)
-    a = np.abs(t)[..., None]
-    col = np.where((t < 0)[..., None], base * (F(1) - a) + neg * a, base * (F(1) - a) + pos * a)
-    np.testing.assert_allclose(col, rgb[2][fluid], rtol=0, atol=2e-6)
-    np.testing.assert_allclose(rgb[0][~fluid], np.broadcast_to(np.asarray([0.039, 0.043, 0.078], F), rgb[0][~fluid].shape), atol=1e-7)
+        col = oracle_np.render_rgb(mode, t, mask)
+        assert col.dtype == np.float32 and col.shape == (ny, nx, 3)
+        np.testing.assert_allclose(col[fluid], rgb[mode][fluid], rtol=0, atol=2e-6)
+        np.testing.assert_allclose(col[~fluid], rgb[mode][~fluid], rtol=0, atol=1e-7)
+        img = oracle_np.render_rgba8(mode, t, mask)
+        assert img.shape == (ny, nx, 4) and img.dtype == np.uint8 and (img[..., 3] == 255).all()
+        assert np.array_equal(img[..., :3], want8[mode]), mode
+
+
+@pytest.mark.parametrize("name", ["run_64x32_naca0012_a0_f32", "run_default_320x160_naca2412_a6_f32"])
+def test_tracer_sampling_and_advection_vs_reference_js(oracle_np, oracle_c, pkg, name):
+    """sampleUV (html:616-639) and advect() (html:758-771) run by Node on the golden macro field vs the oracle's
+    sample_uv / advect: the same particles without a sample, the same positions, speeds and samples."""
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    _, _, mask, u0 = _replay(oracle_c, g, pkg)
+    ny, nx = mask.shape
+    window = (oracle_np.DX0, oracle_np.DX1, -0.46, 0.46)              # yHalf = 1.84 * NY / NX / 2 (html:73-76)
+    assert 1.84 * ny / nx / 2 == pytest.approx(0.46)
+    pts, want_uv, want = g["tracer_points"], g["tracer_uv"], g["tracer_advect"]
+    u, v, ok = oracle_np.sample_uv(g["ux"], g["uy"], mask, u0, window, pts[:, 0], pts[:, 1])
+    null = np.isnan(want_uv[:, 0])
+    assert np.array_equal(~ok, null) and null.sum() > 50 and (~null).sum() > 500
+    np.testing.assert_allclose(np.stack([u, v], 1)[ok], want_uv[~null], rtol=1e-12, atol=1e-14)
+    xn, yn, sp, ok = oracle_np.advect(g["ux"], g["uy"], mask, u0, window, pts[:, 0], pts[:, 1], float(g["tracer_dt"]))
+    null = np.isnan(want[:, 0])
+    assert np.array_equal(~ok, null)
+    np.testing.assert_allclose(np.stack([xn, yn, sp], 1)[ok], want[~null], rtol=1e-12, atol=1e-14)
+    assert np.array_equal(xn[~ok], pts[~ok, 0]) and np.array_equal(yn[~ok], pts[~ok, 1]) and (sp[~ok] == 0).all()
