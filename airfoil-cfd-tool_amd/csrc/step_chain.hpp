@@ -457,7 +457,7 @@ static inline void chain_blocks(MarchPlan &pl, const uint8_t *wcls, const Geom &
 // sets, and a workgroup barrier sits behind `uflags & MU_CHAIN` — a block with three chain units and one solo unit, a chain unit shorter than
 // the pipeline, or two "partners" that are not neighbours would spin for ever or read columns nobody published.  The planners above produce
 // well-formed plans by construction (tests/_march_plan_check.hip); this is the same statement checked on EVERY plan the library uploads
-// (windtunnel.hip upload_units), whoever built it.  A group of four that carries a chain flag must be: four chain units of one window,
+// (finish_units below), whoever built it.  A group of four that carries a chain flag must be: four chain units of one window,
 // contiguous, at least depth + 1 columns each, flagged (DIR_NEG | -), (END_SHARED), (DIR_NEG | END_SHARED), (-), none the outlet unit, the
 // footprint (`pad` columns beyond either end) inside the local lattice, clear of the tunnel's ends and FAST throughout.
 static inline bool chain_group_ok(const MarchUnit *u, const uint8_t *wcls, const Geom &g, int depth)
@@ -651,6 +651,17 @@ static inline void xcd_order(std::vector<MarchUnit> &units)
         for (size_t k = 0; k < 4 && 4 * b + k < units.size(); k++) out[4 * i + k] = units[4 * b + k];
     }
     units.swap(out);
+}
+
+// What every unit list goes through on its way to the device, taken in the order its planner produced it: the chain-block check
+// (sanitize_chain_plan; a downgraded unit is split to at most march_max_len(depth) - 2 columns), then the XCD order where `order` holds.
+// `between` (experiment builds only) runs between the two.  Returns the number of groups downgraded.
+static inline int finish_units(MarchPlan &pl, const uint8_t *wcls, const Geom &g, int depth, bool order, void (*between)(MarchPlan &) = nullptr)
+{
+    const int bad = sanitize_chain_plan(pl, wcls, g, depth, march_max_len(depth) - 2);
+    if (between) between(pl);
+    if (order) xcd_order(pl.units);
+    return bad;
 }
 
 }  // namespace wt

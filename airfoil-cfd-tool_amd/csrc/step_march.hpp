@@ -32,6 +32,8 @@ namespace wt {
 
 static constexpr int MARCH_MAX_CHUNK = 60;       // two-step tables: the unit length of round 2's two-step kernel (one ballot of class bits), kept so that their plans stay as they were
 static constexpr int MARCH3_MAX_CHUNK = 124;     // three / four steps per pass: two ballots (ClassMask), columns ia-PAD .. ib+PAD-1 <= 128
+// most columns a unit of a `depth`-step plan may hold (the planners' max_len; a four-step unit's class masks reach three columns beyond it)
+static inline int march_max_len(int depth) { return depth == 4 ? MARCH3_MAX_CHUNK - 3 : (depth == 3 ? MARCH3_MAX_CHUNK : MARCH_MAX_CHUNK); }
 
 // classes of up to 128 consecutive columns of a window, one bit each (lane l of the first ballot <-> the first column + l, of the second + 64 + l)
 struct ClassMask { unsigned long long lo, hi; };

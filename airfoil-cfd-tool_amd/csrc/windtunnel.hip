@@ -86,6 +86,14 @@ static int fail(int code, const char *fmt, ...)
 // ------------------------------------------------------------------------------------------
 enum Transport { TR_NONE = 0, TR_LOCAL = 1, TR_RCCL = 2 };
 
+// a unit list of the marching kernel on the device (put_units): n units in a buffer of cap
+struct UnitList { MarchUnit *d = nullptr; size_t cap = 0; int n = 0; };
+static void free_units(UnitList &ul)
+{
+    if (ul.d) (void)hipFree(ul.d);
+    ul = UnitList{};
+}
+
 struct wt_handle {
     int nx_g = 0, ny = 0, dtype = WT_F32, device = 0;
     int rank = 0, nranks = 1, halo = 0;
@@ -140,9 +148,8 @@ struct wt_handle {
     void *seams = nullptr;               // seam rows written by a marching pass beside its output lattice, (nwin+1) * (nxl+2) * M3_SREC elements
     uint8_t *seam_plain = nullptr;       // per (seam, column): both sites next to the seam are plain interior fluid, (nwin-1) * nxl
     bool seams_valid = false;            // `seams` describes lattice f[cur] (set by a marching pass, cleared by everything else that writes f)
-    MarchUnit *d_units = nullptr;
-    size_t units_cap = 0;
-    int n_units = 0, n_win = 0, nonfast_tiles = 0;
+    UnitList units;                      // the plan's unit list (upload_units)
+    int n_win = 0, nonfast_tiles = 0;
     std::vector<uint8_t> host_wcls;
     // fast division by tau (d2q9.hpp): proved per tau on the device before it is used
     unsigned int *d_nbad = nullptr;
@@ -169,7 +176,7 @@ struct wt_handle {
     bool tune_deferred = false;
     int tune_rounds = 0;                 // refinements tried for the present plan
     double tune_gain = 0.0;              // makespan of the modelled plan / makespan of the plan kept (unit clocks)
-    unsigned long long *d_clk = nullptr;  // unit clocks of tuning passes: two records of n_units {start, end}
+    unsigned long long *d_clk = nullptr;  // unit clocks of tuning passes: two records of units.n {start, end}
     size_t clk_cap = 0;
     bool clk_on = false;
     size_t clk_off = 0;
@@ -187,11 +194,11 @@ struct wt_handle {
     // Trimmed ghost marching (slab handles, three / four steps per pass): a pass that starts with gv exact ghost columns and advances k steps
     // leaves gv - k of them exact — marching the others is work whose result nobody may read.  One unit list per "exact ghost columns after
     // the pass" (the kept plan's range shrunk at the slab's local edges), cut lazily with the kept plan's measured column costs.
-    struct TrimPlan { int v_after = -1; MarchUnit *d_units = nullptr; size_t cap = 0; int n_units = 0; bool valid = false; };
+    struct TrimPlan { int v_after = -1; UnitList units; bool valid = false; };
     std::vector<TrimPlan> trim_plans;
     bool trim_prebuilt = false;          // the lists of the two standard cycles exist (prebuild_trim_plans)
     // refresh = 2 (renew_plan_for): per pass length, the unit lists of the interior columns [0] and of the two edge strips [1]
-    struct RenewPlan { int depth = 0; MarchUnit *d_units[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; int n_units[2] = {0, 0}; int strip_lo[2] = {0, 0}, strip_hi[2] = {0, 0}; bool valid = false; };
+    struct RenewPlan { int depth = 0; UnitList units[2]; int strip_lo[2] = {0, 0}, strip_hi[2] = {0, 0}; bool valid = false; };
     std::vector<RenewPlan> renew_plans;
     long long fused_renewals = 0;        // ghost renewals taken inside a fused pass (option "fused_renewals")
     std::vector<float> colw_kept;        // column-cost corrections of the plan tune_fuse_plan kept (empty: the modelled costs)
@@ -410,9 +417,9 @@ extern "C" int wt_destroy(wt_handle *h)
     if (h->hlines) (void)hipFree(h->hlines);
     if (h->seams) (void)hipFree(h->seams);
     if (h->seam_plain) (void)hipFree(h->seam_plain);
-    if (h->d_units) (void)hipFree(h->d_units);
-    for (auto &tp : h->trim_plans) if (tp.d_units) (void)hipFree(tp.d_units);
-    for (auto &rp : h->renew_plans) for (int i = 0; i < 2; i++) if (rp.d_units[i]) (void)hipFree(rp.d_units[i]);
+    free_units(h->units);
+    for (auto &tp : h->trim_plans) free_units(tp.units);
+    for (auto &rp : h->renew_plans) for (UnitList &ul : rp.units) free_units(ul);
     if (h->d_clk) (void)hipFree(h->d_clk);
     if (h->d_nbad) (void)hipFree(h->d_nbad);
     if (h->d_agree) (void)hipFree(h->d_agree);
@@ -553,7 +560,7 @@ static void cut_units(wt_handle *h, const float *colw, MarchPlan *out, const Mar
     static const double alpha = exp_env("WT_ALPHA") ? atof(exp_env("WT_ALPHA")) : 1.6;
     static const double alpha_solid = exp_env("WT_ALPHA_SOLID") ? atof(exp_env("WT_ALPHA_SOLID")) : alpha;
     static const int timed = exp_env("WT_PLAN_TIMED") ? atoi(exp_env("WT_PLAN_TIMED")) : 1;
-    const int min_last = depth == 4 ? 2 : 1, max_len = depth == 4 ? MARCH3_MAX_CHUNK - 3 : (depth == 3 ? MARCH3_MAX_CHUNK : MARCH_MAX_CHUNK);
+    const int min_last = depth == 4 ? 2 : 1, max_len = march_max_len(depth);
     const double over = depth == 4 ? 4.5 : (depth == 3 ? 2.7 : 1.5), tail = depth == 4 ? 1.25 : (depth == 3 ? 1.0 : 0.5);
     const bool by_time = plan_by_time(h);
     const bool chain = depth >= 3 && h->chain;
@@ -593,43 +600,52 @@ static bool xcd_order_on(const wt_handle *h)
     return e >= 0 ? e != 0 : h->ovl;
 }
 
-static int upload_units(wt_handle *h, const MarchPlan &plan_in)
+// A fresh cut on its way to the device: the chain-block invariant the kernel's LDS hand-over rests on is checked on every list (finish_units,
+// step_chain.hpp: an ill-formed group is downgraded to solo units and counted, never launched), then the XCD order where `order` and xcd_order_on hold.
+static void finish_cut(wt_handle *h, MarchPlan &pl, bool order, void (*between)(MarchPlan &) = nullptr)
 {
-    // the chain-block invariant the kernel's LDS hand-over rests on, checked on every plan that reaches the device (sanitize_chain_plan,
-    // step_chain.hpp): an ill-formed group is downgraded to solo units and counted, never launched
-    MarchPlan pl = plan_in;
-    if (!h->host_wcls.empty()) {
-        const int max_solo = (h->march_depth == 4 ? MARCH3_MAX_CHUNK - 3 : (h->march_depth == 3 ? MARCH3_MAX_CHUNK : MARCH_MAX_CHUNK)) - 2;
-        h->chain_downgrades += sanitize_chain_plan(pl, h->host_wcls.data(), h->g, h->march_depth, max_solo);
+    h->chain_downgrades += finish_units(pl, h->host_wcls.data(), h->g, h->march_depth, order && xcd_order_on(h), between);
+}
+// a finished list into its device buffer (grown with a quarter to spare)
+static int put_units(wt_handle *h, UnitList &ul, const std::vector<MarchUnit> &units)
+{
+    const size_t total = units.size();
+    ul.n = (int)total;
+    if (total == 0) return WT_OK;
+    if (total > ul.cap) {
+        if (ul.d) HIP_TRY(hipFree(ul.d));
+        ul.d = nullptr; ul.cap = 0;
+        const size_t cap = total + total / 4 + 64;
+        HIP_TRY(hipMalloc((void **)&ul.d, cap * sizeof(MarchUnit)));
+        ul.cap = cap;
     }
-    if (const char *e = exp_env("WT_DEBUG_CORRUPT_PLAN")) {
-        // experiment builds only (tools/r4_stuck_check.py): strip the chain flags of ONE unit of the first chain block BEHIND the guard above, so that
-        // its start-seam partner waits for a hand-over that never comes — the bounded poll of chain_receive must end the unit and raise `stuck`
-        if (atoi(e) != 0)
-            for (size_t b = 0; b + 3 < pl.units.size(); b += 4)
-                if (pl.units[b].flags & MU_CHAIN) { pl.units[b + 1].flags = 0; break; }
-    }
-    if (xcd_order_on(h)) xcd_order(pl.units);
-    for (auto &tp : h->trim_plans) tp.valid = false;       // cut from the kept plan's costs: stale now
+    HIP_TRY(hipMemcpyAsync(ul.d, units.data(), total * sizeof(MarchUnit), hipMemcpyHostToDevice, h->s_compute));
+    HIP_TRY(hipStreamSynchronize(h->s_compute));
+    return WT_OK;
+}
+// experiment builds only (tools/r4_stuck_check.py): strip the chain flags of ONE unit of the first chain block BEHIND the check, so that its
+// start-seam partner waits for a hand-over that never comes — the bounded poll of chain_receive must end the unit and raise `stuck`
+static void corrupt_first_chain_block(MarchPlan &pl)
+{
+    for (size_t b = 0; b + 3 < pl.units.size(); b += 4)
+        if (pl.units[b].flags & MU_CHAIN) { pl.units[b + 1].flags = 0; break; }
+}
+
+// The plan's own list; the lists cut from the kept plan's costs (trim_plan_for, renew_plan_for) are stale now.
+static int upload_units(wt_handle *h, MarchPlan pl)
+{
+    const char *e = exp_env("WT_DEBUG_CORRUPT_PLAN");
+    finish_cut(h, pl, true, e && atoi(e) != 0 ? corrupt_first_chain_block : nullptr);
+    for (auto &tp : h->trim_plans) tp.valid = false;
     h->trim_prebuilt = false;
     for (auto &rp : h->renew_plans) rp.valid = false;
     h->n_chain_units = 0;
     for (const MarchUnit &u : pl.units) h->n_chain_units += (u.flags & MU_CHAIN) != 0;
-    const size_t total = pl.units.size();
-    h->n_units = (int)total;
     h->fuse_chunk_used = pl.chunk;
-    h->host_units = pl.units;
-    if (total == 0) return WT_OK;
-    if (total > h->units_cap) {
-        if (h->d_units) { HIP_TRY(hipFree(h->d_units)); h->d_units = nullptr; h->units_cap = 0; }
-        const size_t cap = total + total / 4 + 64;
-        HIP_TRY(hipMalloc((void **)&h->d_units, cap * sizeof(MarchUnit)));
-        h->units_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_units, pl.units.data(), total * sizeof(MarchUnit), hipMemcpyHostToDevice, h->s_compute));
-    HIP_TRY(hipStreamSynchronize(h->s_compute));
-    return WT_OK;
+    h->host_units = pl.units;        // (in launch order: the tuner reads unit clocks by position)
+    return put_units(h, h->units, pl.units);
 }
+static const float *kept_colw(const wt_handle *h) { return h->colw_kept.empty() ? nullptr : h->colw_kept.data(); }
 
 // Overlapping windows (k_march3, step_chain.hpp: four margin rows on either side in place of the halo lines): 128 / 120 of the arithmetic and loads /
 // stores that straddle lines for no halo kernel — 10 of the 58 us of a pass on a slab of an 8-way split of 4096^2, 21 of 307 on the whole lattice.
@@ -652,11 +668,13 @@ static int build_fuse_plan(wt_handle *h, int sites, long target, int depth)
     const Geom &g = h->g;
     const int win = 64 * sites;
     const size_t eb = h->dtype == WT_F32 ? 4 : 8;
-    h->ovl = depth >= 3 && want_overlap(h);
-    const int wstride = h->ovl ? win - 8 : win, woff = h->ovl ? -4 : 0;
+    const bool ovl = depth >= 3 && want_overlap(h);
+    const int wstride = ovl ? win - 8 : win, woff = ovl ? -4 : 0;
     const int nwin = march_nwin(g.ny, wstride);
     const size_t wbytes = (size_t)nwin * (g.nxl + 2), cbytes = (size_t)(g.nxl + 2) * g.pitch;
     if (h->n_win != nwin || h->march_s != sites || h->march_depth != depth) free_march_tables(h);
+    if (h->ovl != ovl) h->seams_valid = false;       // (both layouts can give the same window count: the seam rows are the other layout's)
+    h->ovl = ovl;
     long long added = 0;
     if (!h->wcls) { HIP_TRY(hipMalloc((void **)&h->wcls, wbytes)); added += (long long)wbytes; }
     if (!h->seams) {
@@ -687,7 +705,7 @@ static int build_fuse_plan(wt_handle *h, int sites, long target, int depth)
     const long nt = (long)(g.nxl + 2) * nwin;
     hipLaunchKernelGGL(k_classify_windows, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, h->wcls, g, nwin, win, wstride, woff);
     hipLaunchKernelGGL(k_bounce_codes, dim3(2048), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, h->bcode, g);
-    if (nwin > 1 && !h->ovl) {
+    if (nwin > 1 && !ovl) {
         const long nth = (long)(nwin - 1) * g.nxl;
         if (depth == 4)
             hipLaunchKernelGGL(k_seam_flags4, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->s_compute, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
@@ -736,7 +754,7 @@ static long march_target_units(const wt_handle *h, int sites, long slots, bool f
 static int rebuild_fuse_plan(wt_handle *h)
 {
     h->fuse_ready = false;
-    h->n_units = h->nonfast_tiles = 0;
+    h->units.n = h->nonfast_tiles = 0;
     h->pass_cap = 0;
     if (!h->fuse || !fuse_eligible(h) || !h->mask_set) return WT_OK;
     const long slots = h->wave_slots;
@@ -794,7 +812,7 @@ static int rebuild_fuse_plan(wt_handle *h)
             if (!h->chain || h->fuse_chunk > 0)
                 while (tiles / target > MARCH3_MAX_CHUNK - 6) target += slots;     // a solo unit holds at most MARCH3_MAX_CHUNK columns: more rounds
             WT_TRY(build_fuse_plan(h, s3, target, depth));
-            h->fuse_ready = h->n_units > 0;
+            h->fuse_ready = h->units.n > 0;
             h->pass_cap = two_on_three ? 2 : 0;
             return WT_OK;
         }
@@ -807,7 +825,7 @@ two_step:
     const long target = march_target_units(h, 2, slots, true, 4);
     if (target == 0) return WT_OK;
     WT_TRY(build_fuse_plan(h, 2, target, 2));
-    h->fuse_ready = h->n_units > 0;
+    h->fuse_ready = h->units.n > 0;
     return WT_OK;
 }
 
@@ -833,10 +851,10 @@ extern "C" WT_API int wt_debug_unit_clocks(wt_handle *h, unsigned long long *clk
 {
     WT_TRY(check_handle(h));
     HIP_TRY(hipDeviceSynchronize());
-    const int n = h->n_units < cap ? h->n_units : cap;
+    const int n = h->units.n < cap ? h->units.n : cap;
     if (!h->d_clk) return fail(WT_ERR_STATE, "no pass has recorded unit clocks yet");
     HIP_TRY(hipMemcpy(clk, h->d_clk, (size_t)2 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(units4, h->d_units, (size_t)n * sizeof(MarchUnit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(units4, h->units.d, (size_t)n * sizeof(MarchUnit), hipMemcpyDeviceToHost));
     return n;
 }
 #endif
@@ -978,7 +996,7 @@ extern "C" int wt_get_option(const wt_handle *h, const char *name, double *value
     if (strcmp(name, "fuse_steps") == 0) { *value = h->fuse ? (h->fuse_force ? 2.0 : 1.0) : 0.0; return WT_OK; }
     if (strcmp(name, "fuse_active") == 0) { *value = h->fuse_ready ? 1.0 : 0.0; return WT_OK; }
     if (strcmp(name, "fuse_chunk") == 0) { *value = h->fuse_ready ? h->fuse_chunk_used : h->fuse_chunk; return WT_OK; }
-    if (strcmp(name, "fuse_units") == 0) { *value = h->n_units; return WT_OK; }
+    if (strcmp(name, "fuse_units") == 0) { *value = h->units.n; return WT_OK; }
     if (strcmp(name, "fuse_sites") == 0) { *value = h->fuse_ready ? h->march_s : h->fuse_sites; return WT_OK; }
     if (strcmp(name, "fuse_depth") == 0) { *value = h->fuse_ready ? plan_depth(h) : h->fuse_depth; return WT_OK; }
     if (strcmp(name, "fuse_tiles_general") == 0) { *value = h->nonfast_tiles; return WT_OK; }   // window-tiles that take the body paths
@@ -1371,7 +1389,7 @@ static inline bool tune_due(const wt_handle *h, int nsteps)
 
 static int ensure_clocks(wt_handle *h)
 {
-    const size_t need = (size_t)4 * (size_t)h->n_units + 8;       // two records
+    const size_t need = (size_t)4 * (size_t)h->units.n + 8;       // two records
     if (need > h->clk_cap) {
         if (h->d_clk) { HIP_TRY(hipFree(h->d_clk)); h->d_clk = nullptr; h->clk_cap = 0; }
         HIP_TRY(hipMalloc((void **)&h->d_clk, need * sizeof(unsigned long long)));
@@ -1383,7 +1401,7 @@ static int ensure_clocks(wt_handle *h)
 // The unit list of a pass that leaves `v_after` exact ghost columns (fewer than the kept plan's range covers): the kept plan's range shrunk to
 // the owned columns + v_after ghost columns at every LOCAL slab edge (the tunnel's own ends are marched as always).  Same planners, same
 // invariants, same tables; cut with the column costs the kept plan was cut with.  Every plan computes the same bits in the columns it marches.
-static int trim_plan_for(wt_handle *h, int v_after, const MarchUnit **units, int *nunits)
+static int trim_plan_for(wt_handle *h, int v_after, const UnitList **out)
 {
     wt_handle::TrimPlan *tp = nullptr;
     for (auto &t : h->trim_plans) if (t.v_after == v_after) tp = &t;
@@ -1394,28 +1412,12 @@ static int trim_plan_for(wt_handle *h, int v_after, const MarchUnit **units, int
         if (h->gl) r.i_begin = std::max(r.i_begin, h->gl - v_after);
         if (h->gr) r.i_end = std::min(r.i_end, h->gl + h->width + v_after);
         MarchPlan pl;
-        cut_units(h, h->colw_kept.empty() ? nullptr : h->colw_kept.data(), &pl, &r);
-        if (!h->host_wcls.empty()) {
-            const int max_solo = (h->march_depth == 4 ? MARCH3_MAX_CHUNK - 3 : MARCH3_MAX_CHUNK) - 2;
-            h->chain_downgrades += sanitize_chain_plan(pl, h->host_wcls.data(), g, h->march_depth, max_solo);
-        }
-        if (xcd_order_on(h)) xcd_order(pl.units);
-        const size_t total = pl.units.size();
-        if (total > tp->cap) {
-            if (tp->d_units) { HIP_TRY(hipFree(tp->d_units)); tp->d_units = nullptr; tp->cap = 0; }
-            const size_t cap = total + total / 4 + 64;
-            HIP_TRY(hipMalloc((void **)&tp->d_units, cap * sizeof(MarchUnit)));
-            tp->cap = cap;
-        }
-        if (total > 0) {
-            HIP_TRY(hipMemcpyAsync(tp->d_units, pl.units.data(), total * sizeof(MarchUnit), hipMemcpyHostToDevice, h->s_compute));
-            HIP_TRY(hipStreamSynchronize(h->s_compute));
-        }
-        tp->n_units = (int)total;
+        cut_units(h, kept_colw(h), &pl, &r);
+        finish_cut(h, pl, true);
+        WT_TRY(put_units(h, tp->units, pl.units));
         tp->valid = true;
     }
-    *units = tp->d_units;
-    *nunits = tp->n_units;
+    *out = &tp->units;
     return WT_OK;
 }
 
@@ -1444,7 +1446,7 @@ static void march3_params(wt_handle *h, double tau, double u0, MarchParams<T> &p
         if (rev_mode == 0 || rev_mode == 1) p.rev = rev_mode;
     }
     p.stuck = h->stuck_dev;
-    p.units = h->d_units; p.nunits = h->n_units;
+    p.units = h->units.d; p.nunits = h->units.n;
 }
 
 // level-0 .. level-(D-1) values of the rows around the window seams for the column blocks xb0 .. xb0 + nbx - 1 (HL_COLS columns each; nbx < 0: all)
@@ -1503,6 +1505,26 @@ static int launch_march3(const MarchParams<T> &p, int depth, bool emit, bool two
     return WT_OK;
 }
 
+// Exact ghost columns after a pass of k steps that started with gv_before of them.  One column of ghost validity is consumed per step — and the
+// units of a depth-D plan leave the D-1 columns next to a local edge unwritten whatever the pass advances (march_range3), so a SHORTER pass on
+// those tables still costs D-1 columns of the fresh ghosts (found by the mixed-depth group test: two-step passes on four-step tables right after
+// an initialisation).  run_steps and wt_plan_steps both count by it.
+static inline int ghosts_after_pass(const wt_handle *h, int gv_before, int k)
+{
+    return std::max(0, std::min(gv_before - k, h->halo - (h->march_depth - 1)));
+}
+// what every marching pass of k steps leaves behind (gv_before: the exact ghost columns it started from).  A pass on windows that tile the
+// column writes the seam rows of its output lattice beside it; one on overlapping windows writes none, so the seam buffer is valid exactly then.
+static void end_pass(wt_handle *h, int k, int gv_before)
+{
+    h->cur = 1 - h->cur;
+    h->steps_done += k;
+    h->passes += 1;
+    h->passes_total += 1;
+    h->seams_valid = !h->ovl;
+    if (h->nranks > 1) h->ghost_valid = ghosts_after_pass(h, gv_before, k);
+}
+
 // `depth` steps in one pass (step_march3.hpp): the plan's own depth, or a shorter pass on the same tables (what a step count leaves over).
 // A = f[cur] (time t), B = f[1-cur] (receives time t + depth).
 template <typename T, int S, int FD>
@@ -1518,27 +1540,18 @@ static int step_triple_fused_t(wt_handle *h, double tau, double u0, bool emit, i
     launch_halo_lines<T, S, FD>(h, p, h->seams_valid ? 1 : 0, 0, -1, st);
     if (h->nranks > 1 && h->trim && !h->clk_on && h->march_depth >= 3) {
         // ghost columns that will still be exact after this pass: the others are not marched (trim_plan_for; not on two-step plans)
-        const int v_full = h->halo - (h->march_depth - 1), v_after = std::max(0, std::min(h->ghost_valid - depth, v_full));
+        const int v_full = h->halo - (h->march_depth - 1), v_after = ghosts_after_pass(h, h->ghost_valid, depth);
         if (v_after < v_full) {
-            const MarchUnit *tu = nullptr;
-            int tn = 0;
-            WT_TRY(trim_plan_for(h, v_after, &tu, &tn));
-            if (tn > 0) { p.units = tu; p.nunits = tn; h->trimmed_passes += 1; }
+            const UnitList *tl = nullptr;
+            WT_TRY(trim_plan_for(h, v_after, &tl));
+            if (tl->n > 0) { p.units = tl->d; p.nunits = tl->n; h->trimmed_passes += 1; }
         }
     }
     if (h->clk_on) HIP_TRY(hipEventRecord(h->ev_t0, st));       // tuning passes: the marching kernel alone is timed
     WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
     HIP_TRY(hipGetLastError());
     if (h->clk_on) HIP_TRY(hipEventRecord(h->ev_t1, st));
-    h->cur = 1 - h->cur;
-    h->steps_done += depth;
-    h->passes += 1;
-    h->passes_total += 1;
-    h->seams_valid = true;
-    // One column of ghost validity is consumed per step — and the units of a depth-D plan leave the D-1 columns next to a local edge
-    // unwritten whatever the pass advances (march_range3), so a SHORTER pass on those tables still costs D-1 columns of the fresh ghosts
-    // (found by the mixed-depth group test: two-step passes on four-step tables right after an initialisation).
-    if (h->nranks > 1) h->ghost_valid = std::max(0, std::min(h->ghost_valid - depth, h->halo - (h->march_depth - 1)));
+    end_pass(h, depth, h->ghost_valid);
     return WT_OK;
 }
 
@@ -1557,57 +1570,35 @@ static int renew_plan_for(wt_handle *h, int depth, wt_handle::RenewPlan **out)
     if (!rp->valid) {
         const Geom &g = h->g;
         const MarchRange full = march_range3(g, h->march_depth);
-        const int v_after = std::max(0, std::min(h->halo - depth, h->halo - (h->march_depth - 1)));
+        const int v_after = ghosts_after_pass(h, h->halo, depth);
         MarchRange ri = full;                                  // interior
         if (h->gl) ri.i_begin = h->gl + depth;
         if (h->gr) ri.i_end = h->gl + h->width - depth;
         if (h->gr) ri.outlet_after = 0;
         if (ri.i_end - ri.i_begin < 2 * h->march_depth + 2) return fail(WT_ERR_STATE, "slab too narrow for a fused renewal (refresh = 2): %d interior columns", ri.i_end - ri.i_begin);
-        const int max_solo = (h->march_depth == 4 ? MARCH3_MAX_CHUNK - 3 : MARCH3_MAX_CHUNK) - 2;
-        const float *colw = h->colw_kept.empty() ? nullptr : h->colw_kept.data();
-        std::vector<MarchUnit> lists[2];
-        {
-            MarchPlan pl;
-            cut_units(h, colw, &pl, &ri);
-            if (!h->host_wcls.empty()) h->chain_downgrades += sanitize_chain_plan(pl, h->host_wcls.data(), g, h->march_depth, max_solo);
-            if (xcd_order_on(h)) xcd_order(pl.units);
-            lists[0] = pl.units;
-        }
+        MarchPlan pl;
+        cut_units(h, kept_colw(h), &pl, &ri);
+        finish_cut(h, pl, true);
+        WT_TRY(put_units(h, rp->units[0], pl.units));
         // the strips: a handful of columns per window.  They run AFTER the exchange, with nothing beside them: what counts is how long their slowest
         // unit takes, not how many columns are recomputed — so they are cut by time into as many units as the device holds (a plain strip column
         // becomes a unit of its own: 1 + the pipeline's fill instead of halo + fill iterations; measured on the 8-way split of 4096^2,
-        // profiles/r05_d_slab_costs_cfg2.txt)
-        const long target_save = h->plan_target;
-        for (int side = 0; side < 2; side++) {
-            if (!(side ? h->gr : h->gl)) continue;
-            MarchRange rs = full;
-            rs.outlet_after = 0;
-            if (side == 0) { rs.i_begin = std::max(full.i_begin, h->gl - v_after); rs.i_end = h->gl + depth; }
-            else { rs.i_begin = h->gl + h->width - depth; rs.i_end = std::min(full.i_end, h->gl + h->width + v_after); }
-            if (rs.i_end <= rs.i_begin) continue;
-            h->plan_target = std::max<long>(h->n_win, target_save / ((h->gl ? 1 : 0) + (h->gr ? 1 : 0)));
-            MarchPlan pl;
-            cut_units(h, colw, &pl, &rs);
-            h->plan_target = target_save;
-            if (!h->host_wcls.empty()) h->chain_downgrades += sanitize_chain_plan(pl, h->host_wcls.data(), g, h->march_depth, max_solo);
-            lists[1].insert(lists[1].end(), pl.units.begin(), pl.units.end());
-        }
-        h->plan_target = target_save;
-        while (lists[1].size() % 4) lists[1].push_back(MarchUnit{0, 0, 0, 0});
-        for (int i = 0; i < 2; i++) {
-            const size_t total = lists[i].size();
-            if (total > rp->cap[i]) {
-                if (rp->d_units[i]) { HIP_TRY(hipFree(rp->d_units[i])); rp->d_units[i] = nullptr; rp->cap[i] = 0; }
-                const size_t cap = total + total / 4 + 64;
-                HIP_TRY(hipMalloc((void **)&rp->d_units[i], cap * sizeof(MarchUnit)));
-                rp->cap[i] = cap;
-            }
-            if (total > 0) HIP_TRY(hipMemcpyAsync(rp->d_units[i], lists[i].data(), total * sizeof(MarchUnit), hipMemcpyHostToDevice, h->s_compute));
-            rp->n_units[i] = (int)total;
-        }
-        HIP_TRY(hipStreamSynchronize(h->s_compute));
+        // profiles/r05_d_slab_costs_cfg2.txt).  Not put in XCD order.
         rp->strip_lo[0] = std::max(full.i_begin, h->gl - v_after); rp->strip_hi[0] = h->gl + depth;
         rp->strip_lo[1] = h->gl + h->width - depth; rp->strip_hi[1] = std::min(full.i_end, h->gl + h->width + v_after);
+        const long target_save = h->plan_target;
+        std::vector<MarchUnit> strips;
+        for (int side = 0; side < 2; side++) {
+            if (!(side ? h->gr : h->gl) || rp->strip_hi[side] <= rp->strip_lo[side]) continue;
+            const MarchRange rs{rp->strip_lo[side], rp->strip_hi[side], 0};
+            h->plan_target = std::max<long>(h->n_win, target_save / ((h->gl ? 1 : 0) + (h->gr ? 1 : 0)));
+            cut_units(h, kept_colw(h), &pl, &rs);
+            h->plan_target = target_save;
+            finish_cut(h, pl, false);
+            strips.insert(strips.end(), pl.units.begin(), pl.units.end());
+        }
+        while (strips.size() % 4) strips.push_back(MarchUnit{0, 0, 0, 0});
+        WT_TRY(put_units(h, rp->units[1], strips));
         rp->valid = true;
     }
     *out = rp;
@@ -1625,7 +1616,7 @@ static int renew_interior_t(wt_handle *h, double tau, double u0, bool emit, int 
     hipStream_t st = h->s_compute;
     if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 2), st));
     launch_halo_lines<T, S, FD>(h, p, seams_were_valid ? 1 : 0, 0, -1, st);      // (the lines of the ghost columns come out of stale records: rebuilt below, unused here)
-    p.units = rp->d_units[0]; p.nunits = rp->n_units[0];
+    p.units = rp->units[0].d; p.nunits = rp->units[0].n;
     WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
     HIP_TRY(hipGetLastError());
     if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 3), st));
@@ -1649,16 +1640,11 @@ static int renew_strips_t(wt_handle *h, double tau, double u0, bool emit, int de
         const int lo = std::max(0, rp->strip_lo[side] - D), hi = std::min(h->g.nxl, rp->strip_hi[side] + D);
         launch_halo_lines<T, S, FD>(h, p, 0, lo / HL_COLS, (hi - 1) / HL_COLS - lo / HL_COLS + 1, st);
     }
-    p.units = rp->d_units[1]; p.nunits = rp->n_units[1];
+    p.units = rp->units[1].d; p.nunits = rp->units[1].n;
     p.rev = 0;
     WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
     HIP_TRY(hipGetLastError());
-    h->cur = 1 - h->cur;
-    h->steps_done += depth;
-    h->passes += 1;
-    h->passes_total += 1;
-    h->seams_valid = true;                       // interior and strips together wrote the seam rows of every column that is still exact
-    h->ghost_valid = std::max(0, std::min(h->halo - depth, h->halo - (h->march_depth - 1)));
+    end_pass(h, depth, h->halo);                 // (on tiling windows, interior and strips together wrote the seam rows of every column still exact)
     h->fused_renewals += 1;
     return WT_OK;
 }
@@ -1740,14 +1726,13 @@ static int tune_fuse_plan(wt_handle *h, double tau, double u0)
     static const int rounds = exp_env("WT_TUNE_ROUNDS") ? atoi(exp_env("WT_TUNE_ROUNDS")) : 6;
     static const int trace = exp_env("WT_TUNE_TRACE") ? atoi(exp_env("WT_TUNE_TRACE")) : 0;
     static const double damp = exp_env("WT_TUNE_DAMP") ? atof(exp_env("WT_TUNE_DAMP")) : 0.6;
-    if (!h->tune || rounds <= 0 || !h->fuse_ready || h->march_depth < 3 || !plan_by_time(h) || h->n_units < 8) return WT_OK;
+    if (!h->tune || rounds <= 0 || !h->fuse_ready || h->march_depth < 3 || !plan_by_time(h) || h->units.n < 8) return WT_OK;
     const int k = fuse_pick(eff_depth(h), 1 << 20);
     if (k < 2) return WT_OK;
     const Geom &g = h->g;
     const int ld = g.nxl + 2;
     std::vector<float> colw((size_t)h->n_win * ld, 1.0f);
     std::vector<float> colw_cur, colw_best;          // the corrections the present / the best plan was cut with (empty: the modelled costs)
-    std::vector<MarchUnit> best = h->host_units;
     double best_span = 0.0, first_span = 0.0;
     std::vector<unsigned long long> clk;
     std::vector<double> dur, chain_dur;
@@ -1755,7 +1740,7 @@ static int tune_fuse_plan(wt_handle *h, double tau, double u0)
     const long long s_steps = h->steps_done, s_passes = h->passes, s_total = h->passes_total;
     bool have_best = false, uploaded_best = true;
     for (int it = 0; it < rounds; it++) {
-        const int n = h->n_units;
+        const int n = h->units.n;
         WT_TRY(ensure_clocks(h));
         HIP_TRY(hipMemsetAsync(h->d_clk, 0, (size_t)4 * n * sizeof(unsigned long long), h->s_compute));
         // the plan's score: the time of its marching kernel, one launch per launch order (the units' clocks are per XCD and not
@@ -1810,7 +1795,7 @@ static int tune_fuse_plan(wt_handle *h, double tau, double u0)
         }
         if (span <= 0.0) break;
         if (it == 0) first_span = span;
-        if (!have_best || span < best_span) { best_span = span; best = h->host_units; colw_best = colw_cur; have_best = true; uploaded_best = true; }
+        if (!have_best || span < best_span) { best_span = span; colw_best = colw_cur; have_best = true; uploaded_best = true; }
         else uploaded_best = false;
         h->tune_rounds = it + 1;
         if (it + 1 == rounds) break;
@@ -1840,11 +1825,12 @@ static int tune_fuse_plan(wt_handle *h, double tau, double u0)
         colw_cur = colw;
         uploaded_best = false;
     }
-    h->colw_kept = colw_best;                        // the trimmed plans of a slab (trim_plan_for) are cut with the kept plan's costs
+    // the kept plan and the trimmed / renewal lists of a slab (trim_plan_for, renew_plan_for) are all cut with the kept costs: a cut is
+    // determined by them (and the tables and target), so the kept plan is cut again rather than stored
+    h->colw_kept = colw_best;
     if (have_best && !uploaded_best) {
         MarchPlan pl;
-        pl.units = best;
-        pl.chunk = h->fuse_chunk_used;
+        cut_units(h, kept_colw(h), &pl);
         WT_TRY(upload_units(h, pl));
     }
     if (best_span > 0.0) h->tune_gain = first_span / best_span;
@@ -1981,9 +1967,8 @@ static int prebuild_trim_plans(wt_handle *h)
     if (h->trim_prebuilt || !(h->nranks > 1 && h->trim && h->fuse_ready && h->march_depth >= 3)) return WT_OK;
     const int v_full = h->halo - (h->march_depth - 1);
     for (int v_after = 0; v_after < v_full; v_after++) {
-        const MarchUnit *tu = nullptr;
-        int tn = 0;
-        WT_TRY(trim_plan_for(h, v_after, &tu, &tn));
+        const UnitList *tl = nullptr;
+        WT_TRY(trim_plan_for(h, v_after, &tl));
     }
     if (h->refresh_mode == 2) {
         wt_handle::RenewPlan *rp = nullptr;
@@ -2059,7 +2044,7 @@ extern "C" int wt_plan_steps(wt_handle *h, int nsteps, double tau, int *seq, int
         if (const int kr = renew_stride(h, nsteps - s)) {     // refresh = 2: 100 + k = a fused pass of k steps that renews the ghost columns
             if (n < cap) seq[n] = 100 + kr;
             n++;
-            h->ghost_valid = std::max(0, std::min(h->halo - kr, h->halo - (h->march_depth - 1)));
+            h->ghost_valid = ghosts_after_pass(h, h->halo, kr);
             s += kr;
             continue;
         }
@@ -2067,7 +2052,7 @@ extern "C" int wt_plan_steps(wt_handle *h, int nsteps, double tau, int *seq, int
         int code;
         if (k > 0) {
             code = k;
-            if (h->nranks > 1) h->ghost_valid = std::max(0, std::min(h->ghost_valid - k, h->halo - (h->march_depth - 1)));
+            if (h->nranks > 1) h->ghost_valid = ghosts_after_pass(h, h->ghost_valid, k);
             s += k;
         } else {
             const bool refresh = needs_halo(h);

@@ -1,13 +1,36 @@
 // Host-only check of build_march_plan (csrc/step_march.hpp): compiled by tests/test_march_plan.py with hipcc and run on the CPU —
 // it makes no HIP runtime call.  Invariants: every marched column of every window belongs to exactly one unit, units respect
 // the length cap and the minimum length of a window's last unit, the outlet flag sits on the last unit only, and with a target
-// the unit count does not exceed it (whole resident rounds).
+// the unit count does not exceed it (whole resident rounds).  A cut by time is a function of its inputs (the tuner cuts its kept plan
+// again from the kept costs), and finish_units is sanitize_chain_plan followed by the optional xcd_order.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <random>
 #include "../airfoil-cfd-tool_amd/csrc/step_chain.hpp"
 using namespace wt;
+
+static bool same_units(const std::vector<MarchUnit> &a, const std::vector<MarchUnit> &b)
+{
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); i++)
+        if (a[i].ia != b[i].ia || a[i].ib != b[i].ib || a[i].w != b[i].w || a[i].flags != b[i].flags) return false;
+    return true;
+}
+
+// finish_units (step_chain.hpp), the way every list takes to the device: with ordering on, xcd_order of the sanitized input; with it off, the
+// sanitized input unchanged; the same count of downgraded groups either way
+static int check_finish(const MarchPlan &in, const uint8_t *wcls, const Geom &g, int depth)
+{
+    MarchPlan ref = in, on = in, off = in;
+    const int nd = sanitize_chain_plan(ref, wcls, g, depth, march_max_len(depth) - 2);
+    std::vector<MarchUnit> ordered = ref.units;
+    xcd_order(ordered);
+    int bad = 0;
+    if (finish_units(on, wcls, g, depth, true) != nd || !same_units(on.units, ordered)) { printf("finish_units (ordered) is not xcd_order(sanitize)\n"); bad++; }
+    if (finish_units(off, wcls, g, depth, false) != nd || !same_units(off.units, ref.units)) { printf("finish_units (unordered) is not sanitize\n"); bad++; }
+    return bad;
+}
 
 static int check(const char *name, int nxl, int ny, int gi0, int nx_g, int win, int depth, long target, int max_cost, unsigned seed, int timed = 1)
 {
@@ -23,7 +46,7 @@ static int check(const char *name, int nxl, int ny, int gi0, int nx_g, int win, 
             if (body ? r < 600 : r < 2) wcls[(size_t)w * ld + x + 1] = r % 3 == 0 ? WC_SOLID : WC_GENERAL;
         }
     const MarchRange r = depth >= 3 ? march_range3(g, depth) : march_range(g);
-    const int min_last = depth == 4 ? 2 : 1, max_len = depth == 4 ? MARCH3_MAX_CHUNK - 3 : (depth == 3 ? MARCH3_MAX_CHUNK : MARCH_MAX_CHUNK);
+    const int min_last = depth == 4 ? 2 : 1, max_len = march_max_len(depth);
     // max_cost > 0 (the fuse_chunk option): the cut by owned columns; otherwise the library's default, the cut by time
     const double over = depth == 4 ? 4.5 : (depth == 3 ? 2.7 : 1.5), tail = depth == 4 ? 1.25 : (depth == 3 ? 1.0 : 0.5);
     const bool chain_timed = depth >= 3 && max_cost <= 0 && (timed == 1 || timed == 3);
@@ -32,10 +55,17 @@ static int check(const char *name, int nxl, int ny, int gi0, int nx_g, int win, 
     if (timed >= 3) { colw.resize(wcls.size()); for (float &c : colw) c = 0.2f + 5.8f * (float)(rng() % 1000) / 999.0f; }
     const float *cw = colw.empty() ? nullptr : colw.data();
     const ChainCost cc{over, tail, depth == 4 ? 2.0 : 1.4, depth == 4 ? 2.0 : 1.4, 1.25, 0.6, 160, 0.3};
-    MarchPlan pl = (max_cost > 0 || timed == 0) ? build_march_plan(wcls.data(), g, win, target, max_cost, 2.0, &r, min_last, max_len, depth >= 3 ? 4 : 1)
-                   : chain_timed                ? build_chain_plan_timed(wcls.data(), g, win, target, 2.2, r, min_last, max_len, depth, cc, cw)
-                                                : build_march_plan_timed(wcls.data(), g, win, target, 2.2, r, min_last, max_len, over, tail, 0.3, cw);
+    auto cut = [&]() {
+        return (max_cost > 0 || timed == 0) ? build_march_plan(wcls.data(), g, win, target, max_cost, 2.0, &r, min_last, max_len, depth >= 3 ? 4 : 1)
+               : chain_timed                ? build_chain_plan_timed(wcls.data(), g, win, target, 2.2, r, min_last, max_len, depth, cc, cw)
+                                            : build_march_plan_timed(wcls.data(), g, win, target, 2.2, r, min_last, max_len, over, tail, 0.3, cw);
+    };
+    MarchPlan pl = cut();
     int bad = 0;
+    {
+        const MarchPlan again = cut();       // the same inputs: the same list
+        if (!same_units(again.units, pl.units) || again.chunk != pl.chunk) { printf("a second cut differs\n"); bad++; }
+    }
     size_t n_chain = 0;
     if (depth >= 3) {
         // step_chain.hpp: whole blocks of four units of one window; chain flags on all four or none; a chain block is contiguous, plain
@@ -59,6 +89,7 @@ static int check(const char *name, int nxl, int ny, int gi0, int nx_g, int win, 
             for (int x = lo; x < hi; x++) if (wcls[(size_t)u[0].w * ld + x + 1] != WC_FAST) bad++;
         }
     }
+    bad += check_finish(pl, wcls.data(), g, depth);
     std::vector<int> cover((size_t)nwin * nxl, 0);
     std::vector<int> last_len(nwin, -1), n_outlet(nwin, 0);
     for (const MarchUnit &u : pl.units) {
@@ -99,13 +130,13 @@ static int check_sanitize(int depth, int corruption, unsigned seed)
         for (int x = 0; x < nxl; x++)
             if ((w % 3 == 1) && x > nxl / 3 && x < nxl / 2 && rng() % 1000 < 600) wcls[(size_t)w * ld + x + 1] = WC_GENERAL;
     const MarchRange r = march_range3(g, depth);
-    const int min_last = depth == 4 ? 2 : 1, max_len = depth == 4 ? MARCH3_MAX_CHUNK - 3 : MARCH3_MAX_CHUNK;
+    const int min_last = depth == 4 ? 2 : 1, max_len = march_max_len(depth);
     const double over = depth == 4 ? 4.5 : 2.7, tail = depth == 4 ? 1.25 : 1.0;
     const ChainCost cc{over, tail, depth == 4 ? 2.0 : 1.4, depth == 4 ? 2.0 : 1.4, 1.25, 0.6, 160, 0.3};
     // (a small target: long chain units, so that a downgraded one has to be split for the solo kernel's class masks)
     MarchPlan pl = build_chain_plan_timed(wcls.data(), g, win, corruption == 5 ? 192 : 2048, 2.2, r, min_last, max_len, depth, cc, nullptr);
     MarchPlan good = pl;
-    int bad = 0;
+    int bad = check_finish(pl, wcls.data(), g, depth);
     if (sanitize_chain_plan(good, wcls.data(), g, depth, max_len - 2) != 0 || good.units.size() != pl.units.size()) { printf("sanitize touched a good plan\n"); bad++; }
     std::vector<size_t> chain_groups;
     for (size_t b = 0; b + 3 < pl.units.size(); b += 4) if (pl.units[b].flags & MU_CHAIN) chain_groups.push_back(b);
@@ -120,7 +151,8 @@ static int check_sanitize(int depth, int corruption, unsigned seed)
     case 4: wcls[(size_t)u[0].w * ld + u[1].ia + 1] = WC_GENERAL; break;       // a body column inside the footprint
     case 5: u[3].flags |= MU_CHAIN | MU_END_SHARED; break;                     // (long units) an end seam nobody shares
     }
-    if (corruption == 1 && u[2].ib - u[2].ia > 160) return 0;
+    if (corruption == 1 && u[2].ib - u[2].ia > 160) return bad;
+    bad += check_finish(pl, wcls.data(), g, depth);
     const int nd = sanitize_chain_plan(pl, wcls.data(), g, depth, max_len - 2);
     if (nd < 1) { printf("corruption %d (depth %d) not detected\n", corruption, depth); bad++; }
     if (pl.units.size() % 4) bad++;
@@ -173,6 +205,7 @@ static int check_xcd_order(int ngroups, unsigned seed)
 int main()
 {
     int bad = 0;
+    if (march_max_len(2) != 60 || march_max_len(3) != 124 || march_max_len(4) != 121) { printf("march_max_len: %d %d %d\n", march_max_len(2), march_max_len(3), march_max_len(4)); bad++; }
     for (int n : {3, 15, 16, 17, 255, 256, 512, 513, 519}) bad += check_xcd_order(n, 7u + (unsigned)n);
     for (int depth : {3, 4})
         for (int c = 0; c < 6; c++) bad += check_sanitize(depth, c, 100u + (unsigned)(10 * depth + c));

@@ -107,3 +107,39 @@ def test_slab_group_equals_single_lattice_on_either_window_layout(pkg, overlap, 
     finally:
         for s in es:
             s.close()
+
+
+@pytest.mark.parametrize("depth", [3, 4])
+@pytest.mark.parametrize("ny", [240, 480])
+@pytest.mark.parametrize("switch", ["window_overlap", "fast_math"])
+def test_seam_buffer_is_stale_after_passes_on_overlapping_windows(pkg, ny, depth, switch):
+    """Heights at which both window layouts give the same window count (ceil(ny / 120) = ceil(ny / 128)): a plan cut again on windows that tile the
+    column keeps its tables, but the passes before it, on overlapping windows, wrote no seam rows — the next pass must build its halo lines from the
+    lattice.  The switch: window_overlap 1 -> 0 (against single steps), or fast_math 0 -> 1, which has no overlapping windows (against a handle that
+    tiled the column from the start, whose seam rows are valid).  Untuned plans: the tuner's trial passes would hide a stale flag."""
+    nx, n, m = 320, 9, 10
+    mask = pkg.geometry.build_geometry(nx, ny, 4.0, None, "naca0012").mask
+
+    def run(overlap, then):
+        with pkg.Engine(nx, ny) as e:
+            for k, v in (("fuse_steps", 2), ("fuse_depth", depth), ("tune", 0), ("window_overlap", overlap)):
+                e.set_option(k, v)
+            e.set_mask(mask)
+            e.init_equilibrium(0.06)
+            e.step(n, 0.58, 0.06)
+            assert e.get_option("window_overlap") == float(overlap) and e.get_option("passes") > 0
+            e.set_option(switch, then)
+            assert e.get_option("window_overlap") == 0.0 and e.get_option("fuse_active") == 1.0 and e.get_option("fuse_depth") == depth
+            e.step(m, 0.58, 0.06)
+            assert e.get_option("single_steps") == 0
+            return e.read_f(), e.read_macro()
+
+    if switch == "window_overlap":
+        ref_f, ref_m, _ = _run(pkg, nx, ny, mask, n + m, {"fuse_steps": 0})
+        f, m_ = run(1, 0)
+    else:
+        ref_f, ref_m = run(0, 1)
+        f, m_ = run(1, 1)
+    assert bits_equal(f, ref_f)
+    for a, b in zip(m_, ref_m):
+        assert bits_equal(a, b)
