@@ -6,6 +6,10 @@
 // (step_fast.hpp) with tau and U0 rounded to the storage type on the host as wt_step rounds them, and a force sample
 // runs k_forces' block body (forces_block, kernels.hpp) over wt_forces' block count, summed over the blocks in the
 // same order in double.
+//
+// Surface loads (wtp_enable_loads) are a reduction of their own, k_loads_batch, launched behind k_forces_batch: the pitching
+// moment of the force model's faces about a per-member point and the running sums of rho above and below the body, one
+// wave per (member, column).  It shares nothing with the force reduction, whose values it leaves as they are.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -48,6 +52,8 @@ static int fail(int code, const char *fmt, ...)
     } while (0)
 
 static const int kReduceBlocks = 1024;     // wt_forces' cap on the reduction's block count
+static const int kLoadsWaves = 16;         // waves (columns) of one k_loads_batch block
+static const int kTicketStride = 32;       // unsigned ints between the members' k_loads_batch tickets: one 128-byte line each
 
 // Element strides between consecutive members of each array.  Every stride is rounded to 4 KiB and grown by 17 KiB, as
 // wt_create's plane stride is, so that the members' lattices do not all start on the same HBM channels.
@@ -78,6 +84,15 @@ struct wtp_batch {
     int nb = 0;                          // blocks of one member's force reduction
     hipStream_t st = nullptr;
     std::vector<uint8_t> mask_set;
+    std::vector<int32_t> surf_rows;      // [B][2][NX]: rows of the fluid cells above / below each column's body (-1: none), from the masks
+    // surface loads (wtp_enable_loads); every pointer is null until then
+    bool loads = false;
+    double *l_ref = nullptr;             // [B][2]: xref, yref
+    double *l_col = nullptr;             // [B][NX]: the columns' moment partials of the running reduction
+    unsigned int *l_tickets = nullptr;   // [B] tickets, kTicketStride apart
+    double *h_mz = nullptr;              // history [cap + 1][B]; row cap = wtp_moment's scratch row
+    double *s_rho = nullptr;             // [B][2][NX]: sums of rho over the samples, upper then lower
+    long long *s_cnt = nullptr;          // [B][2][NX]: samples added
     bool inited = false;
     long long steps_done = 0;
 };
@@ -132,6 +147,94 @@ __global__ __launch_bounds__(256) void k_forces_batch(const T *__restrict__ macr
     tickets[m] = 0;
 }
 
+// Surface loads of every member in one launch: grid (ceil(NX / kLoadsWaves), B), one wave per (member, column i).  The time
+// of the launch follows its number of blocks (one device-wide fence and one ticket each), hence the large blocks.  A column is one
+// contiguous run of the mask and of rho (y fastest), read in chunks of 64 rows, one row per lane; rows past NY never count.
+//  * Moment: forces_block's faces (fluid cell, solid 4-neighbour inside the grid in direction d, p = (double)rho / 3, force
+//    p * d at the face centre r = (i + 0.5 + 0.5 dx, j + 0.5 + 0.5 dy)), each adding (r.x - xr) F.y - (r.y - yr) F.x.  The
+//    column's terms are added by wave_sum; the last block of a member to finish (ticket, as k_forces_batch) adds the
+//    columns' partials in column order, so that a sample does not depend on the order in which the blocks ran.
+//  * Surface: the highest and lowest solid row of the column from the chunks' ballots; with `accumulate`, rho of the fluid
+//    cell above the one and below the other is added to the member's sums.  One lane owns an entry and launches are
+//    stream-ordered, so the sums are plain read-modify-writes in sample order.
+template <typename T>
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__restrict__ macro, const uint8_t *__restrict__ mask, Geom g,
+                                                     MemberStrides ms, const double *__restrict__ ref, double *__restrict__ col,
+                                                     unsigned int *__restrict__ tickets, double *__restrict__ mz,
+                                                     double *__restrict__ s_rho, long long *__restrict__ s_cnt, int accumulate)
+{
+    const long m = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int nx = g.nxl, ny = g.ny;
+    const int i = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
+    if (i < nx) {                                                   // (wave-uniform)
+        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
+        const T *rho = macro + m * ms.macro + (long)i * g.pitch;
+        const double xr = ref[2 * m], yr = ref[2 * m + 1];
+        const double ax = ((double)i + 0.5) - xr;                   // r.x - xr of the column's horizontal faces
+        const bool left = i > 0, right = i + 1 < nx;
+        double t = 0.0;
+        int jhi = -1, jlo = ny;
+        for (int j0 = 0; j0 < ny; j0 += 64) {
+            const int j = j0 + lane;
+            const bool in = j < ny;
+            const int solid = in && mk[j];
+            const unsigned long long sb = __ballot(solid);
+            if (sb) {
+                jhi = j0 + 63 - __clzll((long long)sb);
+                if (jlo == ny) jlo = j0 + __ffsll((unsigned long long)sb) - 1;
+            }
+            if (in && !solid) {
+                const int sxp = right && mk[g.pitch + j];
+                const int sxm = left && mk[j - g.pitch];
+                const int syp = (j + 1 < ny) && mk[j + 1];
+                const int sym = (j > 0) && mk[j - 1];
+                if (sxp + sxm + syp + sym) {
+                    const double p = (double)rho[j] / 3.0;
+                    const double ay = ((double)j + 0.5) - yr;       // r.y - yr of the cell's vertical faces
+                    if (sxp) t -= ay * p;                           // F = (+p, 0) at (i + 1, j + 0.5)
+                    if (sxm) t += ay * p;                           // F = (-p, 0) at (i, j + 0.5)
+                    if (syp) t += ax * p;                           // F = (0, +p) at (i + 0.5, j + 1)
+                    if (sym) t -= ax * p;                           // F = (0, -p) at (i + 0.5, j)
+                }
+            }
+        }
+        t = wave_sum(t);
+        if (lane == 0) {
+            col[m * nx + i] = t;
+            if (accumulate) {
+                const long e = (m * 2) * nx + i;                    // upper; the lower entry is nx further on
+                if (jhi >= 0 && jhi + 1 < ny) { s_rho[e] += (double)rho[jhi + 1]; s_cnt[e] += 1; }
+                if (jlo < ny && jlo > 0) { s_rho[e + nx] += (double)rho[jlo - 1]; s_cnt[e + nx] += 1; }
+            }
+        }
+    }
+    constexpr int NT = kLoadsWaves * 64;
+    __shared__ int last;
+    __shared__ double sh[NT];
+    __syncthreads();                                                // the block's partials are written ...
+    if (threadIdx.x == 0) {
+        __threadfence();                                            // ... and visible device-wide before the block is counted
+        last = atomicAdd(&tickets[m * kTicketStride], 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    const volatile double *vc = col + m * nx;
+    double s = 0.0;
+    for (int c0 = 0; c0 < nx; c0 += NT) {                           // NT partials at a time through LDS; thread 0 adds them in column order
+        const int c = c0 + (int)threadIdx.x;
+        sh[threadIdx.x] = c < nx ? vc[c] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = nx - c0 < NT ? nx - c0 : NT;
+            for (int k = 0; k < n; k++) s += sh[k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { mz[m] = s; tickets[m * kTicketStride] = 0; }
+}
+
 // ------------------------------------------------------------------------------------------
 // life cycle
 // ------------------------------------------------------------------------------------------
@@ -159,7 +262,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets,
-                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage};
+                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage, b->l_ref, b->l_col, b->l_tickets, b->h_mz, b->s_rho, b->s_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (b->st) (void)hipStreamDestroy(b->st);
     delete b;
@@ -199,6 +302,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     const long total = (long)nx * ny;
     b->nb = (int)std::min<long>((total + 255) / 256, kReduceBlocks);
     b->mask_set.assign((size_t)members, 0);
+    b->surf_rows.assign((size_t)members * 2 * nx, -1);
 
     auto cleanup = [&](int rc) { wtp_destroy(b); return rc; };
 #define CREATE_TRY(expr)                                                                               \
@@ -239,7 +343,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.1 (gfx950, batched D2Q9 members, column-major SoA)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.2 (gfx950, batched D2Q9 members, column-major SoA, surface loads)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -252,6 +356,31 @@ extern "C" int wtp_sync(wtp_batch *b)
 // ------------------------------------------------------------------------------------------
 // masks and state
 // ------------------------------------------------------------------------------------------
+// Rows of the fluid cells directly above the highest / below the lowest solid cell of every column of one [NY][NX] mask;
+// -1 where the column holds no solid cell or its extreme one touches the border.
+static void surface_rows(wtp_batch *b, int member, const uint8_t *m01)
+{
+    const int nx = b->nx, ny = b->ny;
+    int32_t *up = b->surf_rows.data() + (size_t)member * 2 * nx, *lo = up + nx;
+    for (int i = 0; i < nx; i++) {
+        int jhi = -1, jlo = ny;
+        for (int j = 0; j < ny; j++)
+            if (m01[(size_t)j * nx + i]) { jhi = j; if (jlo == ny) jlo = j; }
+        up[i] = (jhi >= 0 && jhi + 1 < ny) ? jhi + 1 : -1;
+        lo[i] = (jlo < ny && jlo > 0) ? jlo - 1 : -1;
+    }
+}
+
+// Zero the surface sums of members [first, first+count), in stream order.  Nothing to do while loads are off.
+static int clear_surface_sums(wtp_batch *b, int first, int count)
+{
+    if (!b->loads) return WT_OK;
+    const size_t off = (size_t)first * 2 * b->nx, n = (size_t)count * 2 * b->nx;
+    HIP_TRY(hipMemsetAsync(b->s_rho + off, 0, n * sizeof(double), b->st));
+    HIP_TRY(hipMemsetAsync(b->s_cnt + off, 0, n * sizeof(long long), b->st));
+    return WT_OK;
+}
+
 extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *masks)
 {
     WT_TRY(check_batch(b));
@@ -267,6 +396,8 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
     for (int k = 0; k < count; k++) {
         const uint8_t *src = masks + (size_t)k * n;
         for (size_t q = 0; q < n; q++) m01[q] = src[q] ? 1 : 0;
+        surface_rows(b, first + k, m01.data());
+        WT_TRY(clear_surface_sums(b, first + k, 1));            // the member's surface cells moved
         HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
         uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
         dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
@@ -314,7 +445,7 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
     b->inited = true;
     b->steps_done = 0;
     b->h_step.clear();
-    return WT_OK;
+    return clear_surface_sums(b, 0, b->members);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -354,6 +485,17 @@ static int launch_forces(wtp_batch *b, int row)
     return WT_OK;
 }
 
+// The surface loads of the last emitted state: Mz into row `row` of the history; accumulate: also add to the surface sums.
+template <typename T>
+static int launch_loads(wtp_batch *b, int row, bool accumulate)
+{
+    hipLaunchKernelGGL(k_loads_batch<T>, dim3((unsigned)((b->nx + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members),
+                       dim3(kLoadsWaves * 64), 0, b->st, (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, (const double *)b->l_ref, b->l_col, b->l_tickets,
+                       b->h_mz + (size_t)row * b->members, b->s_rho, b->s_cnt, accumulate ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 template <typename T>
 static int step_impl(wtp_batch *b, int nsteps, int sample_every)
 {
@@ -377,6 +519,7 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         b->steps_done = n;
         if (sample) {
             WT_TRY(launch_forces<T>(b, (int)b->h_step.size()));
+            if (b->loads) WT_TRY(launch_loads<T>(b, (int)b->h_step.size(), true));
             b->h_step.push_back(n);
         }
     }
@@ -434,7 +577,9 @@ extern "C" int wtp_clear_history(wtp_batch *b)
 {
     WT_TRY(check_batch(b));
     b->h_step.clear();                           // (rows are only written by later, stream-ordered reductions)
-    return WT_OK;
+    if (!b->loads) return WT_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    return clear_surface_sums(b, 0, b->members);
 }
 
 extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, int64_t *rev)
@@ -450,6 +595,85 @@ extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, i
     HIP_TRY(hipMemcpy(fy, b->h_fy + off, B * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(surf, b->h_surf + off, B * sizeof(long long), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rev, b->h_rev + off, B * sizeof(long long), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// surface loads
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_loads(wtp_batch *b, const double *xref, const double *yref)
+{
+    WT_TRY(check_batch(b));
+    if (!xref || !yref) return fail(WT_ERR_ARG, "xref or yref is null");
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", m);
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->members, rows = (size_t)b->cap + 1, cols = B * b->nx;
+    if (!b->l_ref) HIP_TRY(hipMalloc((void **)&b->l_ref, B * 2 * sizeof(double)));
+    if (!b->l_col) HIP_TRY(hipMalloc((void **)&b->l_col, cols * sizeof(double)));
+    if (!b->l_tickets) HIP_TRY(hipMalloc((void **)&b->l_tickets, B * kTicketStride * sizeof(unsigned int)));
+    if (!b->h_mz) HIP_TRY(hipMalloc((void **)&b->h_mz, rows * B * sizeof(double)));
+    if (!b->s_rho) HIP_TRY(hipMalloc((void **)&b->s_rho, 2 * cols * sizeof(double)));
+    if (!b->s_cnt) HIP_TRY(hipMalloc((void **)&b->s_cnt, 2 * cols * sizeof(long long)));
+    std::vector<double> ref(B * 2);
+    for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
+    HIP_TRY(hipStreamSynchronize(b->st));        // samples already enqueued read the previous points
+    HIP_TRY(hipMemcpy(b->l_ref, ref.data(), ref.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(b->l_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
+    HIP_TRY(hipMemsetAsync(b->h_mz, 0xFF, rows * B * sizeof(double), b->st));     // rows sampled before this call hold no Mz about these points: NaN
+    b->loads = true;
+    return clear_surface_sums(b, 0, b->members);
+}
+
+static int check_loads(const wtp_batch *b)
+{
+    if (!b->loads) return fail(WT_ERR_STATE, "surface loads are not enabled (wtp_enable_loads)");
+    return WT_OK;
+}
+
+extern "C" int wtp_history_moment(wtp_batch *b, int first, int count, double *mz)
+{
+    WT_TRY(check_batch(b));
+    if (!mz) return fail(WT_ERR_ARG, "mz is null");
+    const int held = (int)b->h_step.size();
+    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    WT_TRY(check_loads(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
+    if (n) HIP_TRY(hipMemcpy(mz, b->h_mz + off, n * sizeof(double), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+extern "C" int wtp_moment(wtp_batch *b, double *mz)
+{
+    WT_TRY(check_batch(b));
+    if (!mz) return fail(WT_ERR_ARG, "mz is null");
+    WT_TRY(check_loads(b));
+    WT_TRY(check_ready(b));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? launch_loads<float>(b, b->cap, false) : launch_loads<double>(b, b->cap, false));     // the scratch row
+    HIP_TRY(hipStreamSynchronize(b->st));
+    HIP_TRY(hipMemcpy(mz, b->h_mz + (size_t)b->cap * b->members, (size_t)b->members * sizeof(double), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+extern "C" int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *rho_lower, int64_t *n_upper, int64_t *n_lower,
+                           int32_t *j_upper, int32_t *j_lower)
+{
+    WT_TRY(check_batch(b));
+    if (!rho_upper || !rho_lower || !n_upper || !n_lower || !j_upper || !j_lower) return fail(WT_ERR_ARG, "null output");
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_loads(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t nx = (size_t)b->nx, off = (size_t)member * 2 * nx;
+    HIP_TRY(hipMemcpy(rho_upper, b->s_rho + off, nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rho_lower, b->s_rho + off + nx, nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_upper, b->s_cnt + off, nx * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_lower, b->s_cnt + off + nx, nx * sizeof(long long), hipMemcpyDeviceToHost));
+    memcpy(j_upper, b->surf_rows.data() + off, nx * sizeof(int32_t));
+    memcpy(j_lower, b->surf_rows.data() + off + nx, nx * sizeof(int32_t));
     return WT_OK;
 }
 

@@ -4,7 +4,9 @@ The reference's analysis page sweeps the angle of attack (``pages/Airfoil_Analys
 with one XFOIL request per angle (``:930-966``) and tabulates CL, CD, L/D and Cm per angle.  Here the angles of a
 sweep are the members of one batch of ``libwtpolar.so`` (include/wt_polar.h): every member is a whole wind tunnel,
 bit-identical to a :class:`~airfoil_cfd_tool_amd.WindTunnel` with the same inputs, and all of them advance by one
-kernel launch per step.  Lift, drag and separation are sampled on the device into a history that is read once.
+kernel launch per step.  Lift, drag and separation are sampled on the device into a history that is read once; with
+surface loads enabled (``PolarEngine.enable_loads``, ``run_polar(loads=True)``) so are the pitching moment and the
+chordwise surface pressure.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -15,7 +17,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -31,6 +33,7 @@ POLAR_LIB_PATH = os.path.join(_PKG_DIR, "lib", "libwtpolar.so")
 EXPORTS = (
     "wtp_create", "wtp_destroy", "wtp_last_error", "wtp_version", "wtp_set_masks", "wtp_init_equilibrium", "wtp_step",
     "wtp_history", "wtp_clear_history", "wtp_forces", "wtp_clamp_events", "wtp_read_f", "wtp_read_macro", "wtp_sync",
+    "wtp_enable_loads", "wtp_history_moment", "wtp_moment", "wtp_surface",
 )
 
 _lib = None
@@ -65,6 +68,10 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_read_f": ([B, c_int, c_void_p], c_int),
         "wtp_read_macro": ([B, c_int, c_void_p, c_void_p, c_void_p], c_int),
         "wtp_sync": ([B], c_int),
+        "wtp_enable_loads": ([B, dp, dp], c_int),
+        "wtp_history_moment": ([B, c_int, c_int, dp], c_int),
+        "wtp_moment": ([B, dp], c_int),
+        "wtp_surface": ([B, c_int, dp, dp, ip, ip, POINTER(c_int32), POINTER(c_int32)], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -101,6 +108,7 @@ class PolarEngine:
         self.dtype = _np_dtype(dtype)
         self.nx, self.ny, self.members, self.history_cap = int(nx), int(ny), int(members), int(history_cap)
         self._b = c_void_p()
+        self.loads_enabled = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -141,13 +149,16 @@ class PolarEngine:
         _check(self._lib.wtp_step(self._b, int(nsteps), _dp(t), _dp(u), int(sample_every)))
 
     def history(self) -> Dict[str, np.ndarray]:
-        """Every row held: step [R], fx / fy [R][B] float64, surf / rev [R][B] int64."""
+        """Every row held: step [R], fx / fy [R][B] float64, surf / rev [R][B] int64; with loads enabled also mz [R][B] float64."""
         rows = _check(self._lib.wtp_history(self._b, 0, 0, None, None, None, None, None))
         B = self.members
         out = {"step": np.empty(rows, np.int64), "fx": np.empty((rows, B)), "fy": np.empty((rows, B)),
                "surf": np.empty((rows, B), np.int64), "rev": np.empty((rows, B), np.int64)}
         _check(self._lib.wtp_history(self._b, 0, rows, _ip(out["step"]), _dp(out["fx"]), _dp(out["fy"]), _ip(out["surf"]),
                                      _ip(out["rev"])))
+        if self.loads_enabled:
+            out["mz"] = np.empty((rows, B))
+            _check(self._lib.wtp_history_moment(self._b, 0, rows, _dp(out["mz"])))
         return out
 
     def clear_history(self) -> None:
@@ -159,6 +170,30 @@ class PolarEngine:
         fx, fy, surf, rev = np.empty(B), np.empty(B), np.empty(B, np.int64), np.empty(B, np.int64)
         _check(self._lib.wtp_forces(self._b, _dp(fx), _dp(fy), _ip(surf), _ip(rev)))
         return fx, fy, surf, rev
+
+    def enable_loads(self, xref, yref) -> None:
+        """Sample the pitching moment about (xref, yref) (one value or [B], lattice units) and the surface density sums from the
+        next sample on (wt_polar.h).  Calling it again replaces the points and clears the sums."""
+        x, y = _f64(xref, self.members), _f64(yref, self.members)
+        _check(self._lib.wtp_enable_loads(self._b, _dp(x), _dp(y)))
+        self.loads_enabled = True
+
+    def moment(self) -> np.ndarray:
+        """Mz [B] of the last emitted state, counter-clockwise positive, lattice units; adds nothing to the surface sums."""
+        mz = np.empty(self.members)
+        _check(self._lib.wtp_moment(self._b, _dp(mz)))
+        return mz
+
+    def surface(self, member: int) -> Dict[str, np.ndarray]:
+        """One member's surface sums per column: rho_upper / rho_lower (sums of rho over the samples), n_upper / n_lower (samples
+        added), j_upper / j_lower (row of the sampled fluid cell, -1 where the column has none)."""
+        nx = self.nx
+        out = {"rho_upper": np.empty(nx), "rho_lower": np.empty(nx), "n_upper": np.empty(nx, np.int64), "n_lower": np.empty(nx, np.int64),
+               "j_upper": np.empty(nx, np.int32), "j_lower": np.empty(nx, np.int32)}
+        _check(self._lib.wtp_surface(self._b, int(member), _dp(out["rho_upper"]), _dp(out["rho_lower"]), _ip(out["n_upper"]),
+                                     _ip(out["n_lower"]), out["j_upper"].ctypes.data_as(POINTER(c_int32)),
+                                     out["j_lower"].ctypes.data_as(POINTER(c_int32))))
+        return out
 
     def clamp_events(self):
         """(density events, speed events), [B] each."""
@@ -196,6 +231,9 @@ class PolarPoint:
     finite: bool                 # every sample finite
     clamp_events: Tuple[int, int]
     history: Dict[str, np.ndarray] = field(repr=False, default_factory=dict)   # step, fx, fy, surf, rev of this angle
+    cm_mean: Optional[float] = None      # pitching-moment coefficient about the quarter chord, nose-up positive (None: not sampled)
+    cm_std: Optional[float] = None
+    surface: Optional[Dict[str, np.ndarray]] = field(repr=False, default=None)   # x_over_c, cp_upper, cp_lower per body column
 
     @property
     def converged(self) -> bool:
@@ -223,8 +261,33 @@ def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
     return fy[keep] / q, fx[keep] / q, rev[keep] / surf[keep]
 
 
-def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0)) -> PolarPoint:
-    """Statistics of one angle's force history."""
+def moment_coefficient(mz, u0: float, nx: int):
+    """Cm = -Mz / (U0^2/2 * chord_cells(nx)^2): Mz is counter-clockwise positive and the nose points in -x, so nose-up is clockwise."""
+    c = chord_cells(nx)
+    return -np.asarray(mz, np.float64) / (0.5 * u0 * u0 * (c * c))
+
+
+def quarter_chord(nx: int, ny: int) -> Tuple[float, float]:
+    """The quarter-chord point (0.25, 0) in lattice units: the pivot of geometry.rotate, so the same point at every angle."""
+    return (0.25 - geo.DX0) / (geo.DX1 - geo.DX0) * nx, ny / 2
+
+
+def surface_cp(surface: Dict[str, np.ndarray], alpha: float, u0: float) -> Dict[str, np.ndarray]:
+    """Cp(x/c) of one member from PolarEngine.surface: Cp = (mean rho - 1) / (1.5 U0^2), k_ranges' formula, NaN where a column
+    has no sample on that side.  Columns that hold a body only.  x/c is the point of the chord line that the rotation about
+    (0.25, 0) by `alpha` puts at the column centre's world x: 0.25 + (x - 0.25) / cos(alpha)."""
+    nu, nl = surface["n_upper"], surface["n_lower"]
+    nx = nu.size
+    body = (surface["j_upper"] >= 0) | (surface["j_lower"] >= 0)
+    xw = geo.DX0 + (np.arange(nx) + 0.5) / nx * (geo.DX1 - geo.DX0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cpu = (surface["rho_upper"] / nu - 1.0) / (1.5 * u0 * u0)
+        cpl = (surface["rho_lower"] / nl - 1.0) / (1.5 * u0 * u0)
+    return {"x_over_c": (0.25 + (xw - 0.25) / math.cos(math.radians(alpha)))[body], "cp_upper": cpu[body], "cp_lower": cpl[body]}
+
+
+def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0), *, mz=None, surface=None) -> PolarPoint:
+    """Statistics of one angle's force history; with `mz` (the sampled moments) also Cm over the samples that have a body surface."""
     cl, cd, sep = raw_coefficients(fx, fy, surf, rev, u0, nx)
     finite = bool(np.all(np.isfinite(np.asarray(fx, np.float64))) and np.all(np.isfinite(np.asarray(fy, np.float64))))
     n = int(cl.size)
@@ -232,19 +295,27 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
     hist = {"step": np.asarray(step, np.int64), "fx": np.asarray(fx, np.float64), "fy": np.asarray(fy, np.float64),
             "surf": np.asarray(surf, np.int64), "rev": np.asarray(rev, np.int64)}
     sep_mean = float(sep.mean()) if n else 0.0
+    cm_mean = cm_std = None
+    if mz is not None:
+        hist["mz"] = np.asarray(mz, np.float64)
+        kept = hist["mz"][hist["surf"] != 0]
+        cm_mean, cm_std = (float(moment_coefficient(kept.mean(), u0, nx)), float(abs(moment_coefficient(kept.std(), u0, nx)))) if n else (nan, nan)
     return PolarPoint(alpha=float(alpha), cl_mean=float(cl.mean()) if n else nan, cl_std=float(cl.std()) if n else nan,
                       cd_mean=float(cd.mean()) if n else nan, cd_std=float(cd.std()) if n else nan, sep_frac=sep_mean,
                       separation=stall_label(sep_mean), samples=n, finite=finite,
-                      clamp_events=(int(clamp_events[0]), int(clamp_events[1])), history=hist)
+                      clamp_events=(int(clamp_events[0]), int(clamp_events[1])), history=hist, cm_mean=cm_mean, cm_std=cm_std,
+                      surface=surface)
 
 
 # ---- the sweep -------------------------------------------------------------------------------
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
-              samples: int = 256, sample_every: int = 12, device: int = 0) -> PolarResult:
+              samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
-    win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58."""
+    win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
+    `loads`: also sample the pitching moment about the quarter chord and the surface pressure (PolarPoint.cm_mean / cm_std /
+    surface); the forces and the flow are the same bits either way."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -262,13 +333,17 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device) as eng:
         eng.set_masks(masks)
         eng.init_equilibrium(u0)
+        if loads:
+            eng.enable_loads(*quarter_chord(nx, ny))
         if warmup_steps:
             eng.step(warmup_steps, tau, u0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
         eng.step(samples * sample_every, tau, u0, sample_every=sample_every)
         h = eng.history()
         rho_ev, u_ev = eng.clamp_events()
-    points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]))
+        surfaces = [surface_cp(eng.surface(m), a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
+    points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]),
+                          mz=h["mz"][:, m] if loads else None, surface=surfaces[m])
               for m, a in enumerate(alphas)]
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every))
 
@@ -281,7 +356,8 @@ def sweep_alphas(start: float, end: float, step: float) -> List[float]:
 
 
 def polar_rows(result: PolarResult) -> List[dict]:
-    """The page's sweep table (pages/Airfoil_Analysis.py:950-966), one row per angle.  The LBM computes no moment: Cm is "—".
+    """The page's sweep table (pages/Airfoil_Analysis.py:950-966), one row per angle.  Cm is the mean moment coefficient of a
+    point that carries one (run_polar(loads=True)), "—" otherwise.
     A point converged when every sample is finite and the stability net held no site at a bound; a failed one shows "—"
     throughout, as the page's failed rows do."""
     rows = []
@@ -289,7 +365,8 @@ def polar_rows(result: PolarResult) -> List[dict]:
         if p.converged:
             ld = p.cl_mean / p.cd_mean if p.cd_mean != 0 else None
             rows.append({"α (°)": p.alpha, "CL": round(p.cl_mean, 4), "CD": round(p.cd_mean, 5),
-                         "L/D": round(ld, 2) if ld is not None else "—", "Cm": "—", "Status": "✅ Converged"})
+                         "L/D": round(ld, 2) if ld is not None else "—",
+                         "Cm": round(p.cm_mean, 4) if p.cm_mean is not None else "—", "Status": "✅ Converged"})
         else:
             rows.append({"α (°)": p.alpha, "CL": "—", "CD": "—", "L/D": "—", "Cm": "—", "Status": "❌ Failed"})
     return rows

@@ -65,6 +65,32 @@ WTP_API int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_event
 /* One member's populations [9][NY][NX] / macroscopic fields [NY][NX] (any of rho, ux, uy may be NULL). */
 WTP_API int wtp_read_f(wtp_batch *b, int member, void *f_out);
 WTP_API int wtp_read_macro(wtp_batch *b, int member, void *rho, void *ux, void *uy);
+/*
+ * Surface loads: the pitching moment and the chordwise surface density of every member, reduced on the device behind
+ * the force reduction of a sampled step.  Definitions (cell (i, j), column i, row j from the bottom, covers
+ * [i, i+1) x [j, j+1) lattice units): as in wt_forces, every fluid cell with a solid 4-neighbour inside the grid in
+ * direction d adds a face with p = (double)rho / 3 and force F = p d on the body, at r = (i + 0.5 + 0.5 dx, j + 0.5 + 0.5 dy).
+ *   Mz = sum over the faces of (r.x - xref) F.y - (r.y - yref) F.x, in double, counter-clockwise positive.
+ *   Surface: per column that holds a solid cell, the upper sample is the fluid cell directly above its highest solid
+ *   cell and the lower sample the one directly below its lowest (none where that solid cell touches row 0 / NY-1);
+ *   the device keeps the sum of (double)rho over the history samples, in sample order, and the number of samples.
+ * A sample's Mz does not depend on the order in which the device ran its blocks: it is the same bits from run to run.
+ *
+ * wtp_enable_loads switches the sampling on.  xref, yref: [B], lattice units, finite.  It allocates the buffers; from the
+ * next sample on, every history row also records Mz and adds to the surface sums.  Calling it again replaces the reference
+ * points and clears the sums; history rows sampled before the latest call read NaN.  A batch that never calls it behaves,
+ * and costs, as before.  wtp_init_equilibrium and wtp_clear_history zero the sums; wtp_set_masks zeroes those of the
+ * members it touches.  The three read-backs below fail with WT_ERR_STATE while loads are not enabled.
+ */
+WTP_API int wtp_enable_loads(wtp_batch *b, const double *xref, const double *yref);
+/* Mz of history rows [first, first+count): [count][B]. */
+WTP_API int wtp_history_moment(wtp_batch *b, int first, int count, double *mz);
+/* Mz of every member on the last emitted state, [B]: the moment twin of wtp_forces.  Adds nothing to the surface sums. */
+WTP_API int wtp_moment(wtp_batch *b, double *mz);
+/* One member's surface sums: rho_upper, rho_lower [NX] doubles, n_upper, n_lower [NX] sample counts, and the rows
+ * j_upper, j_lower [NX] of the sampled fluid cells (-1 where there is none) of the member's current mask.  No output may be NULL. */
+WTP_API int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *rho_lower, int64_t *n_upper, int64_t *n_lower,
+                        int32_t *j_upper, int32_t *j_lower);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

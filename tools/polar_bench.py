@@ -6,7 +6,14 @@
 Per line: us per batched step and member-steps per second (host clock around wtp_step + wtp_sync, after a warm-up), aggregate
 GLUPS, algorithmic bytes per step (72 B per site fp32, + 12 B per site on the emitting last step of a call) over the time as a
 fraction of 8 TB/s, and the same member-steps taken by B libwindtunnel handles stepped one after another (library defaults),
-timed in the same process.  Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
+timed in the same process.
+
+    python tools/polar_bench.py --loads [--sizes 320x160] [--members 32] [--steps 1200] [--sample-every 12] [--repeats 7]
+
+The sampled batched step with and without surface loads (wtp_enable_loads: one k_loads_batch behind every k_forces_batch): the two
+variants are timed in turn, `repeats` times each in the same process, and the line gives the median and the range of each.
+
+Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
 import json
@@ -42,6 +49,46 @@ def bench_batch(nx, ny, b, steps, warmup, masks):
         return time.perf_counter() - t0
 
 
+def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats):
+    """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats."""
+    out = []
+    with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1) as eng:
+        eng.set_masks(masks)
+        eng.init_equilibrium(U0)
+        if loads:
+            eng.enable_loads(*pkg.polar.quarter_chord(nx, ny))
+        eng.step(warmup - warmup % every, TAU, U0)
+        eng.sync()
+        for _ in range(repeats):
+            eng.clear_history()
+            eng.sync()
+            t0 = time.perf_counter()
+            eng.step(steps, TAU, U0, sample_every=every)
+            eng.sync()
+            out.append(time.perf_counter() - t0)
+    return out
+
+
+def loads_cost(a):
+    for size in a.sizes.split(","):
+        nx, ny = (int(v) for v in size.split("x"))
+        for b in (int(v) for v in a.members.split(",")):
+            masks = _masks(nx, ny, b)
+            t = {False: [], True: []}
+            for r in range(a.repeats):                 # in turn, so that a drift of the clocks lands on both
+                for loads in (False, True):
+                    t[loads] += bench_sampled(nx, ny, b, a.steps, a.warmup, masks, a.sample_every, loads, 1)
+            us = {k: np.array(v) / a.steps * 1e6 for k, v in t.items()}
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            samples = a.steps // a.sample_every
+            print(json.dumps({"tool": "polar_bench --loads", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
+                              "sample_every": a.sample_every, "repeats": a.repeats,
+                              "us_per_step_plain_median": round(med[False], 3), "us_per_step_plain_range": [round(float(us[False].min()), 3), round(float(us[False].max()), 3)],
+                              "us_per_step_loads_median": round(med[True], 3), "us_per_step_loads_range": [round(float(us[True].min()), 3), round(float(us[True].max()), 3)],
+                              "loads_us_per_sample": round((med[True] - med[False]) * a.steps / samples, 3),
+                              "loads_fraction_of_step": round(med[True] / med[False] - 1.0, 5)}), flush=True)
+
+
 def bench_sequential(nx, ny, b, steps, warmup, masks):
     hs = []
     try:
@@ -72,7 +119,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--no-sequential", action="store_true", help="time the batch only")
+    ap.add_argument("--loads", action="store_true", help="the sampled step with and without surface loads")
+    ap.add_argument("--sample-every", type=int, default=12)
+    ap.add_argument("--repeats", type=int, default=7)
     a = ap.parse_args()
+    if a.loads:
+        return loads_cost(a)
     for size in a.sizes.split(","):
         nx, ny = (int(v) for v in size.split("x"))
         for b in (int(v) for v in a.members.split(",")):
