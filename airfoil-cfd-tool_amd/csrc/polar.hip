@@ -10,6 +10,10 @@
 // Surface loads (wtp_enable_loads) are a reduction of their own, k_loads_batch, launched behind k_forces_batch: the pitching
 // moment of the force model's faces about a per-member point and the running sums of rho above and below the body, one
 // wave per (member, column).  It shares nothing with the force reduction, whose values it leaves as they are.
+//
+// Momentum exchange (wtp_enable_mex) is a third reduction, k_mex_batch, launched behind the other two: the force and the moment
+// that the half-way bounce-back links hand to the body, summed from the populations of the lattice the step wrote.  It reads
+// the lattice and the mask and writes buffers of its own.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -53,7 +57,12 @@ static int fail(int code, const char *fmt, ...)
 
 static const int kReduceBlocks = 1024;     // wt_forces' cap on the reduction's block count
 static const int kLoadsWaves = 16;         // waves (columns) of one k_loads_batch block
-static const int kTicketStride = 32;       // unsigned ints between the members' k_loads_batch tickets: one 128-byte line each
+static const int kTicketStride = 32;       // unsigned ints between the members' k_loads_batch / k_mex_batch tickets: one 128-byte line each
+#ifndef WTP_MEX_WINDOW
+#define WTP_MEX_WINDOW 1                   // 1: k_mex_batch visits a member's body columns only; 0: every interior column (measurements)
+#endif
+
+struct MexPartial { double fx, fy, mz; long long links; };     // one column's sums of k_mex_batch
 
 // Element strides between consecutive members of each array.  Every stride is rounded to 4 KiB and grown by 17 KiB, as
 // wt_create's plane stride is, so that the members' lattices do not all start on the same HBM channels.
@@ -93,6 +102,15 @@ struct wtp_batch {
     double *h_mz = nullptr;              // history [cap + 1][B]; row cap = wtp_moment's scratch row
     double *s_rho = nullptr;             // [B][2][NX]: sums of rho over the samples, upper then lower
     long long *s_cnt = nullptr;          // [B][2][NX]: samples added
+    // momentum exchange (wtp_enable_mex); every pointer is null until then
+    bool mex = false;
+    std::vector<int32_t> mex_win;        // [B][2]: first column that can own a link and the number of such columns, from the masks
+    int32_t *x_win = nullptr;            // ... on the device
+    double *x_ref = nullptr;             // [B][2]: xref, yref
+    MexPartial *x_col = nullptr;         // [B][NX]: the columns' partials of the running reduction
+    unsigned int *x_tickets = nullptr;   // [B] tickets, kTicketStride apart
+    double *h_xfx = nullptr, *h_xfy = nullptr, *h_xmz = nullptr;     // history [cap + 1][B]; row cap = wtp_mex's scratch row
+    long long *h_xlinks = nullptr;
     bool inited = false;
     long long steps_done = 0;
 };
@@ -235,6 +253,109 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
     if (threadIdx.x == 0) { mz[m] = s; tickets[m * kTicketStride] = 0; }
 }
 
+// Momentum exchange of every member in one launch: grid (ceil(W / kLoadsWaves), B), one wave per (member, column), W the widest
+// member's window.  Definition (include/wt_polar.h): directions e_k, k = 1..8, as d2q9.hpp / html:238-248; cell (i, j) covers
+// [i, i+1) x [j, j+1).  After step n the current lattice holds, in every interior fluid cell x (not solid, 1 <= i <= NX-2,
+// 1 <= j <= NY-2: the cells that take STEP_FS's interior branch), the post-collision populations f*_k(x, n).  A link is a pair
+// (interior fluid cell x, direction k) whose neighbour x + e_k is solid.  In step n+1 the population f*_k(x, n) that leaves x
+// along the link comes back to x as population opp(k) unchanged (half-way bounce-back), so the body receives the momentum
+// 2 f*_k(x, n) e_k per step from that link.  Hence, all in double from the stored values converted exactly:
+//   F = sum over the links of 2 (double)f*_k(x) e_k (diagonal links included),
+//   Mz = sum over the links of (r.x - xref) F_link.y - (r.y - yref) F_link.x, r = (i + 0.5 + 0.5 e_kx, j + 0.5 + 0.5 e_ky),
+//   links = the number of links.
+// No rest-state term is subtracted; boundary cells own no link.
+// A member's window win[m] = (first column, columns) holds every interior column next to one of its solid columns: no other
+// column can own a link.  A column is one contiguous run of the mask and of each population plane (y fastest), read in chunks of
+// 64 rows, one row per lane: the mask bytes of columns i-1, i, i+1 at rows j-1, j, j+1, then a population only on the lanes that
+// own a link in its direction.  The column's terms are added by wave_sum; the last block of a member to finish (ticket, as
+// k_loads_batch) adds the columns' partials in column order, so that a sample is the same bits from run to run.
+template <typename T>
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
+                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
+                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
+                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
+                                                   long long *__restrict__ links)
+{
+    const long m = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int nx = g.nxl, ny = g.ny;
+    const int width = win[2 * m + 1];
+    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
+    if (c < width) {                                                // (wave-uniform)
+        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
+        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
+        const T *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;               // column i of population plane 0
+        const double xr = ref[2 * m], yr = ref[2 * m + 1];
+        double sx = 0.0, sy = 0.0, sm = 0.0;
+        long long n = 0;
+        for (int j0 = 0; j0 < ny; j0 += 64) {
+            const int j = j0 + lane;
+            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
+            if (j >= 1 && j <= ny - 2 && !mk[j]) {
+                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
+                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
+                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
+            }
+            if (__ballot(s != 0) == 0ULL) continue;
+#pragma unroll
+            for (int k = 1; k <= 8; k++) {
+                if (!(s >> k & 1u)) continue;
+                const double t = 2.0 * (double)fc[k * g.plane + j];
+                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
+                const double rx = ((double)i + 0.5) + 0.5 * (double)ex_of(k), ry = ((double)j + 0.5) + 0.5 * (double)ey_of(k);
+                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
+                sx += flx;
+                sy += fly;
+                sm += a - b;
+                n += 1;
+            }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
+        if (lane == 0) {
+            MexPartial p;
+            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
+            col[m * nx + c] = p;
+        }
+    }
+    constexpr int NT = kLoadsWaves * 64;
+    __shared__ int last;
+    __shared__ double sh[3][NT];
+    __shared__ long long shn[NT];
+    __syncthreads();                                                // the block's partials are written ...
+    if (threadIdx.x == 0) {
+        __threadfence();                                            // ... and visible device-wide before the block is counted
+        last = atomicAdd(&tickets[m * kTicketStride], 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    const volatile MexPartial *vc = col + m * nx;
+    const int w = (int)(threadIdx.x >> 6);
+    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
+    long long sn = 0;                                               // lane 0 of wave 3: links
+    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
+        const int q = c0 + (int)threadIdx.x;
+        const bool in = q < width;
+        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
+        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
+        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
+        shn[threadIdx.x] = in ? vc[q].links : 0;
+        __syncthreads();
+        if (lane == 0 && w < 4) {
+            const int cnt = width - c0 < NT ? width - c0 : NT;
+            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
+            else for (int k = 0; k < cnt; k++) sn += shn[k];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
+        else if (w == 1) fy[m] = s;
+        else if (w == 2) mz[m] = s;
+        else if (w == 3) links[m] = sn;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // life cycle
 // ------------------------------------------------------------------------------------------
@@ -262,7 +383,8 @@ extern "C" int wtp_destroy(wtp_batch *b)
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets,
-                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage, b->l_ref, b->l_col, b->l_tickets, b->h_mz, b->s_rho, b->s_cnt};
+                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage, b->l_ref, b->l_col, b->l_tickets, b->h_mz, b->s_rho, b->s_cnt,
+                    b->x_win, b->x_ref, b->x_col, b->x_tickets, b->h_xfx, b->h_xfy, b->h_xmz, b->h_xlinks};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (b->st) (void)hipStreamDestroy(b->st);
     delete b;
@@ -303,6 +425,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     b->nb = (int)std::min<long>((total + 255) / 256, kReduceBlocks);
     b->mask_set.assign((size_t)members, 0);
     b->surf_rows.assign((size_t)members * 2 * nx, -1);
+    b->mex_win.assign((size_t)members * 2, 0);
 
     auto cleanup = [&](int rc) { wtp_destroy(b); return rc; };
 #define CREATE_TRY(expr)                                                                               \
@@ -343,7 +466,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.2 (gfx950, batched D2Q9 members, column-major SoA, surface loads)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.3 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -369,6 +492,24 @@ static void surface_rows(wtp_batch *b, int member, const uint8_t *m01)
         up[i] = (jhi >= 0 && jhi + 1 < ny) ? jhi + 1 : -1;
         lo[i] = (jlo < ny && jlo > 0) ? jlo - 1 : -1;
     }
+}
+
+// The columns of one [NY][NX] mask that can own a momentum-exchange link: the interior columns (1 .. NX-2) from the one before
+// its first solid column to the one after its last.  (first column, count); count 0 where the mask holds no solid cell.
+static void mex_window(wtp_batch *b, int member, const uint8_t *m01)
+{
+    const int nx = b->nx, ny = b->ny;
+    int first = nx, last = -1;
+    for (int j = 0; j < ny; j++)
+        for (int i = 0; i < nx; i++)
+            if (m01[(size_t)j * nx + i]) { if (i < first) first = i; if (i > last) last = i; }
+    int c0 = 1, c1 = nx - 2;
+#if WTP_MEX_WINDOW
+    if (last < 0) c1 = 0;
+    else { c0 = std::max(first - 1, 1); c1 = std::min(last + 1, nx - 2); }
+#endif
+    b->mex_win[2 * (size_t)member] = c0;
+    b->mex_win[2 * (size_t)member + 1] = std::max(c1 - c0 + 1, 0);
 }
 
 // Zero the surface sums of members [first, first+count), in stream order.  Nothing to do while loads are off.
@@ -397,6 +538,7 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
         const uint8_t *src = masks + (size_t)k * n;
         for (size_t q = 0; q < n; q++) m01[q] = src[q] ? 1 : 0;
         surface_rows(b, first + k, m01.data());
+        mex_window(b, first + k, m01.data());
         WT_TRY(clear_surface_sums(b, first + k, 1));            // the member's surface cells moved
         HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
         uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
@@ -410,6 +552,9 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
         HIP_TRY(hipStreamSynchronize(b->st));
         b->mask_set[(size_t)(first + k)] = 1;
     }
+    if (b->mex)                                  // (the stream is idle: samples already enqueued read the previous windows)
+        HIP_TRY(hipMemcpy(b->x_win + 2 * (size_t)first, b->mex_win.data() + 2 * (size_t)first, (size_t)count * 2 * sizeof(int32_t),
+                          hipMemcpyHostToDevice));
     return WT_OK;
 }
 
@@ -496,6 +641,20 @@ static int launch_loads(wtp_batch *b, int row, bool accumulate)
     return WT_OK;
 }
 
+// The momentum exchange of the current lattice into row `row` of its history.
+template <typename T>
+static int launch_mex(wtp_batch *b, int row)
+{
+    int widest = 1;                              // (a batch without a body still runs one block per member, which writes zeros)
+    for (int m = 0; m < b->members; m++) widest = std::max(widest, (int)b->mex_win[2 * (size_t)m + 1]);
+    const size_t off = (size_t)row * b->members;
+    hipLaunchKernelGGL(k_mex_batch<T>, dim3((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), dim3(kLoadsWaves * 64), 0,
+                       b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms, (const double *)b->x_ref,
+                       (const int32_t *)b->x_win, b->x_col, b->x_tickets, b->h_xfx + off, b->h_xfy + off, b->h_xmz + off, b->h_xlinks + off);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 template <typename T>
 static int step_impl(wtp_batch *b, int nsteps, int sample_every)
 {
@@ -520,6 +679,7 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         if (sample) {
             WT_TRY(launch_forces<T>(b, (int)b->h_step.size()));
             if (b->loads) WT_TRY(launch_loads<T>(b, (int)b->h_step.size(), true));
+            if (b->mex) WT_TRY(launch_mex<T>(b, (int)b->h_step.size()));
             b->h_step.push_back(n);
         }
     }
@@ -674,6 +834,83 @@ extern "C" int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *
     HIP_TRY(hipMemcpy(n_lower, b->s_cnt + off + nx, nx * sizeof(long long), hipMemcpyDeviceToHost));
     memcpy(j_upper, b->surf_rows.data() + off, nx * sizeof(int32_t));
     memcpy(j_lower, b->surf_rows.data() + off + nx, nx * sizeof(int32_t));
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// momentum exchange
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_mex(wtp_batch *b, const double *xref, const double *yref)
+{
+    WT_TRY(check_batch(b));
+    if (!xref || !yref) return fail(WT_ERR_ARG, "xref or yref is null");
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", m);
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->members, rows = (size_t)b->cap + 1;
+    const bool first = !b->h_xlinks;
+    if (!b->x_win) HIP_TRY(hipMalloc((void **)&b->x_win, B * 2 * sizeof(int32_t)));
+    if (!b->x_ref) HIP_TRY(hipMalloc((void **)&b->x_ref, B * 2 * sizeof(double)));
+    if (!b->x_col) HIP_TRY(hipMalloc((void **)&b->x_col, B * b->nx * sizeof(MexPartial)));
+    if (!b->x_tickets) HIP_TRY(hipMalloc((void **)&b->x_tickets, B * kTicketStride * sizeof(unsigned int)));
+    if (!b->h_xfx) HIP_TRY(hipMalloc((void **)&b->h_xfx, rows * B * sizeof(double)));
+    if (!b->h_xfy) HIP_TRY(hipMalloc((void **)&b->h_xfy, rows * B * sizeof(double)));
+    if (!b->h_xmz) HIP_TRY(hipMalloc((void **)&b->h_xmz, rows * B * sizeof(double)));
+    if (!b->h_xlinks) HIP_TRY(hipMalloc((void **)&b->h_xlinks, rows * B * sizeof(long long)));
+    std::vector<double> ref(B * 2);
+    for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
+    HIP_TRY(hipStreamSynchronize(b->st));        // samples already enqueued read the previous points
+    HIP_TRY(hipMemcpy(b->x_ref, ref.data(), ref.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->x_win, b->mex_win.data(), B * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(b->x_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
+    HIP_TRY(hipMemsetAsync(b->h_xmz, 0xFF, rows * B * sizeof(double), b->st));    // rows sampled before this call hold no Mz about these points: NaN
+    if (first) {                                 // rows sampled before the first call hold nothing at all: NaN forces, -1 links
+        HIP_TRY(hipMemsetAsync(b->h_xfx, 0xFF, rows * B * sizeof(double), b->st));
+        HIP_TRY(hipMemsetAsync(b->h_xfy, 0xFF, rows * B * sizeof(double), b->st));
+        HIP_TRY(hipMemsetAsync(b->h_xlinks, 0xFF, rows * B * sizeof(long long), b->st));
+    }
+    b->mex = true;
+    return WT_OK;
+}
+
+static int check_mex(const wtp_batch *b)
+{
+    if (!b->mex) return fail(WT_ERR_STATE, "the momentum exchange is not enabled (wtp_enable_mex)");
+    return WT_OK;
+}
+
+extern "C" int wtp_history_mex(wtp_batch *b, int first, int count, double *fx, double *fy, double *mz, int64_t *links)
+{
+    WT_TRY(check_batch(b));
+    const int held = (int)b->h_step.size();
+    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    WT_TRY(check_mex(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
+    if (n) {
+        if (fx) HIP_TRY(hipMemcpy(fx, b->h_xfx + off, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (fy) HIP_TRY(hipMemcpy(fy, b->h_xfy + off, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (mz) HIP_TRY(hipMemcpy(mz, b->h_xmz + off, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (links) HIP_TRY(hipMemcpy(links, b->h_xlinks + off, n * sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t *links)
+{
+    WT_TRY(check_batch(b));
+    if (!fx || !fy || !mz || !links) return fail(WT_ERR_ARG, "null output");
+    WT_TRY(check_mex(b));
+    WT_TRY(check_ready(b));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? launch_mex<float>(b, b->cap) : launch_mex<double>(b, b->cap));     // the scratch row
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t off = (size_t)b->cap * b->members, B = (size_t)b->members;
+    HIP_TRY(hipMemcpy(fx, b->h_xfx + off, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fy, b->h_xfy + off, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mz, b->h_xmz + off, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(links, b->h_xlinks + off, B * sizeof(long long), hipMemcpyDeviceToHost));
     return WT_OK;
 }
 

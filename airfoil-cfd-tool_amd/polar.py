@@ -6,7 +6,8 @@ sweep are the members of one batch of ``libwtpolar.so`` (include/wt_polar.h): ev
 bit-identical to a :class:`~airfoil_cfd_tool_amd.WindTunnel` with the same inputs, and all of them advance by one
 kernel launch per step.  Lift, drag and separation are sampled on the device into a history that is read once; with
 surface loads enabled (``PolarEngine.enable_loads``, ``run_polar(loads=True)``) so are the pitching moment and the
-chordwise surface pressure.
+chordwise surface pressure; with the momentum exchange enabled (``PolarEngine.enable_momentum_exchange``,
+``run_polar(total_forces=True)``) a second force read-out that holds pressure and friction together.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -18,7 +19,7 @@ import ctypes
 import math
 import os
 from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -34,6 +35,7 @@ EXPORTS = (
     "wtp_create", "wtp_destroy", "wtp_last_error", "wtp_version", "wtp_set_masks", "wtp_init_equilibrium", "wtp_step",
     "wtp_history", "wtp_clear_history", "wtp_forces", "wtp_clamp_events", "wtp_read_f", "wtp_read_macro", "wtp_sync",
     "wtp_enable_loads", "wtp_history_moment", "wtp_moment", "wtp_surface",
+    "wtp_enable_mex", "wtp_history_mex", "wtp_mex",
 )
 
 _lib = None
@@ -72,6 +74,9 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_history_moment": ([B, c_int, c_int, dp], c_int),
         "wtp_moment": ([B, dp], c_int),
         "wtp_surface": ([B, c_int, dp, dp, ip, ip, POINTER(c_int32), POINTER(c_int32)], c_int),
+        "wtp_enable_mex": ([B, dp, dp], c_int),
+        "wtp_history_mex": ([B, c_int, c_int, dp, dp, dp, ip], c_int),
+        "wtp_mex": ([B, dp, dp, dp, ip], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -109,6 +114,7 @@ class PolarEngine:
         self.nx, self.ny, self.members, self.history_cap = int(nx), int(ny), int(members), int(history_cap)
         self._b = c_void_p()
         self.loads_enabled = False
+        self.mex_enabled = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -149,7 +155,8 @@ class PolarEngine:
         _check(self._lib.wtp_step(self._b, int(nsteps), _dp(t), _dp(u), int(sample_every)))
 
     def history(self) -> Dict[str, np.ndarray]:
-        """Every row held: step [R], fx / fy [R][B] float64, surf / rev [R][B] int64; with loads enabled also mz [R][B] float64."""
+        """Every row held: step [R], fx / fy [R][B] float64, surf / rev [R][B] int64; with loads enabled also mz [R][B] float64;
+        with the momentum exchange enabled also fx_mex / fy_mex / mz_mex [R][B] float64 and links [R][B] int64."""
         rows = _check(self._lib.wtp_history(self._b, 0, 0, None, None, None, None, None))
         B = self.members
         out = {"step": np.empty(rows, np.int64), "fx": np.empty((rows, B)), "fy": np.empty((rows, B)),
@@ -159,6 +166,11 @@ class PolarEngine:
         if self.loads_enabled:
             out["mz"] = np.empty((rows, B))
             _check(self._lib.wtp_history_moment(self._b, 0, rows, _dp(out["mz"])))
+        if self.mex_enabled:
+            out.update({"fx_mex": np.empty((rows, B)), "fy_mex": np.empty((rows, B)), "mz_mex": np.empty((rows, B)),
+                        "links": np.empty((rows, B), np.int64)})
+            _check(self._lib.wtp_history_mex(self._b, 0, rows, _dp(out["fx_mex"]), _dp(out["fy_mex"]), _dp(out["mz_mex"]),
+                                             _ip(out["links"])))
         return out
 
     def clear_history(self) -> None:
@@ -194,6 +206,21 @@ class PolarEngine:
                                      _ip(out["n_lower"]), out["j_upper"].ctypes.data_as(POINTER(c_int32)),
                                      out["j_lower"].ctypes.data_as(POINTER(c_int32))))
         return out
+
+    def enable_momentum_exchange(self, xref, yref) -> None:
+        """Sample the momentum-exchange force (pressure and friction together), its moment about (xref, yref) (one value or [B],
+        lattice units) and the number of links from the next sample on (wt_polar.h).  Calling it again replaces the points.
+        Independent of enable_loads."""
+        x, y = _f64(xref, self.members), _f64(yref, self.members)
+        _check(self._lib.wtp_enable_mex(self._b, _dp(x), _dp(y)))
+        self.mex_enabled = True
+
+    def momentum_exchange(self):
+        """(fx, fy, mz, links), [B] each, of the current lattice: the momentum-exchange twin of forces() / moment()."""
+        B = self.members
+        fx, fy, mz, links = np.empty(B), np.empty(B), np.empty(B), np.empty(B, np.int64)
+        _check(self._lib.wtp_mex(self._b, _dp(fx), _dp(fy), _dp(mz), _ip(links)))
+        return fx, fy, mz, links
 
     def clamp_events(self):
         """(density events, speed events), [B] each."""
@@ -234,6 +261,22 @@ class PolarPoint:
     cm_mean: Optional[float] = None      # pitching-moment coefficient about the quarter chord, nose-up positive (None: not sampled)
     cm_std: Optional[float] = None
     surface: Optional[Dict[str, np.ndarray]] = field(repr=False, default=None)   # x_over_c, cp_upper, cp_lower per body column
+    # Momentum-exchange ("total": pressure + friction) statistics, None when not sampled.  Init-only: they are accepted by the
+    # constructor after the fields above and kept as attributes, while dataclasses.fields(), repr and == stay those of the
+    # pressure read-out, which callers enumerate.
+    cl_total_mean: InitVar[Optional[float]] = None
+    cl_total_std: InitVar[Optional[float]] = None
+    cd_total_mean: InitVar[Optional[float]] = None
+    cd_total_std: InitVar[Optional[float]] = None
+    cm_total_mean: InitVar[Optional[float]] = None
+    cm_total_std: InitVar[Optional[float]] = None
+    cd_friction_mean: InitVar[Optional[float]] = None      # cd_total_mean - cd_mean
+
+    def __post_init__(self, cl_total_mean, cl_total_std, cd_total_mean, cd_total_std, cm_total_mean, cm_total_std, cd_friction_mean):
+        self.cl_total_mean, self.cl_total_std = cl_total_mean, cl_total_std
+        self.cd_total_mean, self.cd_total_std = cd_total_mean, cd_total_std
+        self.cm_total_mean, self.cm_total_std = cm_total_mean, cm_total_std
+        self.cd_friction_mean = cd_friction_mean
 
     @property
     def converged(self) -> bool:
@@ -286,8 +329,11 @@ def surface_cp(surface: Dict[str, np.ndarray], alpha: float, u0: float) -> Dict[
     return {"x_over_c": (0.25 + (xw - 0.25) / math.cos(math.radians(alpha)))[body], "cp_upper": cpu[body], "cp_lower": cpl[body]}
 
 
-def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0), *, mz=None, surface=None) -> PolarPoint:
-    """Statistics of one angle's force history; with `mz` (the sampled moments) also Cm over the samples that have a body surface."""
+def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0), *, mz=None, surface=None,
+                fx_mex=None, fy_mex=None, mz_mex=None, links=None) -> PolarPoint:
+    """Statistics of one angle's force history; with `mz` (the sampled moments) also Cm over the samples that have a body surface.
+    With `fx_mex`, `fy_mex`, `mz_mex` (the sampled momentum exchange; all three or none) also the total coefficients over the same
+    samples, with the same normalisation: CL = fy/q, CD = fx/q, Cm = -mz/(q chord_cells(nx)); `links` only joins the history."""
     cl, cd, sep = raw_coefficients(fx, fy, surf, rev, u0, nx)
     finite = bool(np.all(np.isfinite(np.asarray(fx, np.float64))) and np.all(np.isfinite(np.asarray(fy, np.float64))))
     n = int(cl.size)
@@ -300,22 +346,45 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
         hist["mz"] = np.asarray(mz, np.float64)
         kept = hist["mz"][hist["surf"] != 0]
         cm_mean, cm_std = (float(moment_coefficient(kept.mean(), u0, nx)), float(abs(moment_coefficient(kept.std(), u0, nx)))) if n else (nan, nan)
+    cd_mean = float(cd.mean()) if n else nan
+    total = {}
+    given = [v is not None for v in (fx_mex, fy_mex, mz_mex)]
+    if any(given):
+        if not all(given):
+            raise ValueError("fx_mex, fy_mex and mz_mex come together")
+        hist.update({"fx_mex": np.asarray(fx_mex, np.float64), "fy_mex": np.asarray(fy_mex, np.float64),
+                     "mz_mex": np.asarray(mz_mex, np.float64)})
+        if links is not None:
+            hist["links"] = np.asarray(links, np.int64)
+        keep = hist["surf"] != 0
+        q = 0.5 * u0 * u0 * chord_cells(nx)
+        finite = finite and bool(np.all(np.isfinite(hist["fx_mex"])) and np.all(np.isfinite(hist["fy_mex"])))
+        for name, v in (("cl_total", hist["fy_mex"][keep] / q), ("cd_total", hist["fx_mex"][keep] / q)):
+            total[name + "_mean"], total[name + "_std"] = (float(v.mean()), float(v.std())) if n else (nan, nan)
+        kept = hist["mz_mex"][keep]                  # (as cm_mean: the coefficient of the mean moment)
+        total["cm_total_mean"], total["cm_total_std"] = (float(moment_coefficient(kept.mean(), u0, nx)),
+                                                         float(abs(moment_coefficient(kept.std(), u0, nx)))) if n else (nan, nan)
+        total["cd_friction_mean"] = total["cd_total_mean"] - cd_mean
     return PolarPoint(alpha=float(alpha), cl_mean=float(cl.mean()) if n else nan, cl_std=float(cl.std()) if n else nan,
-                      cd_mean=float(cd.mean()) if n else nan, cd_std=float(cd.std()) if n else nan, sep_frac=sep_mean,
+                      cd_mean=cd_mean, cd_std=float(cd.std()) if n else nan, sep_frac=sep_mean,
                       separation=stall_label(sep_mean), samples=n, finite=finite,
                       clamp_events=(int(clamp_events[0]), int(clamp_events[1])), history=hist, cm_mean=cm_mean, cm_std=cm_std,
-                      surface=surface)
+                      surface=surface, **total)
 
 
 # ---- the sweep -------------------------------------------------------------------------------
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
-              samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True) -> PolarResult:
+              samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
+              total_forces: bool = False) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
     `loads`: also sample the pitching moment about the quarter chord and the surface pressure (PolarPoint.cm_mean / cm_std /
-    surface); the forces and the flow are the same bits either way."""
+    surface); the forces and the flow are the same bits either way.
+    `total_forces`: also sample the momentum exchange, the force of pressure and friction together and its moment about the
+    quarter chord (PolarPoint.cl_total_mean ... cd_friction_mean; polar_rows(result, forces="total")).  Off by default: the
+    sweep then runs, and costs, what it did without it; every other value is the same bits either way."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -335,6 +404,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         eng.init_equilibrium(u0)
         if loads:
             eng.enable_loads(*quarter_chord(nx, ny))
+        if total_forces:
+            eng.enable_momentum_exchange(*quarter_chord(nx, ny))
         if warmup_steps:
             eng.step(warmup_steps, tau, u0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
@@ -343,7 +414,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
     points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]),
-                          mz=h["mz"][:, m] if loads else None, surface=surfaces[m])
+                          mz=h["mz"][:, m] if loads else None, surface=surfaces[m],
+                          **({k: h[k][:, m] for k in ("fx_mex", "fy_mex", "mz_mex", "links")} if total_forces else {}))
               for m, a in enumerate(alphas)]
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every))
 
@@ -355,12 +427,29 @@ def sweep_alphas(start: float, end: float, step: float) -> List[float]:
             if round(start + i * step, 2) <= end + 1e-9]
 
 
-def polar_rows(result: PolarResult) -> List[dict]:
+def polar_rows(result: PolarResult, forces: str = "pressure") -> List[dict]:
     """The page's sweep table (pages/Airfoil_Analysis.py:950-966), one row per angle.  Cm is the mean moment coefficient of a
     point that carries one (run_polar(loads=True)), "—" otherwise.
     A point converged when every sample is finite and the stability net held no site at a bound; a failed one shows "—"
-    throughout, as the page's failed rows do."""
+    throughout, as the page's failed rows do.
+    forces="total" (every point must carry the momentum exchange, run_polar(total_forces=True), else ValueError): CL, CD, L/D
+    and Cm from the totals, and between CD and L/D the pressure drag CDp and the friction drag CDf = CD - CDp."""
+    if forces not in ("pressure", "total"):
+        raise ValueError(f'forces must be "pressure" or "total", got {forces!r}')
     rows = []
+    if forces == "total":
+        if any(p.cd_total_mean is None for p in result.points):
+            raise ValueError('forces="total" needs the momentum exchange of every point: run_polar(total_forces=True)')
+        for p in result.points:
+            if p.converged:
+                ld = p.cl_total_mean / p.cd_total_mean if p.cd_total_mean != 0 else None
+                rows.append({"α (°)": p.alpha, "CL": round(p.cl_total_mean, 4), "CD": round(p.cd_total_mean, 5),
+                             "CDp": round(p.cd_mean, 5), "CDf": round(p.cd_friction_mean, 5),
+                             "L/D": round(ld, 2) if ld is not None else "—", "Cm": round(p.cm_total_mean, 4), "Status": "✅ Converged"})
+            else:
+                rows.append({"α (°)": p.alpha, "CL": "—", "CD": "—", "CDp": "—", "CDf": "—", "L/D": "—", "Cm": "—",
+                             "Status": "❌ Failed"})
+        return rows
     for p in result.points:
         if p.converged:
             ld = p.cl_mean / p.cd_mean if p.cd_mean != 0 else None

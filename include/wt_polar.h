@@ -91,6 +91,41 @@ WTP_API int wtp_moment(wtp_batch *b, double *mz);
  * j_upper, j_lower [NX] of the sampled fluid cells (-1 where there is none) of the member's current mask.  No output may be NULL. */
 WTP_API int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *rho_lower, int64_t *n_upper, int64_t *n_lower,
                         int32_t *j_upper, int32_t *j_lower);
+/*
+ * Momentum exchange: the force (pressure and friction together) and the moment that the bounce-back links hand to the
+ * body, reduced on the device from the populations behind the force reduction of a sampled step.  wtp_history's fx, fy
+ * stay the page's pressure-only read-out; this is a second, independent one.  Definition:
+ *   Directions e_k, k = 1..8, as d2q9.hpp / html:238-248.  Cell (i, j) covers [i, i+1) x [j, j+1) lattice units, as in the
+ *   loads.  After step n the current lattice holds, in every interior fluid cell x (not solid, 1 <= i <= NX-2,
+ *   1 <= j <= NY-2: the cells that take STEP_FS's interior branch), the post-collision populations f*_k(x, n).  A link is
+ *   a pair (interior fluid cell x, direction k) whose neighbour x + e_k is solid.  In step n+1 the population f*_k(x, n)
+ *   that leaves x along the link comes back to x as population opp(k) unchanged (half-way bounce-back), so the body
+ *   receives the momentum 2 f*_k(x, n) e_k per step from that link.  Hence, all in double from the stored values
+ *   converted exactly:
+ *     F = sum over the links of 2 (double)f*_k(x) e_k: the force on the body, lattice units, pressure and shear together
+ *       (diagonal links included: k = 5..8 count).
+ *     Mz = sum over the links of (r.x - xref) F_link.y - (r.y - yref) F_link.x with the link's midpoint
+ *       r = (i + 0.5 + 0.5 e_kx, j + 0.5 + 0.5 e_ky), counter-clockwise positive, about a per-member point as in
+ *       wtp_enable_loads.
+ *     links = the number of links (int64).
+ *   No rest-state term is subtracted (it cancels on a closed body and the sums are in double).  Boundary cells (inlet
+ *   column, top and bottom rows, outlet column) are not link owners: they do not bounce back.  The sample belongs to the
+ *   same step as the pressure sample: the populations are read from the lattice that step wrote.
+ * A sample does not depend on the order in which the device ran its blocks: it is the same bits from run to run.
+ *
+ * wtp_enable_mex switches the sampling on.  xref, yref: [B], lattice units, finite.  It allocates the buffers; from the
+ * next sample on, every history row also records F, Mz and links.  Calling it again replaces the reference points; history
+ * rows sampled before the latest call read NaN for Mz, rows sampled before the first call also NaN for F and -1 for links.
+ * It is independent of wtp_enable_loads: either, both or neither.  A batch that never calls it behaves, and costs, as
+ * before; with it on, every other value (forces, loads, populations, macroscopic fields) is the same bits.  The two
+ * read-backs below fail with WT_ERR_STATE while it is not enabled.
+ */
+WTP_API int wtp_enable_mex(wtp_batch *b, const double *xref, const double *yref);
+/* The momentum exchange of history rows [first, first+count): fx / fy / mz / links [count][B].  Any output pointer may be NULL. */
+WTP_API int wtp_history_mex(wtp_batch *b, int first, int count, double *fx, double *fy, double *mz, int64_t *links);
+/* The momentum exchange of every member on the current lattice, [B] each: the twin of wtp_forces / wtp_moment.  Adds no
+ * history row.  No output may be NULL. */
+WTP_API int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t *links);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

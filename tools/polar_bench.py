@@ -13,6 +13,12 @@ timed in the same process.
 The sampled batched step with and without surface loads (wtp_enable_loads: one k_loads_batch behind every k_forces_batch): the two
 variants are timed in turn, `repeats` times each in the same process, and the line gives the median and the range of each.
 
+    python tools/polar_bench.py --mex [--loads] [--lib PATH] [the same options]
+
+The same protocol for the momentum-exchange readout (wtp_enable_mex: one k_mex_batch behind the other reductions); with --loads the
+surface loads are on in both variants.  --lib loads another build of libwtpolar.so (such as one compiled with -DWTP_MEX_WINDOW=0,
+which visits every interior column).
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -49,7 +55,7 @@ def bench_batch(nx, ny, b, steps, warmup, masks):
         return time.perf_counter() - t0
 
 
-def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats):
+def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False):
     """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats."""
     out = []
     with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1) as eng:
@@ -57,6 +63,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats):
         eng.init_equilibrium(U0)
         if loads:
             eng.enable_loads(*pkg.polar.quarter_chord(nx, ny))
+        if mex:
+            eng.enable_momentum_exchange(*pkg.polar.quarter_chord(nx, ny))
         eng.step(warmup - warmup % every, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -87,6 +95,30 @@ def loads_cost(a):
                               "us_per_step_loads_median": round(med[True], 3), "us_per_step_loads_range": [round(float(us[True].min()), 3), round(float(us[True].max()), 3)],
                               "loads_us_per_sample": round((med[True] - med[False]) * a.steps / samples, 3),
                               "loads_fraction_of_step": round(med[True] / med[False] - 1.0, 5)}), flush=True)
+
+
+def mex_cost(a):
+    variants = (False, True)
+    for size in a.sizes.split(","):
+        nx, ny = (int(v) for v in size.split("x"))
+        for b in (int(v) for v in a.members.split(",")):
+            masks = _masks(nx, ny, b)
+            t = {v: [] for v in variants}
+            for r in range(a.repeats):                 # in turn, so that a drift of the clocks lands on both
+                for mex in variants:
+                    t[mex] += bench_sampled(nx, ny, b, a.steps, a.warmup, masks, a.sample_every, a.loads, 1, mex=mex)
+            us = {k: np.array(v) / a.steps * 1e6 for k, v in t.items()}
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            samples = a.steps // a.sample_every
+            line = {"tool": "polar_bench --mex", "lib": a.lib or "default", "loads": bool(a.loads), "nx": nx, "ny": ny, "dtype": "float32",
+                    "members": b, "steps": a.steps, "sample_every": a.sample_every, "repeats": a.repeats,
+                    "us_per_step_plain_median": round(med[False], 3),
+                    "us_per_step_plain_range": [round(float(us[False].min()), 3), round(float(us[False].max()), 3)],
+                    "us_per_step_mex_median": round(med[True], 3),
+                    "us_per_step_mex_range": [round(float(us[True].min()), 3), round(float(us[True].max()), 3)],
+                    "mex_us_per_sample": round((med[True] - med[False]) * a.steps / samples, 3),
+                    "mex_fraction_of_step": round(med[True] / med[False] - 1.0, 5)}
+            print(json.dumps(line), flush=True)
 
 
 def bench_sequential(nx, ny, b, steps, warmup, masks):
@@ -120,9 +152,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--no-sequential", action="store_true", help="time the batch only")
     ap.add_argument("--loads", action="store_true", help="the sampled step with and without surface loads")
+    ap.add_argument("--mex", action="store_true", help="the sampled step with and without the momentum-exchange readout")
+    ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=7)
     a = ap.parse_args()
+    if a.lib:
+        pkg.polar.load_polar_library(a.lib)
+    if a.mex:
+        return mex_cost(a)
     if a.loads:
         return loads_cost(a)
     for size in a.sizes.split(","):
