@@ -83,6 +83,22 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
 template <typename T>
 struct Init9 { T v[9]; T u0; };
 
+// The equilibrium populations of a uniform flow (u0, 0) at rho = 1: JS doubles, rounded to the storage type once.  The one
+// place wt_init_equilibrium and wtp_init_equilibrium take them from, so a batch member starts from a handle's bits.
+template <typename T>
+inline Init9<T> equilibrium_init(double u0)
+{
+    const double w0 = 4.0 / 9.0, ws = 1.0 / 9.0, wd = 1.0 / 36.0;
+    Init9<T> iv;
+    for (int k = 0; k < 9; k++) {
+        const double w = (k == 0) ? w0 : (k <= 4 ? ws : wd);
+        const double eu = ex_of(k) * u0, uu = u0 * u0;
+        iv.v[k] = (T)(w * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu));
+    }
+    iv.u0 = (T)u0;
+    return iv;
+}
+
 template <typename T>
 __global__ void k_fill_equilibrium(T *__restrict__ f0, T *__restrict__ f1, T *__restrict__ macro,
                                    Geom g, Init9<T> iv)
@@ -138,6 +154,11 @@ __global__ void k_rows_to_cols(const T *__restrict__ src, T *__restrict__ dst, i
 // --------------------------------------------------------------------------------------
 struct RangePartial { double max_s, cp_min, cp_max; };
 struct ForcePartial { double fx, fy; long long surf, rev; };
+
+// Blocks of 256 threads of a reduction over `sites` lattice sites: one per 256 sites, capped (the partials buffers hold
+// kReduceBlocks entries).  A sum depends on it through the order of its additions, so a handle and a batch both ask here.
+static const int kReduceBlocks = 1024;
+inline int reduce_blocks(long sites) { return sites > 256L * kReduceBlocks ? kReduceBlocks : (int)((sites + 255) / 256); }
 
 __device__ __forceinline__ double wave_max(double v) { for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o)); return v; }
 __device__ __forceinline__ double wave_min(double v) { for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o)); return v; }

@@ -14,10 +14,12 @@
 // Momentum exchange (wtp_enable_mex) is a third reduction, k_mex_batch, launched behind the other two: the force and the moment
 // that the half-way bounce-back links hand to the body, summed from the populations of the lattice the step wrote.  It reads
 // the lattice and the mask and writes buffers of its own.
+//
+// All three end the same way: the last block of a member to finish (member_done) adds the member's partials in index order, so
+// that a sample does not depend on the order in which the blocks ran, and writes one row of a SampleTable.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -25,37 +27,12 @@
 #include <vector>
 
 #include "../../include/wt_polar.h"
+#include "errors.hpp"       // g_err, fail, HIP_TRY, WT_TRY
 #include "kernels.hpp"
 #include "step_fast.hpp"
 
 using namespace wt;
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "%s failed: %s (%s:%d)",   \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                              \
-    } while (0)
-
-#define WT_TRY(expr)                \
-    do {                            \
-        int rc_ = (expr);           \
-        if (rc_ != WT_OK) return rc_; \
-    } while (0)
-
-static const int kReduceBlocks = 1024;     // wt_forces' cap on the reduction's block count
 static const int kLoadsWaves = 16;         // waves (columns) of one k_loads_batch block
 static const int kTicketStride = 32;       // unsigned ints between the members' k_loads_batch / k_mex_batch tickets: one 128-byte line each
 #ifndef WTP_MEX_WINDOW
@@ -69,6 +46,43 @@ struct MexPartial { double fx, fy, mz; long long links; };     // one column's s
 struct MemberStrides { long lat, macro, mask, tiles; };
 
 static long member_stride(size_t bytes, size_t esz) { return (long)(((bytes + 4095) / 4096 * 4096 + 17408) / esz); }
+
+// The samples of one read-out: up to four columns of 8-byte values (double or long long), [cap + 1][B] each, one value per
+// member and row.  Rows [0, cap) are the history, in step order; row cap is the scratch row of the on-demand call.
+struct SampleTable {
+    void *col[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ncols = 0;
+    size_t rows = 0, members = 0;
+
+    size_t bytes() const { return rows * members * 8; }
+    bool allocated() const { return ncols > 0 && col[ncols - 1]; }
+    int alloc(int n, size_t cap, size_t B)       // (columns already held are kept)
+    {
+        ncols = n; rows = cap + 1; members = B;
+        for (int c = 0; c < n; c++) if (!col[c]) HIP_TRY(hipMalloc(&col[c], bytes()));
+        return WT_OK;
+    }
+    // "Never sampled" in every row of the columns of `mask` (bit c: column c): bytes 0xFF, a NaN as a double, -1 as a long long.
+    int fill(unsigned mask, hipStream_t st)
+    {
+        for (int c = 0; c < ncols; c++) if (mask >> c & 1u) HIP_TRY(hipMemsetAsync(col[c], 0xFF, bytes(), st));
+        return WT_OK;
+    }
+    // Column c of row `row` on the device: what a launch writes.
+    template <typename V> V *at(int c, int row) const
+    {
+        static_assert(sizeof(V) == 8, "a sample is 8 bytes");
+        return reinterpret_cast<V *>(col[c]) + (size_t)row * members;
+    }
+    // Rows [first, first + count) of every column whose destination is not null, to the host.
+    int read(int first, int count, void *const *dst) const
+    {
+        const size_t n = (size_t)count * members * 8;
+        for (int c = 0; c < ncols && n; c++) if (dst[c]) HIP_TRY(hipMemcpy(dst[c], at<double>(c, first), n, hipMemcpyDeviceToHost));
+        return WT_OK;
+    }
+    void release() { for (void *&p : col) { if (p) (void)hipFree(p); p = nullptr; } }
+};
 
 struct wtp_batch {
     int nx = 0, ny = 0, dtype = WT_F32, device = 0, members = 0, cap = 0;
@@ -85,9 +99,8 @@ struct wtp_batch {
     std::vector<double> params_host;     // ... as the caller gave them (doubles), to skip unchanged uploads
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
-    double *h_fx = nullptr, *h_fy = nullptr;          // history [cap + 1][B]; row cap = wtp_forces' scratch row
-    long long *h_surf = nullptr, *h_rev = nullptr;
-    std::vector<int64_t> h_step;         // step count of each history row held
+    SampleTable forces;                  // fx, fy (double), surf, rev (long long)
+    std::vector<int64_t> h_step;         // step count of each history row held, in every table
     void *stage = nullptr;               // layout conversion (one member's plane, or one mask)
     size_t stage_bytes = 0;
     int nb = 0;                          // blocks of one member's force reduction
@@ -99,7 +112,7 @@ struct wtp_batch {
     double *l_ref = nullptr;             // [B][2]: xref, yref
     double *l_col = nullptr;             // [B][NX]: the columns' moment partials of the running reduction
     unsigned int *l_tickets = nullptr;   // [B] tickets, kTicketStride apart
-    double *h_mz = nullptr;              // history [cap + 1][B]; row cap = wtp_moment's scratch row
+    SampleTable moment;                  // mz (double)
     double *s_rho = nullptr;             // [B][2][NX]: sums of rho over the samples, upper then lower
     long long *s_cnt = nullptr;          // [B][2][NX]: samples added
     // momentum exchange (wtp_enable_mex); every pointer is null until then
@@ -109,8 +122,7 @@ struct wtp_batch {
     double *x_ref = nullptr;             // [B][2]: xref, yref
     MexPartial *x_col = nullptr;         // [B][NX]: the columns' partials of the running reduction
     unsigned int *x_tickets = nullptr;   // [B] tickets, kTicketStride apart
-    double *h_xfx = nullptr, *h_xfy = nullptr, *h_xmz = nullptr;     // history [cap + 1][B]; row cap = wtp_mex's scratch row
-    long long *h_xlinks = nullptr;
+    SampleTable xforces;                 // fx, fy, mz (double), links (long long)
     bool inited = false;
     long long steps_done = 0;
 };
@@ -136,9 +148,35 @@ __global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T 
                                  tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane);
 }
 
+// "The last block of a member finishes the sum": called by every thread of a block once the block's partials of member m are
+// written.  tickets[m * STRIDE] counts the member's blocks that have got here in this launch (0 between launches), nblocks is
+// how many there are.  Block-uniform; true in exactly one block per member and launch, the one that drew the last ticket, which
+// may then read all the member's partials through a volatile pointer, because
+//  * the first barrier (SYNC) puts the stores of all the block's threads before thread 0's fence.  SYNC = false is for a
+//    block whose only partial thread 0 wrote itself (forces_block): program order does the same;
+//  * thread 0's __threadfence() makes those stores visible device-wide before its atomicAdd counts the block, so the block
+//    that reads nblocks - 1 there does so after the partials of all the others became visible;
+//  * the second barrier hands thread 0's verdict to the block, and the second fence, with the volatile pointer, keeps the
+//    reads that follow from being served by anything fetched before the ticket was drawn.
+// The ticket is left as it is: the thread that writes the member's result zeroes it, for the next launch in the stream.
+template <bool SYNC, int STRIDE>
+__device__ __forceinline__ bool member_done(unsigned int *tickets, long m, unsigned int nblocks)
+{
+    __shared__ int last;
+    if (SYNC) __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(&tickets[m * STRIDE], 1u) == nblocks - 1;
+    }
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    return true;
+}
+
 // wt_forces of every member in one launch: grid (nb, B).  Each block computes k_forces' partial of its block index; the
-// last block of a member to finish (ticket) sums the member's nb partials in block order, in double, as wt_forces does on
-// the host, and writes one history entry.
+// member's last block (member_done) sums its nb partials in block order, in double, as wt_forces does on the host, and
+// writes one row entry.
 template <typename T>
 __global__ __launch_bounds__(256) void k_forces_batch(const T *__restrict__ macro, const uint8_t *__restrict__ mask, Geom g,
                                                       MemberStrides ms, int nb, ForcePartial *__restrict__ part,
@@ -149,14 +187,7 @@ __global__ __launch_bounds__(256) void k_forces_batch(const T *__restrict__ macr
     const long m = blockIdx.y;
     ForcePartial *p = part + m * nb;
     forces_block<T>(macro + m * ms.macro, mask + m * ms.mask, g, 0, g.nxl, (int)blockIdx.x, nb, p + blockIdx.x);
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        __threadfence();                                            // this block's partial is visible device-wide ...
-        last = atomicAdd(&tickets[m], 1u) == (unsigned)(nb - 1);    // ... before it is counted
-    }
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __threadfence();
+    if (!member_done<false, 1>(tickets, m, (unsigned)nb) || threadIdx.x != 0) return;      // (adjacent tickets)
     const volatile ForcePartial *vp = p;
     double sx = 0.0, sy = 0.0;
     long long ns = 0, nr = 0;
@@ -170,8 +201,7 @@ __global__ __launch_bounds__(256) void k_forces_batch(const T *__restrict__ macr
 // contiguous run of the mask and of rho (y fastest), read in chunks of 64 rows, one row per lane; rows past NY never count.
 //  * Moment: forces_block's faces (fluid cell, solid 4-neighbour inside the grid in direction d, p = (double)rho / 3, force
 //    p * d at the face centre r = (i + 0.5 + 0.5 dx, j + 0.5 + 0.5 dy)), each adding (r.x - xr) F.y - (r.y - yr) F.x.  The
-//    column's terms are added by wave_sum; the last block of a member to finish (ticket, as k_forces_batch) adds the
-//    columns' partials in column order, so that a sample does not depend on the order in which the blocks ran.
+//    column's terms are added by wave_sum; the member's last block (member_done) adds the columns' partials in column order.
 //  * Surface: the highest and lowest solid row of the column from the chunks' ballots; with `accumulate`, rho of the fluid
 //    cell above the one and below the other is added to the member's sums.  One lane owns an entry and launches are
 //    stream-ordered, so the sums are plain read-modify-writes in sample order.
@@ -228,16 +258,8 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
         }
     }
     constexpr int NT = kLoadsWaves * 64;
-    __shared__ int last;
     __shared__ double sh[NT];
-    __syncthreads();                                                // the block's partials are written ...
-    if (threadIdx.x == 0) {
-        __threadfence();                                            // ... and visible device-wide before the block is counted
-        last = atomicAdd(&tickets[m * kTicketStride], 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
     const volatile double *vc = col + m * nx;
     double s = 0.0;
     for (int c0 = 0; c0 < nx; c0 += NT) {                           // NT partials at a time through LDS; thread 0 adds them in column order
@@ -267,8 +289,8 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
 // A member's window win[m] = (first column, columns) holds every interior column next to one of its solid columns: no other
 // column can own a link.  A column is one contiguous run of the mask and of each population plane (y fastest), read in chunks of
 // 64 rows, one row per lane: the mask bytes of columns i-1, i, i+1 at rows j-1, j, j+1, then a population only on the lanes that
-// own a link in its direction.  The column's terms are added by wave_sum; the last block of a member to finish (ticket, as
-// k_loads_batch) adds the columns' partials in column order, so that a sample is the same bits from run to run.
+// own a link in its direction.  The column's terms are added by wave_sum; the member's last block (member_done) adds the
+// columns' partials in column order, each of the four sums on a wave of its own.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
@@ -318,17 +340,9 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restr
         }
     }
     constexpr int NT = kLoadsWaves * 64;
-    __shared__ int last;
     __shared__ double sh[3][NT];
     __shared__ long long shn[NT];
-    __syncthreads();                                                // the block's partials are written ...
-    if (threadIdx.x == 0) {
-        __threadfence();                                            // ... and visible device-wide before the block is counted
-        last = atomicAdd(&tickets[m * kTicketStride], 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
     const volatile MexPartial *vc = col + m * nx;
     const int w = (int)(threadIdx.x >> 6);
     double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
@@ -382,10 +396,10 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets,
-                    b->h_fx, b->h_fy, b->h_surf, b->h_rev, b->stage, b->l_ref, b->l_col, b->l_tickets, b->h_mz, b->s_rho, b->s_cnt,
-                    b->x_win, b->x_ref, b->x_col, b->x_tickets, b->h_xfx, b->h_xfy, b->h_xmz, b->h_xlinks};
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets, b->stage,
+                    b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets};
     for (void *p : bufs) if (p) (void)hipFree(p);
+    for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
     if (b->st) (void)hipStreamDestroy(b->st);
     delete b;
     return WT_OK;
@@ -421,8 +435,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     b->ms.macro = member_stride((size_t)3 * g.nxl * g.pitch * b->esz, b->esz);
     b->ms.mask = member_stride((size_t)(g.nxl + 2) * g.pitch, 1);
     b->ms.tiles = member_stride((size_t)g.nxl * b->tiles_per_col, 1);
-    const long total = (long)nx * ny;
-    b->nb = (int)std::min<long>((total + 255) / 256, kReduceBlocks);
+    b->nb = reduce_blocks((long)nx * ny);
     b->mask_set.assign((size_t)members, 0);
     b->surf_rows.assign((size_t)members * 2 * nx, -1);
     b->mex_win.assign((size_t)members * 2, 0);
@@ -438,7 +451,6 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     const size_t B = (size_t)members;
     const size_t lat_bytes = B * b->ms.lat * b->esz, macro_bytes = B * b->ms.macro * b->esz;
     const size_t mask_bytes = B * b->ms.mask, tile_bytes = B * b->ms.tiles;
-    const size_t rows = (size_t)history_cap + 1;
     CREATE_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
     CREATE_TRY(hipMalloc(&b->f[0], lat_bytes));
     CREATE_TRY(hipMalloc(&b->f[1], lat_bytes));
@@ -448,10 +460,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     CREATE_TRY(hipMalloc(&b->params, B * 2 * b->esz));
     CREATE_TRY(hipMalloc((void **)&b->partials, B * b->nb * sizeof(ForcePartial)));
     CREATE_TRY(hipMalloc((void **)&b->tickets, B * sizeof(unsigned int)));
-    CREATE_TRY(hipMalloc((void **)&b->h_fx, rows * B * sizeof(double)));
-    CREATE_TRY(hipMalloc((void **)&b->h_fy, rows * B * sizeof(double)));
-    CREATE_TRY(hipMalloc((void **)&b->h_surf, rows * B * sizeof(long long)));
-    CREATE_TRY(hipMalloc((void **)&b->h_rev, rows * B * sizeof(long long)));
+    if (int rc = b->forces.alloc(4, (size_t)history_cap, B)) return cleanup(rc);
     CREATE_TRY(hipMemsetAsync(b->f[0], 0, lat_bytes, b->st));
     CREATE_TRY(hipMemsetAsync(b->f[1], 0, lat_bytes, b->st));
     CREATE_TRY(hipMemsetAsync(b->macro, 0, macro_bytes, b->st));
@@ -562,15 +571,7 @@ template <typename T>
 static int init_impl(wtp_batch *b, const double *u0)
 {
     for (int m = 0; m < b->members; m++) {
-        // wt_init_equilibrium (html:474-490): JS doubles, rounded to the storage type
-        const double w0 = 4.0 / 9.0, ws = 1.0 / 9.0, wd = 1.0 / 36.0;
-        Init9<T> iv;
-        for (int k = 0; k < 9; k++) {
-            const double w = (k == 0) ? w0 : (k <= 4 ? ws : wd);
-            const double eu = ex_of(k) * u0[m], uu = u0[m] * u0[m];
-            iv.v[k] = (T)(w * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu));
-        }
-        iv.u0 = (T)u0[m];
+        const Init9<T> iv = equilibrium_init<T>(u0[m]);          // wt_init_equilibrium's values
         hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m),
                            b->g, iv);
         HIP_TRY(hipGetLastError());
@@ -622,10 +623,10 @@ static int upload_params(wtp_batch *b, const double *tau, const double *u0)
 template <typename T>
 static int launch_forces(wtp_batch *b, int row)
 {
-    const size_t off = (size_t)row * b->members;
+    const SampleTable &t = b->forces;
     hipLaunchKernelGGL(k_forces_batch<T>, dim3((unsigned)b->nb, (unsigned)b->members), dim3(256), 0, b->st,
                        (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, b->nb, b->partials, b->tickets,
-                       b->h_fx + off, b->h_fy + off, b->h_surf + off, b->h_rev + off);
+                       t.at<double>(0, row), t.at<double>(1, row), t.at<long long>(2, row), t.at<long long>(3, row));
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -636,7 +637,7 @@ static int launch_loads(wtp_batch *b, int row, bool accumulate)
 {
     hipLaunchKernelGGL(k_loads_batch<T>, dim3((unsigned)((b->nx + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members),
                        dim3(kLoadsWaves * 64), 0, b->st, (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, (const double *)b->l_ref, b->l_col, b->l_tickets,
-                       b->h_mz + (size_t)row * b->members, b->s_rho, b->s_cnt, accumulate ? 1 : 0);
+                       b->moment.at<double>(0, row), b->s_rho, b->s_cnt, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -647,11 +648,22 @@ static int launch_mex(wtp_batch *b, int row)
 {
     int widest = 1;                              // (a batch without a body still runs one block per member, which writes zeros)
     for (int m = 0; m < b->members; m++) widest = std::max(widest, (int)b->mex_win[2 * (size_t)m + 1]);
-    const size_t off = (size_t)row * b->members;
+    const SampleTable &t = b->xforces;
     hipLaunchKernelGGL(k_mex_batch<T>, dim3((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), dim3(kLoadsWaves * 64), 0,
                        b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms, (const double *)b->x_ref,
-                       (const int32_t *)b->x_win, b->x_col, b->x_tickets, b->h_xfx + off, b->h_xfy + off, b->h_xmz + off, b->h_xlinks + off);
+                       (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row), t.at<double>(1, row), t.at<double>(2, row),
+                       t.at<long long>(3, row));
     HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+// One sample of the state the last step left: every read-out that is enabled, into row `row` of its table.
+template <typename T>
+static int sample_into(wtp_batch *b, int row)
+{
+    WT_TRY(launch_forces<T>(b, row));
+    if (b->loads) WT_TRY(launch_loads<T>(b, row, true));
+    if (b->mex) WT_TRY(launch_mex<T>(b, row));
     return WT_OK;
 }
 
@@ -667,19 +679,14 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
         const int rev = (int)(b->steps_done & 1);
-        if (emit)
-            hipLaunchKernelGGL((k_step_batch<T, true, WT_LOADMODE>), grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), b->mask, b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
-        else
-            hipLaunchKernelGGL((k_step_batch<T, false, WT_LOADMODE>), grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), b->mask, b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
+        const auto k_step = emit ? k_step_batch<T, true, WT_LOADMODE> : k_step_batch<T, false, WT_LOADMODE>;
+        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                           b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
         HIP_TRY(hipGetLastError());
         b->cur = 1 - b->cur;
         b->steps_done = n;
         if (sample) {
-            WT_TRY(launch_forces<T>(b, (int)b->h_step.size()));
-            if (b->loads) WT_TRY(launch_loads<T>(b, (int)b->h_step.size(), true));
-            if (b->mex) WT_TRY(launch_mex<T>(b, (int)b->h_step.size()));
+            WT_TRY(sample_into<T>(b, (int)b->h_step.size()));
             b->h_step.push_back(n);
         }
     }
@@ -715,22 +722,29 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
 // ------------------------------------------------------------------------------------------
 // read-backs
 // ------------------------------------------------------------------------------------------
+static int check_rows(const wtp_batch *b, int first, int count)
+{
+    const int held = (int)b->h_step.size();
+    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    return WT_OK;
+}
+
+// Rows [first, first + count) of a table, once everything enqueued has run, into the destinations that are not null (one per
+// column).  Row b->cap with count 1 is what an on-demand call reads back after its launch into the scratch row.
+static int read_rows(wtp_batch *b, const SampleTable &t, int first, int count, void *const (&dst)[4])
+{
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    return t.read(first, count, dst);
+}
+
 extern "C" int wtp_history(wtp_batch *b, int first, int count, int64_t *step, double *fx, double *fy, int64_t *surf, int64_t *rev)
 {
     WT_TRY(check_batch(b));
-    const int held = (int)b->h_step.size();
-    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
+    WT_TRY(check_rows(b, first, count));
+    WT_TRY(read_rows(b, b->forces, first, count, {fx, fy, surf, rev}));
     if (step) for (int r = 0; r < count; r++) step[r] = b->h_step[(size_t)(first + r)];
-    if (n) {
-        if (fx) HIP_TRY(hipMemcpy(fx, b->h_fx + off, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (fy) HIP_TRY(hipMemcpy(fy, b->h_fy + off, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (surf) HIP_TRY(hipMemcpy(surf, b->h_surf + off, n * sizeof(long long), hipMemcpyDeviceToHost));
-        if (rev) HIP_TRY(hipMemcpy(rev, b->h_rev + off, n * sizeof(long long), hipMemcpyDeviceToHost));
-    }
-    return held;
+    return (int)b->h_step.size();
 }
 
 extern "C" int wtp_clear_history(wtp_batch *b)
@@ -749,38 +763,41 @@ extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, i
     WT_TRY(check_ready(b));
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? launch_forces<float>(b, b->cap) : launch_forces<double>(b, b->cap));     // the scratch row
-    HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t off = (size_t)b->cap * b->members, B = (size_t)b->members;
-    HIP_TRY(hipMemcpy(fx, b->h_fx + off, B * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(fy, b->h_fy + off, B * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(surf, b->h_surf + off, B * sizeof(long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rev, b->h_rev + off, B * sizeof(long long), hipMemcpyDeviceToHost));
-    return WT_OK;
+    return read_rows(b, b->forces, b->cap, 1, {fx, fy, surf, rev});
 }
 
 // ------------------------------------------------------------------------------------------
 // surface loads
 // ------------------------------------------------------------------------------------------
+// The reference points of a moment read-out, (xref[m], yref[m]) of every member: checked, packed [B][2] and uploaded to *dev
+// (allocated on the first call) once the samples already enqueued, which read the previous points, have run.
+static int set_ref_points(wtp_batch *b, const double *xref, const double *yref, double **dev)
+{
+    const size_t B = (size_t)b->members;
+    for (size_t m = 0; m < B; m++)
+        if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", (int)m);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!*dev) HIP_TRY(hipMalloc((void **)dev, B * 2 * sizeof(double)));
+    std::vector<double> ref(B * 2);
+    for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
+    HIP_TRY(hipStreamSynchronize(b->st));
+    HIP_TRY(hipMemcpy(*dev, ref.data(), ref.size() * sizeof(double), hipMemcpyHostToDevice));
+    return WT_OK;
+}
+
 extern "C" int wtp_enable_loads(wtp_batch *b, const double *xref, const double *yref)
 {
     WT_TRY(check_batch(b));
     if (!xref || !yref) return fail(WT_ERR_ARG, "xref or yref is null");
-    for (int m = 0; m < b->members; m++)
-        if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", m);
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->members, rows = (size_t)b->cap + 1, cols = B * b->nx;
-    if (!b->l_ref) HIP_TRY(hipMalloc((void **)&b->l_ref, B * 2 * sizeof(double)));
+    WT_TRY(set_ref_points(b, xref, yref, &b->l_ref));
+    const size_t B = (size_t)b->members, cols = B * b->nx;
     if (!b->l_col) HIP_TRY(hipMalloc((void **)&b->l_col, cols * sizeof(double)));
     if (!b->l_tickets) HIP_TRY(hipMalloc((void **)&b->l_tickets, B * kTicketStride * sizeof(unsigned int)));
-    if (!b->h_mz) HIP_TRY(hipMalloc((void **)&b->h_mz, rows * B * sizeof(double)));
     if (!b->s_rho) HIP_TRY(hipMalloc((void **)&b->s_rho, 2 * cols * sizeof(double)));
     if (!b->s_cnt) HIP_TRY(hipMalloc((void **)&b->s_cnt, 2 * cols * sizeof(long long)));
-    std::vector<double> ref(B * 2);
-    for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
-    HIP_TRY(hipStreamSynchronize(b->st));        // samples already enqueued read the previous points
-    HIP_TRY(hipMemcpy(b->l_ref, ref.data(), ref.size() * sizeof(double), hipMemcpyHostToDevice));
+    WT_TRY(b->moment.alloc(1, (size_t)b->cap, B));
     HIP_TRY(hipMemsetAsync(b->l_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
-    HIP_TRY(hipMemsetAsync(b->h_mz, 0xFF, rows * B * sizeof(double), b->st));     // rows sampled before this call hold no Mz about these points: NaN
+    WT_TRY(b->moment.fill(1u, b->st));           // rows sampled before this call hold no Mz about these points
     b->loads = true;
     return clear_surface_sums(b, 0, b->members);
 }
@@ -795,14 +812,9 @@ extern "C" int wtp_history_moment(wtp_batch *b, int first, int count, double *mz
 {
     WT_TRY(check_batch(b));
     if (!mz) return fail(WT_ERR_ARG, "mz is null");
-    const int held = (int)b->h_step.size();
-    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    WT_TRY(check_rows(b, first, count));
     WT_TRY(check_loads(b));
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
-    if (n) HIP_TRY(hipMemcpy(mz, b->h_mz + off, n * sizeof(double), hipMemcpyDeviceToHost));
-    return WT_OK;
+    return read_rows(b, b->moment, first, count, {mz});
 }
 
 extern "C" int wtp_moment(wtp_batch *b, double *mz)
@@ -813,9 +825,7 @@ extern "C" int wtp_moment(wtp_batch *b, double *mz)
     WT_TRY(check_ready(b));
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? launch_loads<float>(b, b->cap, false) : launch_loads<double>(b, b->cap, false));     // the scratch row
-    HIP_TRY(hipStreamSynchronize(b->st));
-    HIP_TRY(hipMemcpy(mz, b->h_mz + (size_t)b->cap * b->members, (size_t)b->members * sizeof(double), hipMemcpyDeviceToHost));
-    return WT_OK;
+    return read_rows(b, b->moment, b->cap, 1, {mz});
 }
 
 extern "C" int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *rho_lower, int64_t *n_upper, int64_t *n_lower,
@@ -844,31 +854,17 @@ extern "C" int wtp_enable_mex(wtp_batch *b, const double *xref, const double *yr
 {
     WT_TRY(check_batch(b));
     if (!xref || !yref) return fail(WT_ERR_ARG, "xref or yref is null");
-    for (int m = 0; m < b->members; m++)
-        if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", m);
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->members, rows = (size_t)b->cap + 1;
-    const bool first = !b->h_xlinks;
+    const bool first = !b->xforces.allocated();
+    WT_TRY(set_ref_points(b, xref, yref, &b->x_ref));
+    const size_t B = (size_t)b->members;
     if (!b->x_win) HIP_TRY(hipMalloc((void **)&b->x_win, B * 2 * sizeof(int32_t)));
-    if (!b->x_ref) HIP_TRY(hipMalloc((void **)&b->x_ref, B * 2 * sizeof(double)));
     if (!b->x_col) HIP_TRY(hipMalloc((void **)&b->x_col, B * b->nx * sizeof(MexPartial)));
     if (!b->x_tickets) HIP_TRY(hipMalloc((void **)&b->x_tickets, B * kTicketStride * sizeof(unsigned int)));
-    if (!b->h_xfx) HIP_TRY(hipMalloc((void **)&b->h_xfx, rows * B * sizeof(double)));
-    if (!b->h_xfy) HIP_TRY(hipMalloc((void **)&b->h_xfy, rows * B * sizeof(double)));
-    if (!b->h_xmz) HIP_TRY(hipMalloc((void **)&b->h_xmz, rows * B * sizeof(double)));
-    if (!b->h_xlinks) HIP_TRY(hipMalloc((void **)&b->h_xlinks, rows * B * sizeof(long long)));
-    std::vector<double> ref(B * 2);
-    for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
-    HIP_TRY(hipStreamSynchronize(b->st));        // samples already enqueued read the previous points
-    HIP_TRY(hipMemcpy(b->x_ref, ref.data(), ref.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->x_win, b->mex_win.data(), B * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+    WT_TRY(b->xforces.alloc(4, (size_t)b->cap, B));
+    HIP_TRY(hipMemcpy(b->x_win, b->mex_win.data(), B * 2 * sizeof(int32_t), hipMemcpyHostToDevice));     // (the stream is idle)
     HIP_TRY(hipMemsetAsync(b->x_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
-    HIP_TRY(hipMemsetAsync(b->h_xmz, 0xFF, rows * B * sizeof(double), b->st));    // rows sampled before this call hold no Mz about these points: NaN
-    if (first) {                                 // rows sampled before the first call hold nothing at all: NaN forces, -1 links
-        HIP_TRY(hipMemsetAsync(b->h_xfx, 0xFF, rows * B * sizeof(double), b->st));
-        HIP_TRY(hipMemsetAsync(b->h_xfy, 0xFF, rows * B * sizeof(double), b->st));
-        HIP_TRY(hipMemsetAsync(b->h_xlinks, 0xFF, rows * B * sizeof(long long), b->st));
-    }
+    // rows sampled before this call hold no Mz about these points; those before the first call hold nothing at all
+    WT_TRY(b->xforces.fill(first ? 0xFu : 1u << 2, b->st));
     b->mex = true;
     return WT_OK;
 }
@@ -882,19 +878,9 @@ static int check_mex(const wtp_batch *b)
 extern "C" int wtp_history_mex(wtp_batch *b, int first, int count, double *fx, double *fy, double *mz, int64_t *links)
 {
     WT_TRY(check_batch(b));
-    const int held = (int)b->h_step.size();
-    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    WT_TRY(check_rows(b, first, count));
     WT_TRY(check_mex(b));
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t off = (size_t)first * b->members, n = (size_t)count * b->members;
-    if (n) {
-        if (fx) HIP_TRY(hipMemcpy(fx, b->h_xfx + off, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (fy) HIP_TRY(hipMemcpy(fy, b->h_xfy + off, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (mz) HIP_TRY(hipMemcpy(mz, b->h_xmz + off, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (links) HIP_TRY(hipMemcpy(links, b->h_xlinks + off, n * sizeof(long long), hipMemcpyDeviceToHost));
-    }
-    return WT_OK;
+    return read_rows(b, b->xforces, first, count, {fx, fy, mz, links});
 }
 
 extern "C" int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t *links)
@@ -905,13 +891,7 @@ extern "C" int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t
     WT_TRY(check_ready(b));
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? launch_mex<float>(b, b->cap) : launch_mex<double>(b, b->cap));     // the scratch row
-    HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t off = (size_t)b->cap * b->members, B = (size_t)b->members;
-    HIP_TRY(hipMemcpy(fx, b->h_xfx + off, B * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(fy, b->h_xfy + off, B * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mz, b->h_xmz + off, B * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(links, b->h_xlinks + off, B * sizeof(long long), hipMemcpyDeviceToHost));
-    return WT_OK;
+    return read_rows(b, b->xforces, b->cap, 1, {fx, fy, mz, links});
 }
 
 extern "C" int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_events)

@@ -7,7 +7,6 @@
 #include "rccl_bind.hpp"      // <rccl/rccl.h> for the types; the entry points are bound at run time to the one RCCL of the process
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +16,7 @@
 #include <vector>
 
 #include "../../include/windtunnel.h"
+#include "errors.hpp"       // g_err, fail, HIP_TRY, WT_TRY
 #include "kernels.hpp"
 #include "step_fast.hpp"
 #include "step_march.hpp"
@@ -48,37 +48,12 @@ static inline const char *exp_env(const char *name)
 // ------------------------------------------------------------------------------------------
 // errors
 // ------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "%s failed: %s (%s:%d)",   \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                              \
-    } while (0)
-
 #define NCCL_TRY(expr)                                                                                  \
     do {                                                                                                \
         ncclResult_t r_ = (expr);                                                                       \
         if (r_ != ncclSuccess)                                                                          \
             return fail(WT_ERR_RCCL, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__,  \
                         __LINE__);                                                                      \
-    } while (0)
-
-#define WT_TRY(expr)                \
-    do {                            \
-        int rc_ = (expr);           \
-        if (rc_ != WT_OK) return rc_; \
     } while (0)
 
 // ------------------------------------------------------------------------------------------
@@ -229,7 +204,6 @@ struct wt_handle {
 };
 static const int XT_RING = 32;
 
-static const int kReduceBlocks = 1024;
 static const long long TUNE_LIVE_PASSES = 16;
 
 template <typename T> static T *fptr(wt_handle *h, int which) { return reinterpret_cast<T *>(h->f[which]); }
@@ -1121,15 +1095,7 @@ extern "C" int wt_set_mask(wt_handle *h, const uint8_t *mask)
 template <typename T>
 static int init_impl(wt_handle *h, double u0)
 {
-    // html:474-490: JS doubles, rounded to the storage type
-    const double w0 = 4.0 / 9.0, ws = 1.0 / 9.0, wd = 1.0 / 36.0;
-    Init9<T> iv;
-    for (int k = 0; k < 9; k++) {
-        const double w = (k == 0) ? w0 : (k <= 4 ? ws : wd);
-        const double eu = ex_of(k) * u0, uu = u0 * u0;
-        iv.v[k] = (T)(w * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu));
-    }
-    iv.u0 = (T)u0;
+    const Init9<T> iv = equilibrium_init<T>(u0);
     hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, h->s_compute, fptr<T>(h, 0), fptr<T>(h, 1),
                        reinterpret_cast<T *>(h->macro), h->g, iv);
     HIP_TRY(hipGetLastError());
@@ -2493,9 +2459,7 @@ extern "C" int wt_reduce_ranges(wt_handle *h, double u0, double *max_s, double *
     if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
     if (!(u0 != 0.0)) return fail(WT_ERR_ARG, "u0 must be non-zero");
     HIP_TRY(hipSetDevice(h->device));
-    const long total = (long)h->width * h->g.ny;
-    int nb = (int)((total + 255) / 256);
-    if (nb > kReduceBlocks) nb = kReduceBlocks;
+    const int nb = reduce_blocks((long)h->width * h->g.ny);
     RangePartial *dp = reinterpret_cast<RangePartial *>(h->partials);
     if (h->dtype == WT_F32)
         hipLaunchKernelGGL(k_ranges<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g,
@@ -2524,9 +2488,7 @@ extern "C" int wt_forces(wt_handle *h, double *fx, double *fy, int64_t *surf, in
     if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
     if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
     HIP_TRY(hipSetDevice(h->device));
-    const long total = (long)h->width * h->g.ny;
-    int nb = (int)((total + 255) / 256);
-    if (nb > kReduceBlocks) nb = kReduceBlocks;
+    const int nb = reduce_blocks((long)h->width * h->g.ny);
     ForcePartial *dp = reinterpret_cast<ForcePartial *>(h->partials);
     if (h->dtype == WT_F32)
         hipLaunchKernelGGL(k_forces<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g,
@@ -2552,9 +2514,7 @@ extern "C" int wt_clamp_events(wt_handle *h, int64_t *rho_events, int64_t *u_eve
     if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
     if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
     HIP_TRY(hipSetDevice(h->device));
-    const long total = (long)h->width * h->g.ny;
-    int nb = (int)((total + 255) / 256);
-    if (nb > kReduceBlocks) nb = kReduceBlocks;
+    const int nb = reduce_blocks((long)h->width * h->g.ny);
     ClampPartial *dp = reinterpret_cast<ClampPartial *>(h->partials);
     if (h->dtype == WT_F32)
         hipLaunchKernelGGL(k_clamp_events<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g, h->gl, h->width, dp);

@@ -337,7 +337,14 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
     cl, cd, sep = raw_coefficients(fx, fy, surf, rev, u0, nx)
     finite = bool(np.all(np.isfinite(np.asarray(fx, np.float64))) and np.all(np.isfinite(np.asarray(fy, np.float64))))
     n = int(cl.size)
-    nan = float("nan")
+
+    def stats(v, scale=float):
+        """(mean, std) of the samples v through `scale`; (nan, nan) when no sample has a body surface."""
+        return (float(scale(v.mean())), float(abs(scale(v.std())))) if n else (float("nan"), float("nan"))
+
+    def cm(mz_value):
+        return moment_coefficient(mz_value, u0, nx)
+
     hist = {"step": np.asarray(step, np.int64), "fx": np.asarray(fx, np.float64), "fy": np.asarray(fy, np.float64),
             "surf": np.asarray(surf, np.int64), "rev": np.asarray(rev, np.int64)}
     sep_mean = float(sep.mean()) if n else 0.0
@@ -345,8 +352,8 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
     if mz is not None:
         hist["mz"] = np.asarray(mz, np.float64)
         kept = hist["mz"][hist["surf"] != 0]
-        cm_mean, cm_std = (float(moment_coefficient(kept.mean(), u0, nx)), float(abs(moment_coefficient(kept.std(), u0, nx)))) if n else (nan, nan)
-    cd_mean = float(cd.mean()) if n else nan
+        cm_mean, cm_std = stats(kept, cm)
+    (cl_mean, cl_std), (cd_mean, cd_std) = stats(cl), stats(cd)
     total = {}
     given = [v is not None for v in (fx_mex, fy_mex, mz_mex)]
     if any(given):
@@ -360,13 +367,10 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
         q = 0.5 * u0 * u0 * chord_cells(nx)
         finite = finite and bool(np.all(np.isfinite(hist["fx_mex"])) and np.all(np.isfinite(hist["fy_mex"])))
         for name, v in (("cl_total", hist["fy_mex"][keep] / q), ("cd_total", hist["fx_mex"][keep] / q)):
-            total[name + "_mean"], total[name + "_std"] = (float(v.mean()), float(v.std())) if n else (nan, nan)
-        kept = hist["mz_mex"][keep]                  # (as cm_mean: the coefficient of the mean moment)
-        total["cm_total_mean"], total["cm_total_std"] = (float(moment_coefficient(kept.mean(), u0, nx)),
-                                                         float(abs(moment_coefficient(kept.std(), u0, nx)))) if n else (nan, nan)
+            total[name + "_mean"], total[name + "_std"] = stats(v)
+        total["cm_total_mean"], total["cm_total_std"] = stats(hist["mz_mex"][keep], cm)      # (as cm_mean: the coefficient of the mean moment)
         total["cd_friction_mean"] = total["cd_total_mean"] - cd_mean
-    return PolarPoint(alpha=float(alpha), cl_mean=float(cl.mean()) if n else nan, cl_std=float(cl.std()) if n else nan,
-                      cd_mean=cd_mean, cd_std=float(cd.std()) if n else nan, sep_frac=sep_mean,
+    return PolarPoint(alpha=float(alpha), cl_mean=cl_mean, cl_std=cl_std, cd_mean=cd_mean, cd_std=cd_std, sep_frac=sep_mean,
                       separation=stall_label(sep_mean), samples=n, finite=finite,
                       clamp_events=(int(clamp_events[0]), int(clamp_events[1])), history=hist, cm_mean=cm_mean, cm_std=cm_std,
                       surface=surface, **total)

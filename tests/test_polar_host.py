@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import _polar_isa
 
 WT_ERR_ARG = -1
 
@@ -132,11 +133,7 @@ def test_importing_the_package_does_not_load_the_polar_library():
 
 @pytest.fixture(scope="module")
 def polar_isa():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not present")
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import check_store_hazard as chk
-    return chk, chk.build(os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "polar.hip"))
+    return _polar_isa.polar_isa()
 
 
 def test_batched_kernels_have_no_scratch_and_no_store_hazard(polar_isa):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import _polar_isa
 from _mex_reference import E, count_links, link_masks, mex_reference
 
 WT_ERR_ARG = -1
@@ -249,11 +250,7 @@ def test_run_polar_and_engine_expose_the_switch(pkg):
 # ---- the kernel's code object ------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def polar_isa():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not present")
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import check_store_hazard as chk
-    return chk, chk.build(os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "polar.hip"))
+    return _polar_isa.polar_isa()
 
 
 def test_mex_kernel_has_no_scratch(polar_isa):
