@@ -12,6 +12,7 @@
 #include <cstring>
 #include <limits>
 #include <new>
+#include <type_traits>
 #include <algorithm>
 #include <vector>
 
@@ -103,7 +104,7 @@ struct wt_handle {
     wt_handle *peer_l = nullptr, *peer_r = nullptr;   // TR_LOCAL
     // several steps per pass (step_march.hpp, step_march3.hpp, step_chain.hpp)
     bool fuse = false;
-    int fuse_sites = 0;                  // option: sites per lane of the marching kernel (0 = automatic; 2 or 4)
+    int fuse_sites = 0;                  // option, kept for callers of round 2: 0 = automatic, or the one value the element type allows (march_sites)
     int fuse_depth = 0;                  // option: steps per pass (0 = automatic; 2 or 3)
     int march_depth = 0;                 // steps per pass the plan's tables are built for (2, 3 or 4; step_march3.hpp)
     int pass_cap = 0;                    // longest pass actually taken on those tables (0 = march_depth): fp64 with fuse_depth = 2
@@ -113,7 +114,7 @@ struct wt_handle {
     long long passes = 0;
     long long single_steps = 0;          // k_step launches of whole steps (option "single_steps"): what a fused plan falls back to
     long long march_table_bytes = 0;     // wcls + hlines + seams + seam_plain (part of device_bytes)
-    int march_s = 0;                     // sites per lane in use (4: fp32 256-row windows; 2: fp64, or fp32 on narrow lattices)
+    int march_s = 0;                     // sites per lane the plan's tables are built for (march_sites: 2 = fp32, 128-row windows; 1 = fp64, 64-row windows)
     bool fuse_force = false;             // fuse_steps = 2: also when the lattice is too small for it to pay
     int fuse_chunk = 0;                  // cost limit of a unit (columns); 0 = whole resident rounds of units (build_march_plan)
     bool fuse_ready = false;
@@ -207,6 +208,12 @@ static const int XT_RING = 32;
 static const long long TUNE_LIVE_PASSES = 16;
 
 template <typename T> static T *fptr(wt_handle *h, int which) { return reinterpret_cast<T *>(h->f[which]); }
+// the handle's element type as the type of f's argument: by_dtype(h, [&](auto t) { using T = decltype(t); ... })
+template <typename F> static auto by_dtype(const wt_handle *h, F &&f) { return h->dtype == WT_F32 ? f(float{}) : f(double{}); }
+// Sites per lane of the marching kernels (their template parameter S): a lane holds one 8-byte vector per direction, so the element type
+// decides — fp32: 2 sites, 128-row windows; fp64: 1 site, 64-row windows.
+template <typename T> constexpr int march_sites = 8 / (int)sizeof(T);
+static inline int march_sites_of(const wt_handle *h) { return by_dtype(h, [](auto t) { return march_sites<decltype(t)>; }); }
 
 static int ensure_stage(wt_handle *h, size_t bytes)
 {
@@ -495,7 +502,7 @@ static bool fuse_eligible_s(const wt_handle *h, int sites)
     const unsigned long long plane = std::max<unsigned long long>((unsigned long long)h->g.plane, plane_elems_of(nxl_max, h->g.pitch, (size_t)eb));
     return h->g.ny % sites == 0 && std::min(h->g.nxl, nxl_min) >= 8 && 9ULL * plane * eb < (1ULL << 32) - (1ULL << 20);
 }
-static bool fuse_eligible(const wt_handle *h) { return fuse_eligible_s(h, h->dtype == WT_F32 ? 2 : 1); }
+static bool fuse_eligible(const wt_handle *h) { return fuse_eligible_s(h, march_sites_of(h)); }
 static inline int plan_depth(const wt_handle *h) { return h->pass_cap > 0 && h->pass_cap < h->march_depth ? h->pass_cap : h->march_depth; }
 static inline int eff_depth(const wt_handle *h)
 {
@@ -732,7 +739,7 @@ static int rebuild_fuse_plan(wt_handle *h)
     h->pass_cap = 0;
     if (!h->fuse || !fuse_eligible(h) || !h->mask_set) return WT_OK;
     const long slots = h->wave_slots;
-    const int s3 = h->dtype == WT_F32 ? 2 : 1;
+    const int s3 = march_sites_of(h);
     const bool two_on_three = h->dtype != WT_F32 && h->fuse_depth == 2;  // fp64: two-step passes on the three-step tables
     // Every slab of a tunnel must take the SAME sequence of passes and refresh steps (the exchange is collective: over RCCL each rank
     // decides on its own), so the automatic choices below look at the NARROWEST slab of the split — an edge slab, W + halo columns —
@@ -1092,12 +1099,13 @@ extern "C" int wt_set_mask(wt_handle *h, const uint8_t *mask)
 // ------------------------------------------------------------------------------------------
 // init
 // ------------------------------------------------------------------------------------------
-template <typename T>
 static int init_impl(wt_handle *h, double u0)
 {
-    const Init9<T> iv = equilibrium_init<T>(u0);
-    hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, h->s_compute, fptr<T>(h, 0), fptr<T>(h, 1),
-                       reinterpret_cast<T *>(h->macro), h->g, iv);
+    by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, h->s_compute, fptr<T>(h, 0), fptr<T>(h, 1),
+                           reinterpret_cast<T *>(h->macro), h->g, equilibrium_init<T>(u0));
+    });
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -1106,7 +1114,7 @@ extern "C" int wt_init_equilibrium(wt_handle *h, double u0)
 {
     WT_TRY(check_handle(h));
     HIP_TRY(hipSetDevice(h->device));
-    WT_TRY(h->dtype == WT_F32 ? init_impl<float>(h, u0) : init_impl<double>(h, u0));
+    WT_TRY(init_impl(h, u0));
     h->cur = 0;
     h->inited = true;
     if (h->stuck_host) { HIP_TRY(hipStreamSynchronize(h->s_compute)); *h->stuck_host = 0; }
@@ -1123,18 +1131,14 @@ extern "C" int wt_init_equilibrium(wt_handle *h, double u0)
 // ------------------------------------------------------------------------------------------
 // stepping
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int launch_step(wt_handle *h, int i_begin, int i_end, double tau, double u0, bool emit, hipStream_t st)
-{
-    if (i_end <= i_begin) return WT_OK;
-    return step_columns<T>(fptr<T>(h, h->cur), fptr<T>(h, 1 - h->cur), reinterpret_cast<T *>(h->macro), h->mask,
-                           h->tiles, h->tiles_per_col, h->g, i_begin, i_end, (T)tau, (T)u0, emit, (int)(h->steps_done & 1), st);
-}
-
 static int launch_step_any(wt_handle *h, int i_begin, int i_end, double tau, double u0, bool emit, hipStream_t st)
 {
-    int rc = h->dtype == WT_F32 ? launch_step<float>(h, i_begin, i_end, tau, u0, emit, st)
-                                : launch_step<double>(h, i_begin, i_end, tau, u0, emit, st);
+    if (i_end <= i_begin) return WT_OK;
+    const int rc = by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        return step_columns<T>(fptr<T>(h, h->cur), fptr<T>(h, 1 - h->cur), reinterpret_cast<T *>(h->macro), h->mask,
+                               h->tiles, h->tiles_per_col, h->g, i_begin, i_end, (T)tau, (T)u0, emit, (int)(h->steps_done & 1), st);
+    });
     if (rc != WT_OK) return fail(rc, "step kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return WT_OK;
 }
@@ -1305,10 +1309,17 @@ static int step_compute(wt_handle *h, double tau, double u0, bool emit, bool ref
     return WT_OK;
 }
 
-static int step_once(wt_handle *h, double tau, double u0, bool emit)
+// asked before anything a slab handle does with its neighbours in a stepping call
+static int require_transport(const wt_handle *h)
 {
     if (h->nranks > 1 && h->transport == TR_NONE)
         return fail(WT_ERR_STATE, "slab handle has no transport (wt_comm_init_rank / wt_link_local)");
+    return WT_OK;
+}
+
+static int step_once(wt_handle *h, double tau, double u0, bool emit)
+{
+    WT_TRY(require_transport(h));
     const bool refresh = needs_halo(h);
     if (refresh) WT_TRY(halo_begin(h));
     return step_compute(h, tau, u0, emit, refresh);
@@ -1416,7 +1427,7 @@ static void march3_params(wt_handle *h, double tau, double u0, MarchParams<T> &p
 }
 
 // level-0 .. level-(D-1) values of the rows around the window seams for the column blocks xb0 .. xb0 + nbx - 1 (HL_COLS columns each; nbx < 0: all)
-template <typename T, int S, int FD>
+template <typename T, int FD>
 static void launch_halo_lines(wt_handle *h, const MarchParams<T> &p, int use_seams, int xb0, int nbx, hipStream_t st)
 {
     const Geom &g = h->g;
@@ -1427,47 +1438,49 @@ static void launch_halo_lines(wt_handle *h, const MarchParams<T> &p, int use_sea
     if (xb0 + nbx > all) nbx = all - xb0;
     if (nbx <= 0) return;
     const unsigned nblk = (unsigned)(h->n_win - 1) * (unsigned)nbx;
-    if (h->march_depth == 4)        // the plan's tables are those of the four-step pass, whatever this pass advances
-        hipLaunchKernelGGL((k_halo4<T, S, FD>), dim3(nblk), dim3(256), 0, st, p.fs, (const T *)p.seams, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
-                           (const uint8_t *)h->seam_plain, reinterpret_cast<T *>(h->hlines), g, h->n_win, use_seams, p.fdv, p.tau, p.U0, xb0, nbx);
-    else
-        hipLaunchKernelGGL((k_halo3<T, S, FD>), dim3(nblk), dim3(256), 0, st, p.fs, (const T *)p.seams, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
-                           (const uint8_t *)h->seam_plain, reinterpret_cast<T *>(h->hlines), g, h->n_win, use_seams, p.fdv, p.tau, p.U0, xb0, nbx);
+    constexpr int S = march_sites<T>;
+    const auto k_halo = h->march_depth == 4 ? k_halo4<T, S, FD> : k_halo3<T, S, FD>;      // the plan's tables are those of the four-step pass, whatever this pass advances
+    hipLaunchKernelGGL(k_halo, dim3(nblk), dim3(256), 0, st, p.fs, (const T *)p.seams, (const uint8_t *)h->mask, (const uint8_t *)h->bcode,
+                       (const uint8_t *)h->seam_plain, reinterpret_cast<T *>(h->hlines), g, h->n_win, use_seams, p.fdv, p.tau, p.U0, xb0, nbx);
 }
 
-// the marching kernel over p.units (depth = steps this pass advances, on the tables of h->march_depth); `ovl`: the plan's windows overlap
-// (p.win_stride: the instantiations without halo lines and seam rows, fp32 only — build_fuse_plan plans no other)
-template <typename T, int S, int FD, int DEPTH>
+// a run-time flag as a compile-time one: f(std::true_type) where the flag is set and the variant exists (CAN), f(std::false_type) otherwise
+template <bool CAN, typename F>
+static void with_flag(bool on, F &&f)
+{
+    if constexpr (CAN) { if (on) { f(std::true_type{}); return; } }
+    f(std::false_type{});
+}
+
+// The marching kernel over p.units (depth = steps this pass advances, on the tables of h->march_depth).  FD arrives as the arithmetic of the
+// division by tau (by_march_variant) and is completed here, once, with the bits that are not arithmetic: MARCH_FD_OVL where the plan's windows
+// overlap (p.win_stride: the instantiations without halo lines and seam rows, fp32 only — build_fuse_plan plans no other) and, in the
+// four-step fp32 kernel, MARCH_FD_TWOOP where the device has proved the division in two operations for this tau (fastdiv_for; three otherwise).
+template <typename T, int FDK, int DEPTH>
 static void launch_march3_k(const MarchParams<T> &p, bool emit, hipStream_t st)
 {
     const dim3 grid((unsigned)((p.nunits + 3) / 4));
-    if (emit) hipLaunchKernelGGL((k_march3<T, S, DEPTH, true, FD>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_march3<T, S, DEPTH, false, FD>), grid, dim3(256), 0, st, p);
+    if (emit) hipLaunchKernelGGL((k_march3<T, march_sites<T>, DEPTH, true, FDK>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_march3<T, march_sites<T>, DEPTH, false, FDK>), grid, dim3(256), 0, st, p);
 }
-template <typename T, int S, int FD>
+template <typename T, int FD>
 static int launch_march3(const MarchParams<T> &p, int depth, bool emit, bool two_op, hipStream_t st)
 {
     if (p.nunits <= 0) return WT_OK;
+    constexpr bool F32 = sizeof(T) == 4;
+    constexpr bool CAN_OVL = F32 && (FD & MARCH_FD_CONTRACTED) == 0, CAN_TWOOP = F32 && FD == 1;
+    // (fp32 with the IEEE division by tau: no four-step kernel is built — 40-80 bytes of scratch per lane; set_tau_cap keeps such a call at three steps per pass)
+    constexpr bool CAN_FOUR = !(F32 && FD == 0);
     const bool ovl = p.win_stride > 0;
-    constexpr bool CAN_OVL = sizeof(T) == 4 && (FD & MARCH_FD_CONTRACTED) == 0;
     if (ovl && !CAN_OVL) return fail(WT_ERR_STATE, "internal: overlapping windows planned for a kernel that has none");
-    if (depth == 4) {
-        // (fp32 with the IEEE division by tau: not built — 40-80 bytes of scratch per lane; set_tau_cap keeps such a call at three steps per pass)
-        if constexpr (sizeof(T) == 4 && FD == 0) return fail(WT_ERR_STATE, "internal: four-step pass with the IEEE division");
-        else if constexpr (sizeof(T) == 4 && FD == 1) {
-            // the division by tau in two operations where the device has proved it for this tau (fastdiv_for), in three otherwise
-            if (ovl) { if (two_op) launch_march3_k<T, S, FD | MARCH_FD_TWOOP | MARCH_FD_OVL, 4>(p, emit, st); else launch_march3_k<T, S, FD | MARCH_FD_OVL, 4>(p, emit, st); }
-            else if (two_op) launch_march3_k<T, S, FD | MARCH_FD_TWOOP, 4>(p, emit, st);
-            else launch_march3_k<T, S, FD, 4>(p, emit, st);
-        }
-        else launch_march3_k<T, S, FD, 4>(p, emit, st);
-    } else if (depth == 3) {
-        if constexpr (CAN_OVL) { if (ovl) { launch_march3_k<T, S, FD | MARCH_FD_OVL, 3>(p, emit, st); return WT_OK; } }
-        launch_march3_k<T, S, FD, 3>(p, emit, st);
-    } else {
-        if constexpr (CAN_OVL) { if (ovl) { launch_march3_k<T, S, FD | MARCH_FD_OVL, 2>(p, emit, st); return WT_OK; } }
-        launch_march3_k<T, S, FD, 2>(p, emit, st);
-    }
+    if (depth == 4 && !CAN_FOUR) return fail(WT_ERR_STATE, "internal: four-step pass with the IEEE division");
+    with_flag<CAN_OVL>(ovl, [&](auto O) {
+        constexpr int FDO = FD | (decltype(O)::value ? MARCH_FD_OVL : 0);
+        if (depth == 3) launch_march3_k<T, FDO, 3>(p, emit, st);
+        else if (depth != 4) launch_march3_k<T, FDO, 2>(p, emit, st);
+        else if constexpr (CAN_FOUR)
+            with_flag<CAN_TWOOP>(two_op, [&](auto W) { launch_march3_k<T, FDO | (decltype(W)::value ? MARCH_FD_TWOOP : 0), 4>(p, emit, st); });
+    });
     return WT_OK;
 }
 
@@ -1491,31 +1504,45 @@ static void end_pass(wt_handle *h, int k, int gv_before)
     if (h->nranks > 1) h->ghost_valid = ghosts_after_pass(h, gv_before, k);
 }
 
-// `depth` steps in one pass (step_march3.hpp): the plan's own depth, or a shorter pass on the same tables (what a step count leaves over).
-// A = f[cur] (time t), B = f[1-cur] (receives time t + depth).
-template <typename T, int S, int FD>
-static int step_triple_fused_t(wt_handle *h, double tau, double u0, bool emit, int depth, bool two_op = false)
+// What every marching pass enqueues on the compute stream: the parameter block, the halo lines of every column (use_seams < 0: none — `mine`
+// builds those the pass reads), whatever is the caller's own between the lines and the kernel (`mine(p)`: its unit list, launch order, clocks),
+// the marching kernel, the launch check.
+template <typename T, int FD, typename Mine>
+static int march_pass(wt_handle *h, double tau, double u0, int use_seams, int depth, bool emit, bool two_op, Mine &&mine)
 {
     MarchParams<T> p;
     march3_params<T>(h, tau, u0, p);
-    if (h->clk_on) p.clk = h->d_clk + h->clk_off;
-#ifdef WT_UNIT_CLOCKS         // diagnostic build (tools/unit_clocks.py): every pass records its units
-    else { WT_TRY(ensure_clocks(h)); p.clk = h->d_clk; }
-#endif
-    hipStream_t st = h->s_compute;
-    launch_halo_lines<T, S, FD>(h, p, h->seams_valid ? 1 : 0, 0, -1, st);
-    if (h->nranks > 1 && h->trim && !h->clk_on && h->march_depth >= 3) {
-        // ghost columns that will still be exact after this pass: the others are not marched (trim_plan_for; not on two-step plans)
-        const int v_full = h->halo - (h->march_depth - 1), v_after = ghosts_after_pass(h, h->ghost_valid, depth);
-        if (v_after < v_full) {
-            const UnitList *tl = nullptr;
-            WT_TRY(trim_plan_for(h, v_after, &tl));
-            if (tl->n > 0) { p.units = tl->d; p.nunits = tl->n; h->trimmed_passes += 1; }
-        }
-    }
-    if (h->clk_on) HIP_TRY(hipEventRecord(h->ev_t0, st));       // tuning passes: the marching kernel alone is timed
-    WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
+    if (use_seams >= 0) launch_halo_lines<T, FD>(h, p, use_seams, 0, -1, h->s_compute);
+    WT_TRY(mine(p));
+    WT_TRY((launch_march3<T, FD>(p, depth, emit, two_op, h->s_compute)));
     HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+// `depth` steps in one pass (step_march3.hpp): the plan's own depth, or a shorter pass on the same tables (what a step count leaves over).
+// A = f[cur] (time t), B = f[1-cur] (receives time t + depth).
+template <typename T, int FD>
+static int step_triple_fused_t(wt_handle *h, double tau, double u0, bool emit, int depth, bool two_op)
+{
+    hipStream_t st = h->s_compute;
+    const auto mine = [&](MarchParams<T> &p) -> int {
+        if (h->clk_on) p.clk = h->d_clk + h->clk_off;
+#ifdef WT_UNIT_CLOCKS         // diagnostic build (tools/unit_clocks.py): every pass records its units
+        else { WT_TRY(ensure_clocks(h)); p.clk = h->d_clk; }
+#endif
+        if (h->nranks > 1 && h->trim && !h->clk_on && h->march_depth >= 3) {
+            // ghost columns that will still be exact after this pass: the others are not marched (trim_plan_for; not on two-step plans)
+            const int v_full = h->halo - (h->march_depth - 1), v_after = ghosts_after_pass(h, h->ghost_valid, depth);
+            if (v_after < v_full) {
+                const UnitList *tl = nullptr;
+                WT_TRY(trim_plan_for(h, v_after, &tl));
+                if (tl->n > 0) { p.units = tl->d; p.nunits = tl->n; h->trimmed_passes += 1; }
+            }
+        }
+        if (h->clk_on) HIP_TRY(hipEventRecord(h->ev_t0, st));       // tuning passes: the marching kernel alone is timed
+        return WT_OK;
+    };
+    WT_TRY((march_pass<T, FD>(h, tau, u0, h->seams_valid ? 1 : 0, depth, emit, two_op, mine)));
     if (h->clk_on) HIP_TRY(hipEventRecord(h->ev_t1, st));
     end_pass(h, depth, h->ghost_valid);
     return WT_OK;
@@ -1572,44 +1599,40 @@ static int renew_plan_for(wt_handle *h, int depth, wt_handle::RenewPlan **out)
 }
 
 // The interior half: to be enqueued right after halo_begin(h) (the exchange is then on its way on the comm stream).
-template <typename T, int S, int FD>
+template <typename T, int FD>
 static int renew_interior_t(wt_handle *h, double tau, double u0, bool emit, int depth, bool two_op, bool seams_were_valid)
 {
     wt_handle::RenewPlan *rp = nullptr;
     WT_TRY(renew_plan_for(h, depth, &rp));
-    MarchParams<T> p;
-    march3_params<T>(h, tau, u0, p);
-    hipStream_t st = h->s_compute;
-    if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 2), st));
-    launch_halo_lines<T, S, FD>(h, p, seams_were_valid ? 1 : 0, 0, -1, st);      // (the lines of the ghost columns come out of stale records: rebuilt below, unused here)
-    p.units = rp->units[0].d; p.nunits = rp->units[0].n;
-    WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
-    HIP_TRY(hipGetLastError());
-    if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 3), st));
+    if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 2), h->s_compute));
+    // (the lines of the ghost columns come out of stale records: rebuilt by renew_strips_t, unused here)
+    const auto mine = [&](MarchParams<T> &p) -> int { p.units = rp->units[0].d; p.nunits = rp->units[0].n; return WT_OK; };
+    WT_TRY((march_pass<T, FD>(h, tau, u0, seams_were_valid ? 1 : 0, depth, emit, two_op, mine)));
+    if (h->xt_on) HIP_TRY(hipEventRecord(xt_event(h, 3), h->s_compute));
     return WT_OK;
 }
 // The edge strips: after the compute stream has waited for the exchange.
-template <typename T, int S, int FD>
+template <typename T, int FD>
 static int renew_strips_t(wt_handle *h, double tau, double u0, bool emit, int depth, bool two_op)
 {
     wt_handle::RenewPlan *rp = nullptr;
     WT_TRY(renew_plan_for(h, depth, &rp));
-    MarchParams<T> p;
-    march3_params<T>(h, tau, u0, p);
     hipStream_t st = h->s_compute;
     HIP_TRY(hipStreamWaitEvent(st, h->ev_halo, 0));
     if (h->xt_on) { HIP_TRY(hipEventRecord(xt_event(h, 4), st)); h->xt_n += 1; }
-    // halo lines of the strips' columns from the lattice (gather path): every line a strip unit reads lies within march_depth columns of its range
-    const int D = h->march_depth;
-    for (int side = 0; side < 2; side++) {
-        if (!(side ? h->gr : h->gl) || rp->strip_hi[side] <= rp->strip_lo[side]) continue;
-        const int lo = std::max(0, rp->strip_lo[side] - D), hi = std::min(h->g.nxl, rp->strip_hi[side] + D);
-        launch_halo_lines<T, S, FD>(h, p, 0, lo / HL_COLS, (hi - 1) / HL_COLS - lo / HL_COLS + 1, st);
-    }
-    p.units = rp->units[1].d; p.nunits = rp->units[1].n;
-    p.rev = 0;
-    WT_TRY((launch_march3<T, S, FD>(p, depth, emit, two_op, st)));
-    HIP_TRY(hipGetLastError());
+    const auto mine = [&](MarchParams<T> &p) -> int {
+        // halo lines of the strips' columns from the lattice (gather path): every line a strip unit reads lies within march_depth columns of its range
+        const int D = h->march_depth;
+        for (int side = 0; side < 2; side++) {
+            if (!(side ? h->gr : h->gl) || rp->strip_hi[side] <= rp->strip_lo[side]) continue;
+            const int lo = std::max(0, rp->strip_lo[side] - D), hi = std::min(h->g.nxl, rp->strip_hi[side] + D);
+            launch_halo_lines<T, FD>(h, p, 0, lo / HL_COLS, (hi - 1) / HL_COLS - lo / HL_COLS + 1, st);
+        }
+        p.units = rp->units[1].d; p.nunits = rp->units[1].n;
+        p.rev = 0;
+        return WT_OK;
+    };
+    WT_TRY((march_pass<T, FD>(h, tau, u0, -1, depth, emit, two_op, mine)));
     end_pass(h, depth, h->halo);                 // (on tiling windows, interior and strips together wrote the seam rows of every column still exact)
     h->fused_renewals += 1;
     return WT_OK;
@@ -1636,13 +1659,24 @@ static inline int fuse_stride(const wt_handle *h, int left)
     return fuse_pick(eff_depth(h), fuse_avail(h, left));
 }
 
-static int step_fused(wt_handle *h, double tau, double u0, bool emit, int k)
+// Which marching kernels a pass runs, decided once: f(T{}, FD, two_op) with the element type, the arithmetic of the division by tau as a
+// compile-time constant (step_march.hpp MARCH_FD_*: fp64 the guarded four-operation division, switched by fdv.on64; option "fast_math" the
+// contracted collision; fp32 the three-operation division where the device has proved it for this tau — fastdiv_for —, the IEEE one where
+// not) and whether the four-step fp32 kernel may divide in two operations (launch_march3).
+template <typename F>
+static int by_march_variant(wt_handle *h, double tau, F &&f)
 {
-    if (h->dtype != WT_F32) return step_triple_fused_t<double, 1, 1>(h, tau, u0, emit, k);      // (FD 1: the guarded four-operation division, switched by fdv.on64)
-    if (h->fast_math) return step_triple_fused_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit, k);
+    using std::integral_constant;
+    if (h->dtype != WT_F32) return f(double{}, integral_constant<int, 1>{}, false);
+    if (h->fast_math) return f(float{}, integral_constant<int, MARCH_FD_CONTRACTED>{}, false);
     bool fd = false, fd2 = false;
     WT_TRY(fastdiv_for(h, (float)tau, &fd, &fd2));
-    return fd ? step_triple_fused_t<float, 2, 1>(h, tau, u0, emit, k, fd2) : step_triple_fused_t<float, 2, 0>(h, tau, u0, emit, k);
+    return fd ? f(float{}, integral_constant<int, 1>{}, fd2) : f(float{}, integral_constant<int, 0>{}, false);
+}
+
+static int step_fused(wt_handle *h, double tau, double u0, bool emit, int k)
+{
+    return by_march_variant(h, tau, [&](auto t, auto fd, bool two_op) { return step_triple_fused_t<decltype(t), decltype(fd)::value>(h, tau, u0, emit, k, two_op); });
 }
 
 // refresh = 2: is the next thing a slab does a fused renewal — a pass of k > 0 steps with the exchange beside its interior columns?
@@ -1659,19 +1693,11 @@ static inline int renew_stride(const wt_handle *h, int left)
 // the two halves of such a pass (see renew_interior_t): between them every slab's exchange is in flight
 static int renew_interior(wt_handle *h, double tau, double u0, bool emit, int k, bool seams_were_valid)
 {
-    if (h->dtype != WT_F32) return renew_interior_t<double, 1, 1>(h, tau, u0, emit, k, false, seams_were_valid);
-    if (h->fast_math) return renew_interior_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit, k, false, seams_were_valid);
-    bool fd = false, fd2 = false;
-    WT_TRY(fastdiv_for(h, (float)tau, &fd, &fd2));
-    return fd ? renew_interior_t<float, 2, 1>(h, tau, u0, emit, k, fd2, seams_were_valid) : renew_interior_t<float, 2, 0>(h, tau, u0, emit, k, false, seams_were_valid);
+    return by_march_variant(h, tau, [&](auto t, auto fd, bool two_op) { return renew_interior_t<decltype(t), decltype(fd)::value>(h, tau, u0, emit, k, two_op, seams_were_valid); });
 }
 static int renew_strips(wt_handle *h, double tau, double u0, bool emit, int k)
 {
-    if (h->dtype != WT_F32) return renew_strips_t<double, 1, 1>(h, tau, u0, emit, k, false);
-    if (h->fast_math) return renew_strips_t<float, 2, MARCH_FD_CONTRACTED>(h, tau, u0, emit, k, false);
-    bool fd = false, fd2 = false;
-    WT_TRY(fastdiv_for(h, (float)tau, &fd, &fd2));
-    return fd ? renew_strips_t<float, 2, 1>(h, tau, u0, emit, k, fd2) : renew_strips_t<float, 2, 0>(h, tau, u0, emit, k, false);
+    return by_march_variant(h, tau, [&](auto t, auto fd, bool two_op) { return renew_strips_t<decltype(t), decltype(fd)::value>(h, tau, u0, emit, k, two_op); });
 }
 
 // Measure, then cut again.  The cut by time rests on a model of what a column costs (cut_units), and a launch takes as long as its
@@ -1683,7 +1709,6 @@ static int renew_strips(wt_handle *h, double tau, double u0, bool emit, int k)
 // the plan with the shortest measured makespan is kept (the modelled one if nothing beat it).  The populations are not touched: the
 // passes write f[1 - cur] and the scratch tables, the handle's counters are put back, and only the seam buffer is marked stale.
 // The cut changes no result — every plan computes the same bits (tests/test_gpu_fused.py runs tuned and untuned plans against the oracle).
-static int step_fused(wt_handle *h, double tau, double u0, bool emit, int k);
 static int tune_fuse_plan(wt_handle *h, double tau, double u0)
 {
     h->plan_tuned = true;
@@ -1965,11 +1990,11 @@ static int run_steps(wt_handle *h, int nsteps, double tau, double u0)
     int s = 0;
     while (s < nsteps) {
         if (boundary_exchange_due(h, nsteps - s)) {
-            if (h->transport == TR_NONE) return fail(WT_ERR_STATE, "slab handle has no transport (wt_comm_init_rank / wt_link_local)");
+            WT_TRY(require_transport(h));
             WT_TRY(exchange_at_boundary(h));
         }
         if (const int kr = renew_stride(h, nsteps - s)) {         // refresh = 2: exchange || interior columns, then the edge strips
-            if (h->transport == TR_NONE) return fail(WT_ERR_STATE, "slab handle has no transport (wt_comm_init_rank / wt_link_local)");
+            WT_TRY(require_transport(h));
             const bool sv = h->seams_valid;
             WT_TRY(halo_begin(h));
             WT_TRY(renew_interior(h, tau, u0, s + kr == nsteps, kr, sv));
@@ -2205,6 +2230,35 @@ static int group_prepare(wt_handle **hs, int n, int nsteps, double tau, double u
     return WT_OK;
 }
 
+// The two joins around every exchange of a locally linked group (a slab's ghost copies read its peers' lattices, on its own comm stream).
+// Before: every slab records its finished state, then every comm stream waits for its neighbours' — all records first, so that no slab
+// waits for an event of an earlier exchange.
+static int group_publish_state(wt_handle **hs, int n)
+{
+    for (int r = 0; r < n; r++) {
+        HIP_TRY(hipSetDevice(hs[r]->device));
+        HIP_TRY(hipEventRecord(hs[r]->ev_state, hs[r]->s_compute));
+    }
+    for (int r = 0; r < n; r++) {
+        HIP_TRY(hipSetDevice(hs[r]->device));
+        if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_l->ev_state, 0));
+        if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_r->ev_state, 0));
+    }
+    return WT_OK;
+}
+// After: the peers' copies read the lattice a slab held when the exchange was enqueued.  The step or pass that runs beside the exchange writes
+// the OTHER lattice; the one after it overwrites the one the copies read.  So behind that step or pass (or, for an exchange that stands alone
+// at a pass boundary, right behind it) every compute stream waits for its neighbours' ev_halo: their copies of ITS columns are done.
+static int group_wait_halos(wt_handle **hs, int n)
+{
+    for (int r = 0; r < n; r++) {
+        HIP_TRY(hipSetDevice(hs[r]->device));
+        if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_l->ev_halo, 0));
+        if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_r->ev_halo, 0));
+    }
+    return WT_OK;
+}
+
 extern "C" int wt_step_group(wt_handle **hs, int n, int nsteps, double tau, double u0)
 {
     if (!hs || n < 1) return fail(WT_ERR_ARG, "no handles");
@@ -2221,24 +2275,12 @@ extern "C" int wt_step_group(wt_handle **hs, int n, int nsteps, double tau, doub
         bool xdue = false;
         for (int r = 0; r < n && multi; r++) xdue = xdue || boundary_exchange_due(hs[r], nsteps - s);
         if (xdue) {
-            for (int r = 0; r < n; r++) {                      // every slab's comm stream must see its neighbours' finished lattices
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                HIP_TRY(hipEventRecord(hs[r]->ev_state, hs[r]->s_compute));
-            }
-            for (int r = 0; r < n; r++) {
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_l->ev_state, 0));
-                if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_r->ev_state, 0));
-            }
+            WT_TRY(group_publish_state(hs, n));
             for (int r = 0; r < n; r++) {
                 HIP_TRY(hipSetDevice(hs[r]->device));
                 WT_TRY(exchange_at_boundary(hs[r]));
             }
-            for (int r = 0; r < n; r++) {                      // a peer's pass after next overwrites the lattice my copies read: it waits for them
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_l->ev_halo, 0));
-                if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_r->ev_halo, 0));
-            }
+            WT_TRY(group_wait_halos(hs, n));
         }
         // refresh = 2 (agreed by the group): the renewal inside a fused pass — every exchange is enqueued, then every slab marches its interior
         // columns beside it, then the edge strips once its own ghosts have landed
@@ -2247,25 +2289,13 @@ extern "C" int wt_step_group(wt_handle **hs, int n, int nsteps, double tau, doub
             for (int r = 0; r < n && multi; r++) kr = std::min(kr, renew_stride(hs[r], nsteps - s));
             if (multi && kr > 0 && kr < (1 << 30)) {
                 std::vector<char> sv((size_t)n);
-                for (int r = 0; r < n; r++) {
-                    HIP_TRY(hipSetDevice(hs[r]->device));
-                    HIP_TRY(hipEventRecord(hs[r]->ev_state, hs[r]->s_compute));
-                    sv[(size_t)r] = hs[r]->seams_valid ? 1 : 0;
-                }
-                for (int r = 0; r < n; r++) {
-                    HIP_TRY(hipSetDevice(hs[r]->device));
-                    if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_l->ev_state, 0));
-                    if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_r->ev_state, 0));
-                }
+                for (int r = 0; r < n; r++) sv[(size_t)r] = hs[r]->seams_valid ? 1 : 0;      // (halo_begin clears it)
+                WT_TRY(group_publish_state(hs, n));
                 for (int r = 0; r < n; r++) { HIP_TRY(hipSetDevice(hs[r]->device)); WT_TRY(halo_begin(hs[r])); }
                 const bool emit_r = s + kr == nsteps;
                 for (int r = 0; r < n; r++) { HIP_TRY(hipSetDevice(hs[r]->device)); WT_TRY(renew_interior(hs[r], tau, u0, emit_r, kr, sv[(size_t)r] != 0)); }
                 for (int r = 0; r < n; r++) { HIP_TRY(hipSetDevice(hs[r]->device)); WT_TRY(renew_strips(hs[r], tau, u0, emit_r, kr)); }
-                for (int r = 0; r < n; r++) {                  // a peer's NEXT pass overwrites the lattice my copies read: it waits for them
-                    HIP_TRY(hipSetDevice(hs[r]->device));
-                    if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_l->ev_halo, 0));
-                    if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_r->ev_halo, 0));
-                }
+                WT_TRY(group_wait_halos(hs, n));
                 s += kr;
                 continue;
             }
@@ -2293,18 +2323,8 @@ extern "C" int wt_step_group(wt_handle **hs, int n, int nsteps, double tau, doub
         bool refresh = false;                             // as soon as ANY slab has no exact ghost column left, all of them refresh
         for (int r = 0; r < n && multi; r++) refresh = refresh || hs[r]->ghost_valid <= 0;
         if (refresh) {
-            // every slab's comm stream must see its neighbours' finished lattices ...
-            for (int r = 0; r < n; r++) {
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                HIP_TRY(hipEventRecord(hs[r]->ev_state, hs[r]->s_compute));
-            }
-            for (int r = 0; r < n; r++) {
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_l->ev_state, 0));
-                if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_comm, hs[r]->peer_r->ev_state, 0));
-            }
-            // ... and ALL refreshes are enqueued before any slab flips its lattice index
-            for (int r = 0; r < n; r++) {
+            WT_TRY(group_publish_state(hs, n));
+            for (int r = 0; r < n; r++) {                     // ALL refreshes are enqueued before any slab flips its lattice index
                 HIP_TRY(hipSetDevice(hs[r]->device));
                 WT_TRY(halo_begin(hs[r]));
             }
@@ -2313,15 +2333,7 @@ extern "C" int wt_step_group(wt_handle **hs, int n, int nsteps, double tau, doub
             HIP_TRY(hipSetDevice(hs[r]->device));
             WT_TRY(step_compute(hs[r], tau, u0, emit, refresh));
         }
-        if (refresh) {
-            // the peers' NEXT step overwrites the lattice my copies just read: their compute
-            // streams wait for my halo copies
-            for (int r = 0; r < n; r++) {
-                HIP_TRY(hipSetDevice(hs[r]->device));
-                if (hs[r]->peer_l) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_l->ev_halo, 0));
-                if (hs[r]->peer_r) HIP_TRY(hipStreamWaitEvent(hs[r]->s_compute, hs[r]->peer_r->ev_halo, 0));
-            }
-        }
+        if (refresh) WT_TRY(group_wait_halos(hs, n));
         s += 1;
     }
     if (nsteps > 0) for (int r = 0; r < n; r++) hs[r]->macro_stale = false;
@@ -2385,7 +2397,7 @@ extern "C" int wt_read_f(wt_handle *h, void *f_out)
     if (!f_out) return fail(WT_ERR_ARG, "f_out is null");
     if (!h->inited) return fail(WT_ERR_STATE, "no state to read");
     HIP_TRY(hipSetDevice(h->device));
-    return h->dtype == WT_F32 ? read_f_impl<float>(h, f_out) : read_f_impl<double>(h, f_out);
+    return by_dtype(h, [&](auto t) { return read_f_impl<decltype(t)>(h, f_out); });
 }
 
 template <typename T>
@@ -2412,10 +2424,10 @@ extern "C" int wt_write_f(wt_handle *h, const void *f_in)
     if (!f_in) return fail(WT_ERR_ARG, "f_in is null");
     HIP_TRY(hipSetDevice(h->device));
     if (!h->inited) {   // make pads / ghosts finite
-        WT_TRY(h->dtype == WT_F32 ? init_impl<float>(h, 0.0) : init_impl<double>(h, 0.0));
+        WT_TRY(init_impl(h, 0.0));
         h->cur = 0;
     }
-    WT_TRY(h->dtype == WT_F32 ? write_f_impl<float>(h, f_in) : write_f_impl<double>(h, f_in));
+    WT_TRY(by_dtype(h, [&](auto t) { return write_f_impl<decltype(t)>(h, f_in); }));
     if (h->stuck_host) { HIP_TRY(hipStreamSynchronize(h->s_compute)); *h->stuck_host = 0; }       // the state is replaced, as by wt_init_equilibrium
     h->inited = true;
     h->seams_valid = false;
@@ -2431,6 +2443,15 @@ extern "C" int wt_write_f(wt_handle *h, const void *f_in)
 // ------------------------------------------------------------------------------------------
 // macro read-back, reductions, field
 // ------------------------------------------------------------------------------------------
+// What every read-out of the macro planes asks of the handle's state (with_mask: its kernel reads the mask too).  Called where each entry
+// point has always asked: behind its argument checks that come first, in front of those that come after.
+static int require_macro(const wt_handle *h, bool with_mask)
+{
+    if (!h->inited || (with_mask && !h->mask_set)) return fail(WT_ERR_STATE, with_mask ? "state or mask missing" : "no state to read");
+    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
+    return WT_OK;
+}
+
 template <typename T>
 static int read_macro_impl(wt_handle *h, void *rho, void *ux, void *uy)
 {
@@ -2445,89 +2466,82 @@ static int read_macro_impl(wt_handle *h, void *rho, void *ux, void *uy)
 extern "C" int wt_read_macro(wt_handle *h, void *rho, void *ux, void *uy)
 {
     WT_TRY(check_handle(h));
-    if (!h->inited) return fail(WT_ERR_STATE, "no state to read");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
+    WT_TRY(require_macro(h, false));
     HIP_TRY(hipSetDevice(h->device));
-    return h->dtype == WT_F32 ? read_macro_impl<float>(h, rho, ux, uy) : read_macro_impl<double>(h, rho, ux, uy);
+    return by_dtype(h, [&](auto t) { return read_macro_impl<decltype(t)>(h, rho, ux, uy); });
+}
+
+// A reduction over the owned sites: `launch(T{}, nb, partials)` enqueues the kernel that leaves one P per block, `fold(partials, nb)` takes
+// them on the host — in block order: a sum depends on it (kernels.hpp reduce_blocks) — and writes the caller's results.
+template <typename P, typename Launch, typename Fold>
+static int reduce_macro(wt_handle *h, Launch &&launch, Fold &&fold)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    const int nb = reduce_blocks((long)h->width * h->g.ny);
+    P *dp = reinterpret_cast<P *>(h->partials), *hp = reinterpret_cast<P *>(h->partials_host);
+    by_dtype(h, [&](auto t) { launch(t, nb, dp); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hp, dp, nb * sizeof(P), hipMemcpyDeviceToHost, h->s_compute));
+    HIP_TRY(hipStreamSynchronize(h->s_compute));
+    fold(hp, nb);
+    return check_stuck(h);
 }
 
 extern "C" int wt_reduce_ranges(wt_handle *h, double u0, double *max_s, double *cp_min, double *cp_max)
 {
     WT_TRY(check_handle(h));
     if (!max_s || !cp_min || !cp_max) return fail(WT_ERR_ARG, "null output");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
+    WT_TRY(require_macro(h, true));
     if (!(u0 != 0.0)) return fail(WT_ERR_ARG, "u0 must be non-zero");
-    HIP_TRY(hipSetDevice(h->device));
-    const int nb = reduce_blocks((long)h->width * h->g.ny);
-    RangePartial *dp = reinterpret_cast<RangePartial *>(h->partials);
-    if (h->dtype == WT_F32)
-        hipLaunchKernelGGL(k_ranges<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g,
-                           h->gl, h->width, u0, dp);
-    else
-        hipLaunchKernelGGL(k_ranges<double>, dim3(nb), dim3(256), 0, h->s_compute, (const double *)h->macro, h->mask,
-                           h->g, h->gl, h->width, u0, dp);
-    HIP_TRY(hipGetLastError());
-    RangePartial *hp = reinterpret_cast<RangePartial *>(h->partials_host);
-    HIP_TRY(hipMemcpyAsync(hp, dp, nb * sizeof(RangePartial), hipMemcpyDeviceToHost, h->s_compute));
-    HIP_TRY(hipStreamSynchronize(h->s_compute));
-    double mx = 0.0, cmin = std::numeric_limits<double>::infinity(), cmax = -cmin;
-    for (int b = 0; b < nb; b++) {
-        if (hp[b].max_s > mx) mx = hp[b].max_s;
-        if (hp[b].cp_min < cmin) cmin = hp[b].cp_min;
-        if (hp[b].cp_max > cmax) cmax = hp[b].cp_max;
-    }
-    *max_s = mx; *cp_min = cmin; *cp_max = cmax;
-    return check_stuck(h);
+    return reduce_macro<RangePartial>(h,
+        [&](auto t, int nb, RangePartial *dp) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_ranges<T>, dim3(nb), dim3(256), 0, h->s_compute, (const T *)h->macro, h->mask, h->g, h->gl, h->width, u0, dp);
+        },
+        [&](const RangePartial *hp, int nb) {
+            double mx = 0.0, cmin = std::numeric_limits<double>::infinity(), cmax = -cmin;
+            for (int b = 0; b < nb; b++) {
+                if (hp[b].max_s > mx) mx = hp[b].max_s;
+                if (hp[b].cp_min < cmin) cmin = hp[b].cp_min;
+                if (hp[b].cp_max > cmax) cmax = hp[b].cp_max;
+            }
+            *max_s = mx; *cp_min = cmin; *cp_max = cmax;
+        });
 }
 
 extern "C" int wt_forces(wt_handle *h, double *fx, double *fy, int64_t *surf, int64_t *rev)
 {
     WT_TRY(check_handle(h));
     if (!fx || !fy || !surf || !rev) return fail(WT_ERR_ARG, "null output");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
-    HIP_TRY(hipSetDevice(h->device));
-    const int nb = reduce_blocks((long)h->width * h->g.ny);
-    ForcePartial *dp = reinterpret_cast<ForcePartial *>(h->partials);
-    if (h->dtype == WT_F32)
-        hipLaunchKernelGGL(k_forces<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g,
-                           h->gl, h->width, dp);
-    else
-        hipLaunchKernelGGL(k_forces<double>, dim3(nb), dim3(256), 0, h->s_compute, (const double *)h->macro, h->mask,
-                           h->g, h->gl, h->width, dp);
-    HIP_TRY(hipGetLastError());
-    ForcePartial *hp = reinterpret_cast<ForcePartial *>(h->partials_host);
-    HIP_TRY(hipMemcpyAsync(hp, dp, nb * sizeof(ForcePartial), hipMemcpyDeviceToHost, h->s_compute));
-    HIP_TRY(hipStreamSynchronize(h->s_compute));
-    double sx = 0.0, sy = 0.0;
-    long long ns = 0, nr = 0;
-    for (int b = 0; b < nb; b++) { sx += hp[b].fx; sy += hp[b].fy; ns += hp[b].surf; nr += hp[b].rev; }
-    *fx = sx; *fy = sy; *surf = ns; *rev = nr;
-    return check_stuck(h);
+    WT_TRY(require_macro(h, true));
+    return reduce_macro<ForcePartial>(h,
+        [&](auto t, int nb, ForcePartial *dp) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_forces<T>, dim3(nb), dim3(256), 0, h->s_compute, (const T *)h->macro, h->mask, h->g, h->gl, h->width, dp);
+        },
+        [&](const ForcePartial *hp, int nb) {
+            double sx = 0.0, sy = 0.0;
+            long long ns = 0, nr = 0;
+            for (int b = 0; b < nb; b++) { sx += hp[b].fx; sy += hp[b].fy; ns += hp[b].surf; nr += hp[b].rev; }
+            *fx = sx; *fy = sy; *surf = ns; *rev = nr;
+        });
 }
 
 extern "C" int wt_clamp_events(wt_handle *h, int64_t *rho_events, int64_t *u_events)
 {
     WT_TRY(check_handle(h));
     if (!rho_events || !u_events) return fail(WT_ERR_ARG, "null output");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
-    HIP_TRY(hipSetDevice(h->device));
-    const int nb = reduce_blocks((long)h->width * h->g.ny);
-    ClampPartial *dp = reinterpret_cast<ClampPartial *>(h->partials);
-    if (h->dtype == WT_F32)
-        hipLaunchKernelGGL(k_clamp_events<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g, h->gl, h->width, dp);
-    else
-        hipLaunchKernelGGL(k_clamp_events<double>, dim3(nb), dim3(256), 0, h->s_compute, (const double *)h->macro, h->mask, h->g, h->gl, h->width, dp);
-    HIP_TRY(hipGetLastError());
-    ClampPartial *hp = reinterpret_cast<ClampPartial *>(h->partials_host);
-    HIP_TRY(hipMemcpyAsync(hp, dp, nb * sizeof(ClampPartial), hipMemcpyDeviceToHost, h->s_compute));
-    HIP_TRY(hipStreamSynchronize(h->s_compute));
-    long long nr = 0, nu = 0;
-    for (int b = 0; b < nb; b++) { nr += hp[b].rho_events; nu += hp[b].u_events; }
-    *rho_events = nr; *u_events = nu;
-    return check_stuck(h);
+    WT_TRY(require_macro(h, true));
+    return reduce_macro<ClampPartial>(h,
+        [&](auto t, int nb, ClampPartial *dp) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_clamp_events<T>, dim3(nb), dim3(256), 0, h->s_compute, (const T *)h->macro, h->mask, h->g, h->gl, h->width, dp);
+        },
+        [&](const ClampPartial *hp, int nb) {
+            long long nr = 0, nu = 0;
+            for (int b = 0; b < nb; b++) { nr += hp[b].rho_events; nu += hp[b].u_events; }
+            *rho_events = nr; *u_events = nu;
+        });
 }
 
 // Vorticity (html:411-417) needs uy of the columns left and right of the slab: fetch the
@@ -2537,9 +2551,7 @@ static int refresh_macro_ghosts(wt_handle *h)
 {
     if (h->transport == TR_NONE) return fail(WT_ERR_STATE, "slab handle has no transport");
     const Geom &g = h->g;
-    const size_t mp = (size_t)g.nxl * g.pitch;
     auto uy_col = [&](wt_handle *q, int i) { return reinterpret_cast<char *>(q->macro) + (2 * (size_t)q->g.nxl * q->g.pitch + (size_t)i * q->g.pitch) * q->esz; };
-    (void)mp;
     HIP_TRY(hipStreamSynchronize(h->s_compute));
     if (h->transport == TR_RCCL) {
         const ncclDataType_t dt = h->dtype == WT_F32 ? ncclFloat32 : ncclFloat64;
@@ -2574,16 +2586,34 @@ static int refresh_macro_ghosts(wt_handle *h)
 }
 
 template <typename T>
-static int field_impl(wt_handle *h, int mode, double u0, double max_s, double cp_min, double cp_max, double vs, void *out)
+static FieldParams<T> field_params(int mode, double u0, double max_s, double cp_min, double cp_max, double vs)
 {
+    return FieldParams<T>{(T)u0, (T)max_s, (T)cp_min, (T)cp_max, (T)vs, mode};
+}
+
+// macro planes -> an image of the owned sites in the staging buffer -> the caller's array: the scalar field in the handle's element type
+// (k_field), or its colours as RGBA8 (k_render)
+static int macro_image(wt_handle *h, bool rgba, int mode, double u0, double max_s, double cp_min, double cp_max, double vort_scale, void *out,
+                       const char *out_name)
+{
+    WT_TRY(check_handle(h));
+    if (!out) return fail(WT_ERR_ARG, "%s is null", out_name);
+    if (mode < 0 || mode > 2) return fail(WT_ERR_ARG, "mode must be 0 (speed), 1 (cp) or 2 (vort)");
+    WT_TRY(require_macro(h, true));
+    HIP_TRY(hipSetDevice(h->device));
+    if (mode == WT_FIELD_VORT && h->nranks > 1) WT_TRY(refresh_macro_ghosts(h));
     const Geom &g = h->g;
-    const size_t bytes = (size_t)h->width * g.ny * sizeof(T);
+    const size_t bytes = (size_t)h->width * g.ny * (rgba ? 4 : h->esz);
     WT_TRY(ensure_stage(h, bytes));
-    FieldParams<T> fp;
-    fp.U0 = (T)u0; fp.maxS = (T)max_s; fp.cpMin = (T)cp_min; fp.cpMax = (T)cp_max; fp.vortScale = (T)vs; fp.mode = mode;
-    dim3 blk(32, 8), grd((g.ny + 31) / 32, (h->width + 31) / 32);
-    hipLaunchKernelGGL(k_field<T>, grd, blk, 0, h->s_compute, reinterpret_cast<const T *>(h->macro), h->mask, g, h->gl,
-                       h->width, fp, reinterpret_cast<T *>(h->stage));
+    by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        const dim3 blk(32, 8), grd((g.ny + 31) / 32, (h->width + 31) / 32);
+        const FieldParams<T> fp = field_params<T>(mode, u0, max_s, cp_min, cp_max, vort_scale);
+        if (rgba) hipLaunchKernelGGL(k_render<T>, grd, blk, 0, h->s_compute, reinterpret_cast<const T *>(h->macro), h->mask, g, h->gl, h->width, fp,
+                                     reinterpret_cast<uchar4 *>(h->stage));
+        else hipLaunchKernelGGL(k_field<T>, grd, blk, 0, h->s_compute, reinterpret_cast<const T *>(h->macro), h->mask, g, h->gl, h->width, fp,
+                                reinterpret_cast<T *>(h->stage));
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, h->stage, bytes, hipMemcpyDeviceToHost, h->s_compute));
     HIP_TRY(hipStreamSynchronize(h->s_compute));
@@ -2593,46 +2623,13 @@ static int field_impl(wt_handle *h, int mode, double u0, double max_s, double cp
 extern "C" int wt_field(wt_handle *h, int mode, double u0, double max_s, double cp_min, double cp_max,
                         double vort_scale, void *t_out)
 {
-    WT_TRY(check_handle(h));
-    if (!t_out) return fail(WT_ERR_ARG, "t_out is null");
-    if (mode < 0 || mode > 2) return fail(WT_ERR_ARG, "mode must be 0 (speed), 1 (cp) or 2 (vort)");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
-    HIP_TRY(hipSetDevice(h->device));
-    if (mode == WT_FIELD_VORT && h->nranks > 1) WT_TRY(refresh_macro_ghosts(h));
-    return h->dtype == WT_F32 ? field_impl<float>(h, mode, u0, max_s, cp_min, cp_max, vort_scale, t_out)
-                              : field_impl<double>(h, mode, u0, max_s, cp_min, cp_max, vort_scale, t_out);
-}
-
-template <typename T>
-static int render_impl(wt_handle *h, int mode, double u0, double max_s, double cp_min, double cp_max, double vs, uint8_t *out)
-{
-    const Geom &g = h->g;
-    const size_t bytes = (size_t)h->width * g.ny * 4;
-    WT_TRY(ensure_stage(h, bytes));
-    FieldParams<T> fp;
-    fp.U0 = (T)u0; fp.maxS = (T)max_s; fp.cpMin = (T)cp_min; fp.cpMax = (T)cp_max; fp.vortScale = (T)vs; fp.mode = mode;
-    dim3 blk(32, 8), grd((g.ny + 31) / 32, (h->width + 31) / 32);
-    hipLaunchKernelGGL(k_render<T>, grd, blk, 0, h->s_compute, reinterpret_cast<const T *>(h->macro), h->mask, g, h->gl,
-                       h->width, fp, reinterpret_cast<uchar4 *>(h->stage));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, h->stage, bytes, hipMemcpyDeviceToHost, h->s_compute));
-    HIP_TRY(hipStreamSynchronize(h->s_compute));
-    return check_stuck(h);
+    return macro_image(h, false, mode, u0, max_s, cp_min, cp_max, vort_scale, t_out, "t_out");
 }
 
 extern "C" int wt_render_rgba(wt_handle *h, int mode, double u0, double max_s, double cp_min, double cp_max,
                               double vort_scale, uint8_t *rgba_out)
 {
-    WT_TRY(check_handle(h));
-    if (!rgba_out) return fail(WT_ERR_ARG, "rgba_out is null");
-    if (mode < 0 || mode > 2) return fail(WT_ERR_ARG, "mode must be 0 (speed), 1 (cp) or 2 (vort)");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
-    HIP_TRY(hipSetDevice(h->device));
-    if (mode == WT_FIELD_VORT && h->nranks > 1) WT_TRY(refresh_macro_ghosts(h));
-    return h->dtype == WT_F32 ? render_impl<float>(h, mode, u0, max_s, cp_min, cp_max, vort_scale, rgba_out)
-                              : render_impl<double>(h, mode, u0, max_s, cp_min, cp_max, vort_scale, rgba_out);
+    return macro_image(h, true, mode, u0, max_s, cp_min, cp_max, vort_scale, rgba_out, "rgba_out");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2644,8 +2641,7 @@ extern "C" int wt_advect_tracers(wt_handle *h, int n, const double *x, const dou
 {
     WT_TRY(check_handle(h));
     if (n < 0 || (n > 0 && (!x || !y || !x_new || !y_new || !speed || !ok))) return fail(WT_ERR_ARG, "bad tracer arrays");
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
+    WT_TRY(require_macro(h, true));
     if (h->nranks > 1) return fail(WT_ERR_STATE, "tracers need the whole lattice on one handle");
     if (!(dx1 > dx0) || !(dy1 > dy0) || !(u0 != 0.0)) return fail(WT_ERR_ARG, "bad window or u0");
     if (n == 0) return WT_OK;
@@ -2659,12 +2655,11 @@ extern "C" int wt_advect_tracers(wt_handle *h, int n, const double *x, const dou
     HIP_TRY(hipMemcpyAsync(dy, y, nd, hipMemcpyHostToDevice, h->s_compute));
     const Window w{dx0, dx1, dy0, dy1};
     const int nb = (n + 255) / 256;
-    if (h->dtype == WT_F32)
-        hipLaunchKernelGGL(k_advect<float>, dim3(nb), dim3(256), 0, h->s_compute, (const float *)h->macro, h->mask, h->g, h->gl, u0, w,
+    by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_advect<T>, dim3(nb), dim3(256), 0, h->s_compute, (const T *)h->macro, h->mask, h->g, h->gl, u0, w,
                            dt_frame, n, dx, dy, ox, oy, os, dok);
-    else
-        hipLaunchKernelGGL(k_advect<double>, dim3(nb), dim3(256), 0, h->s_compute, (const double *)h->macro, h->mask, h->g, h->gl, u0, w,
-                           dt_frame, n, dx, dy, ox, oy, os, dok);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(x_new, ox, nd, hipMemcpyDeviceToHost, h->s_compute));
     HIP_TRY(hipMemcpyAsync(y_new, oy, nd, hipMemcpyDeviceToHost, h->s_compute));
@@ -2737,15 +2732,6 @@ extern "C" int wt_canvas_stroke(wt_handle *h, int scale, int fade, int n, const 
     return WT_OK;
 }
 
-template <typename T>
-static void canvas_launch(wt_handle *h, const CanvasArgs &a, int mode, double u0, double max_s, double cp_min, double cp_max, double vs)
-{
-    FieldParams<T> fp;
-    fp.U0 = (T)u0; fp.maxS = (T)max_s; fp.cpMin = (T)cp_min; fp.cpMax = (T)cp_max; fp.vortScale = (T)vs; fp.mode = mode;
-    hipLaunchKernelGGL(k_canvas_compose<T>, dim3((unsigned)((a.d.w + 15) / 16), (unsigned)((a.d.h + 15) / 16)), dim3(256), 0, h->s_compute,
-                       reinterpret_cast<const T *>(h->macro), (const uint8_t *)h->mask, h->g, fp, a, h->cv_out);
-}
-
 extern "C" int wt_canvas_compose(wt_handle *h, int scale, int mode, double u0, double max_s, double cp_min, double cp_max, double vort_scale,
                                  const double *poly_xy, int npoly, const uint8_t *bar_rgb, const float *text_alpha, int use_trails,
                                  uint8_t *rgba_out)
@@ -2754,8 +2740,7 @@ extern "C" int wt_canvas_compose(wt_handle *h, int scale, int mode, double u0, d
     if (!rgba_out || !bar_rgb) return fail(WT_ERR_ARG, "null argument");
     if (mode < 0 || mode > 2) return fail(WT_ERR_ARG, "mode must be 0 (speed), 1 (cp) or 2 (vort)");
     if (npoly < 0 || npoly > CV_MAX_POLY || (npoly > 0 && !poly_xy)) return fail(WT_ERR_ARG, "polygon of 0 .. %d points expected", CV_MAX_POLY);
-    if (!h->inited || !h->mask_set) return fail(WT_ERR_STATE, "state or mask missing");
-    if (h->macro_stale) return fail(WT_ERR_STATE, "wt_write_f replaced the populations: (rho,ux,uy) are emitted by the next wt_step");
+    WT_TRY(require_macro(h, true));
     HIP_TRY(hipSetDevice(h->device));
     WT_TRY(canvas_ensure(h, scale));
     const CanvasDims d = canvas_dims(scale);
@@ -2779,8 +2764,11 @@ extern "C" int wt_canvas_compose(wt_handle *h, int scale, int mode, double u0, d
         h->cv_text_set = true;
     }
     a.text = h->cv_text_set ? h->cv_text : nullptr;
-    if (h->dtype == WT_F32) canvas_launch<float>(h, a, mode, u0, max_s, cp_min, cp_max, vort_scale);
-    else canvas_launch<double>(h, a, mode, u0, max_s, cp_min, cp_max, vort_scale);
+    by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_canvas_compose<T>, dim3((unsigned)((a.d.w + 15) / 16), (unsigned)((a.d.h + 15) / 16)), dim3(256), 0, h->s_compute,
+                           reinterpret_cast<const T *>(h->macro), (const uint8_t *)h->mask, h->g, field_params<T>(mode, u0, max_s, cp_min, cp_max, vort_scale), a, h->cv_out);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rgba_out, h->cv_out, npx * 4, hipMemcpyDeviceToHost, h->s_compute));
     HIP_TRY(hipStreamSynchronize(h->s_compute));

@@ -109,7 +109,10 @@ def test_write_f_read_f_roundtrip_and_restart(pkg, oracle_c):
         e.write_f(f0)
         assert bits_equal(e.read_f(), f0)
         # (rho,ux,uy) belong to the step that produced a state: after a restore they are unavailable until a step emits them
-        for call in (e.read_macro, lambda: e.reduce_ranges(0.05), e.forces, lambda: e.field(0, 0.05, 1.0, -1.0, 1.0, 0.06)):
+        for call in (e.read_macro, lambda: e.reduce_ranges(0.05), e.forces, lambda: e.field(0, 0.05, 1.0, -1.0, 1.0, 0.06),
+                     e.clamp_events, lambda: e.render_rgba(0, 0.05, 1.0, -1.0, 1.0, 0.06),
+                     lambda: e.advect_tracers(np.array([0.5]), np.array([0.1]), 1.0, 0.05, (-1.0, 2.0, -0.5, 0.5)),
+                     lambda: e.canvas_compose(1, 0, 0.05, 1.0, -1.0, 1.0, 0.06, np.zeros((0, 2)), np.zeros((308, 3), np.uint8), None, False)):
             with pytest.raises(pkg.WTError) as err:
                 call()
             assert err.value.code == -5 and "wt_write_f" in str(err.value)
@@ -137,11 +140,23 @@ def test_error_paths(pkg):
     with pytest.raises(pkg.WTError):
         pkg.Engine(2, 2)
     with pkg.Engine(64, 64) as e:
+        # every read-out of the macro planes that also reads the mask refuses (state error) until both a state and a mask exist
+        masked = (lambda: e.reduce_ranges(0.06), e.forces, e.clamp_events, lambda: e.field(0, 0.06, 1.0, -1.0, 1.0, 0.06),
+                  lambda: e.render_rgba(0, 0.06, 1.0, -1.0, 1.0, 0.06),
+                  lambda: e.advect_tracers(np.array([0.5]), np.array([0.1]), 1.0, 0.06, (-1.0, 2.0, -0.5, 0.5)))
         with pytest.raises(pkg.WTError):
             e.step(1, 0.58, 0.06)            # no state, no mask
+        for call in masked + (e.read_macro, e.read_f):
+            with pytest.raises(pkg.WTError) as err:
+                call()
+            assert err.value.code == -5
         e.init_equilibrium(0.06)
         with pytest.raises(pkg.WTError):
             e.step(1, 0.58, 0.06)            # still no mask
+        for call in masked:
+            with pytest.raises(pkg.WTError) as err:
+                call()
+            assert err.value.code == -5
         e.set_mask(np.zeros((64, 64), np.uint8))
         with pytest.raises(pkg.WTError):
             e.step(1, -1.0, 0.06)            # bad tau
