@@ -17,6 +17,9 @@
 //
 // All three end the same way: the last block of a member to finish (member_done) adds the member's partials in index order, so
 // that a sample does not depend on the order in which the blocks ran, and writes one row of a SampleTable.
+//
+// Mean fields (wtp_enable_mean) are no reduction: k_mean_batch, launched behind the three, streams every member's emitted rho,
+// ux, uy once and adds them and their products to seven planes of running sums, one owner thread per entry.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,7 +42,13 @@ static const int kTicketStride = 32;       // unsigned ints between the members'
 #define WTP_MEX_WINDOW 1                   // 1: k_mex_batch visits a member's body columns only; 0: every interior column (measurements)
 #endif
 
+#ifndef WTP_MEAN_ROWS
+#define WTP_MEAN_ROWS 2                    // rows of a column that one lane of k_mean_batch owns: 2 = 16-byte accesses to the sums; 1 = 8-byte ones (measurements)
+#endif
+static const int kMeanPlanes = 7;          // sums of rho, ux, uy, rho rho, ux ux, uy uy, ux uy, in wtp_mean_sums' order
+
 struct MexPartial { double fx, fy, mz; long long links; };     // one column's sums of k_mex_batch
+template <typename V, int R> using RowRun = V __attribute__((ext_vector_type(R)));     // R consecutive rows of one column: one load or store
 
 // Element strides between consecutive members of each array.  Every stride is rounded to 4 KiB and grown by 17 KiB, as
 // wt_create's plane stride is, so that the members' lattices do not all start on the same HBM channels.
@@ -123,6 +132,12 @@ struct wtp_batch {
     MexPartial *x_col = nullptr;         // [B][NX]: the columns' partials of the running reduction
     unsigned int *x_tickets = nullptr;   // [B] tickets, kTicketStride apart
     SampleTable xforces;                 // fx, fy, mz (double), links (long long)
+    // mean fields (wtp_enable_mean); every pointer is null until then
+    bool mean = false;
+    double *m_sums = nullptr;            // [B][7][NX][m_pitch], y fastest, members m_stride apart
+    long long *m_cnt = nullptr;          // [B]: samples added
+    long m_stride = 0;
+    int m_pitch = 0;                     // NY rounded up to WTP_MEAN_ROWS
     bool inited = false;
     long long steps_done = 0;
 };
@@ -370,6 +385,52 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restr
     }
 }
 
+// Mean fields of every member in one launch: grid (ceil(NX * ceil(NY / R) / 256), B), R = WTP_MEAN_ROWS; one lane per run of R
+// consecutive rows of one column.  Definition (include/wt_polar.h): for member m and cell (i, j), let rho, ux, uy be what
+// wtp_read_macro would return after a sampled step, converted exactly to double.  Solid and boundary cells are included; no cell
+// is special-cased.  The device keeps seven running sums per cell, in double, added in sample order: sum rho, sum ux, sum uy,
+// sum rho*rho, sum ux*ux, sum uy*uy, sum ux*uy.  Each product is one double multiplication, added as a separate operation;
+// nothing is fused.  For fp32 members the products are exact in double; for fp64 members they round once, as NumPy's do.  In
+// both cases the seven sums are bit-identical to a NumPy loop over wtp_read_macro at the sampled steps.  The device also keeps a
+// per-member sample count n (int64).
+// A pure stream: a lane loads its run of each of the three emitted planes ([NX][pitch], y fastest) and of each of the seven sum
+// planes ([NX][apitch], apitch = NY rounded up to R, so that rows past NY are never moved), adds, and stores the seven runs
+// back.  Every entry has one owner and launches are stream-ordered: plain read-modify-writes in sample order.  With R = 2 a lane
+// moves 16 bytes per access to the sums and 8 or 16 per access to the fields.  A run that starts at row NY - 1 of an odd NY owns
+// one row; its second field element lies in the column's pad (pitch > NY there) and is loaded, not used.
+template <typename T>
+__global__ __launch_bounds__(256) void k_mean_batch(const T *__restrict__ macro, Geom g, MemberStrides ms, double *__restrict__ sums,
+                                                    long stride, int apitch, long long *__restrict__ count)
+{
+    constexpr int R = WTP_MEAN_ROWS;
+    const long m = blockIdx.y;
+    const int nx = g.nxl, ny = g.ny;
+    const int runs = (ny + R - 1) / R;                              // runs of a column
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q == 0) count[m] += 1;
+    if (q >= (long)nx * runs) return;
+    const int i = (int)(q / runs), j = (int)(q - (long)i * runs) * R;
+    const long mp = (long)nx * g.pitch, ap = (long)nx * apitch;     // elements of one field plane / one sum plane
+    const T *src = macro + m * ms.macro + (long)i * g.pitch + j;
+    double *acc = sums + m * stride + (long)i * apitch + j;
+    RowRun<T, R> fld[3];
+    RowRun<double, R> s[kMeanPlanes];
+#pragma unroll
+    for (int a = 0; a < 3; a++) fld[a] = *reinterpret_cast<const RowRun<T, R> *>(src + a * mp);
+#pragma unroll
+    for (int k = 0; k < kMeanPlanes; k++) s[k] = *reinterpret_cast<const RowRun<double, R> *>(acc + k * ap);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (j + r >= ny) continue;
+        const double rho = (double)fld[0][r], ux = (double)fld[1][r], uy = (double)fld[2][r];
+        const double rr = rho * rho, uu = ux * ux, vv = uy * uy, uv = ux * uy;
+        s[0][r] += rho; s[1][r] += ux; s[2][r] += uy;
+        s[3][r] += rr; s[4][r] += uu; s[5][r] += vv; s[6][r] += uv;
+    }
+#pragma unroll
+    for (int k = 0; k < kMeanPlanes; k++) *reinterpret_cast<RowRun<double, R> *>(acc + k * ap) = s[k];
+}
+
 // ------------------------------------------------------------------------------------------
 // life cycle
 // ------------------------------------------------------------------------------------------
@@ -397,7 +458,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets, b->stage,
-                    b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets};
+                    b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
     if (b->st) (void)hipStreamDestroy(b->st);
@@ -475,7 +536,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.3 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -531,6 +592,21 @@ static int clear_surface_sums(wtp_batch *b, int first, int count)
     return WT_OK;
 }
 
+// Zero the mean-field sums and the sample counts of members [first, first+count), in stream order.
+static int zero_mean_sums(wtp_batch *b, int first, int count)
+{
+    HIP_TRY(hipMemsetAsync(b->m_sums + (size_t)first * b->m_stride, 0, (size_t)count * b->m_stride * sizeof(double), b->st));
+    HIP_TRY(hipMemsetAsync(b->m_cnt + first, 0, (size_t)count * sizeof(long long), b->st));
+    return WT_OK;
+}
+
+// What restarts the time statistics of members [first, first+count): the surface sums and the mean fields, each if enabled.
+static int clear_sums(wtp_batch *b, int first, int count)
+{
+    WT_TRY(clear_surface_sums(b, first, count));
+    return b->mean ? zero_mean_sums(b, first, count) : WT_OK;
+}
+
 extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *masks)
 {
     WT_TRY(check_batch(b));
@@ -548,7 +624,7 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
         for (size_t q = 0; q < n; q++) m01[q] = src[q] ? 1 : 0;
         surface_rows(b, first + k, m01.data());
         mex_window(b, first + k, m01.data());
-        WT_TRY(clear_surface_sums(b, first + k, 1));            // the member's surface cells moved
+        WT_TRY(clear_sums(b, first + k, 1));                    // the member's surface cells moved; a mean across two bodies means nothing
         HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
         uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
         dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
@@ -591,7 +667,7 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
     b->inited = true;
     b->steps_done = 0;
     b->h_step.clear();
-    return clear_surface_sums(b, 0, b->members);
+    return clear_sums(b, 0, b->members);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -657,6 +733,17 @@ static int launch_mex(wtp_batch *b, int row)
     return WT_OK;
 }
 
+// The emitted fields of every member added to its mean-field sums, and one sample to its count.
+template <typename T>
+static int launch_mean(wtp_batch *b)
+{
+    const long lanes = (long)b->nx * (b->m_pitch / WTP_MEAN_ROWS);
+    hipLaunchKernelGGL(k_mean_batch<T>, dim3((unsigned)((lanes + 255) / 256), (unsigned)b->members), dim3(256), 0, b->st,
+                       (const T *)b->macro, b->g, b->ms, b->m_sums, b->m_stride, b->m_pitch, b->m_cnt);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 // One sample of the state the last step left: every read-out that is enabled, into row `row` of its table.
 template <typename T>
 static int sample_into(wtp_batch *b, int row)
@@ -664,6 +751,7 @@ static int sample_into(wtp_batch *b, int row)
     WT_TRY(launch_forces<T>(b, row));
     if (b->loads) WT_TRY(launch_loads<T>(b, row, true));
     if (b->mex) WT_TRY(launch_mex<T>(b, row));
+    if (b->mean) WT_TRY(launch_mean<T>(b));
     return WT_OK;
 }
 
@@ -751,9 +839,9 @@ extern "C" int wtp_clear_history(wtp_batch *b)
 {
     WT_TRY(check_batch(b));
     b->h_step.clear();                           // (rows are only written by later, stream-ordered reductions)
-    if (!b->loads) return WT_OK;
+    if (!b->loads && !b->mean) return WT_OK;
     HIP_TRY(hipSetDevice(b->device));
-    return clear_surface_sums(b, 0, b->members);
+    return clear_sums(b, 0, b->members);
 }
 
 extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, int64_t *rev)
@@ -921,14 +1009,15 @@ extern "C" int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_ev
     return WT_OK;
 }
 
+// One [NX][pitch] plane of the device (y fastest) to [NY][NX] rows on the host, through the stage.
 template <typename T>
-static int read_plane(wtp_batch *b, const T *src_cols, T *host_dst)
+static int read_plane(wtp_batch *b, const T *src_cols, long pitch, T *host_dst)
 {
     const Geom &g = b->g;
     const size_t bytes = (size_t)b->nx * g.ny * sizeof(T);
     WT_TRY(ensure_stage(b, bytes));
     dim3 blk(32, 8), grd((g.ny + 31) / 32, (b->nx + 31) / 32);
-    hipLaunchKernelGGL(k_cols_to_rows<T>, grd, blk, 0, b->st, src_cols, reinterpret_cast<T *>(b->stage), 0, b->nx, g.ny, g.pitch);
+    hipLaunchKernelGGL(k_cols_to_rows<T>, grd, blk, 0, b->st, src_cols, reinterpret_cast<T *>(b->stage), 0, b->nx, g.ny, pitch);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_dst, b->stage, bytes, hipMemcpyDeviceToHost, b->st));
     HIP_TRY(hipStreamSynchronize(b->st));
@@ -947,7 +1036,7 @@ static int read_f_impl(wtp_batch *b, int member, void *out)
 {
     const size_t n = (size_t)b->nx * b->ny;
     for (int k = 0; k < 9; k++)
-        WT_TRY(read_plane<T>(b, fptr<T>(b, b->cur, member) + k * b->g.plane + b->g.pitch, reinterpret_cast<T *>(out) + k * n));
+        WT_TRY(read_plane<T>(b, fptr<T>(b, b->cur, member) + k * b->g.plane + b->g.pitch, b->g.pitch, reinterpret_cast<T *>(out) + k * n));
     return WT_OK;
 }
 
@@ -967,7 +1056,7 @@ static int read_macro_impl(wtp_batch *b, int member, void *rho, void *ux, void *
     const T *m = macro_of<T>(b, member);
     void *dst[3] = {rho, ux, uy};
     for (int a = 0; a < 3; a++)
-        if (dst[a]) WT_TRY(read_plane<T>(b, m + a * mp, reinterpret_cast<T *>(dst[a])));
+        if (dst[a]) WT_TRY(read_plane<T>(b, m + a * mp, b->g.pitch, reinterpret_cast<T *>(dst[a])));
     return WT_OK;
 }
 
@@ -977,4 +1066,49 @@ extern "C" int wtp_read_macro(wtp_batch *b, int member, void *rho, void *ux, voi
     WT_TRY(check_member(b, member));
     HIP_TRY(hipSetDevice(b->device));
     return b->dtype == WT_F32 ? read_macro_impl<float>(b, member, rho, ux, uy) : read_macro_impl<double>(b, member, rho, ux, uy);
+}
+
+// ------------------------------------------------------------------------------------------
+// mean fields
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_mean(wtp_batch *b)
+{
+    WT_TRY(check_batch(b));
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->m_sums) {
+        const size_t B = (size_t)b->members;
+        const int pitch = (b->ny + WTP_MEAN_ROWS - 1) / WTP_MEAN_ROWS * WTP_MEAN_ROWS;
+        const long stride = member_stride((size_t)kMeanPlanes * b->nx * pitch * sizeof(double), sizeof(double));
+        void *sums = nullptr, *cnt = nullptr;
+        hipError_t e = hipMalloc(&sums, B * (size_t)stride * sizeof(double));
+        if (e == hipSuccess && (e = hipMalloc(&cnt, B * sizeof(long long))) != hipSuccess) (void)hipFree(sums);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // (the batch goes on without the read-out: later launches must not see this error)
+            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the mean-field sums (%zu bytes) could not be allocated: %s",
+                        B * (size_t)stride * sizeof(double), hipGetErrorString(e));
+        }
+        b->m_sums = (double *)sums; b->m_cnt = (long long *)cnt; b->m_stride = stride; b->m_pitch = pitch;
+    }
+    WT_TRY(zero_mean_sums(b, 0, b->members));
+    b->mean = true;
+    return WT_OK;
+}
+
+extern "C" int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy, double *rho2, double *ux2,
+                             double *uy2, double *uxuy)
+{
+    WT_TRY(check_batch(b));
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    if (!b->mean) return fail(WT_ERR_STATE, "the mean fields are not enabled (wtp_enable_mean)");
+    HIP_TRY(hipSetDevice(b->device));
+    double *dst[kMeanPlanes] = {rho, ux, uy, rho2, ux2, uy2, uxuy};
+    const double *src = b->m_sums + (size_t)member * b->m_stride;
+    for (int k = 0; k < kMeanPlanes; k++)
+        if (dst[k]) WT_TRY(read_plane<double>(b, src + (size_t)k * b->nx * b->m_pitch, b->m_pitch, dst[k]));
+    if (n) {
+        static_assert(sizeof(int64_t) == sizeof(long long), "the count is 8 bytes");
+        HIP_TRY(hipStreamSynchronize(b->st));
+        HIP_TRY(hipMemcpy(n, b->m_cnt + member, sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return WT_OK;
 }

@@ -7,7 +7,9 @@ bit-identical to a :class:`~airfoil_cfd_tool_amd.WindTunnel` with the same input
 kernel launch per step.  Lift, drag and separation are sampled on the device into a history that is read once; with
 surface loads enabled (``PolarEngine.enable_loads``, ``run_polar(loads=True)``) so are the pitching moment and the
 chordwise surface pressure; with the momentum exchange enabled (``PolarEngine.enable_momentum_exchange``,
-``run_polar(total_forces=True)``) a second force read-out that holds pressure and friction together.
+``run_polar(total_forces=True)``) a second force read-out that holds pressure and friction together; with the mean fields
+enabled (``PolarEngine.enable_mean_fields``, ``run_polar(mean_fields=True)``) the time-mean flow field of every angle and the
+fluctuation about it (:func:`mean_flow`: Reynolds stresses, pressure r.m.s.), from seven running sums kept on the device.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -36,7 +38,10 @@ EXPORTS = (
     "wtp_history", "wtp_clear_history", "wtp_forces", "wtp_clamp_events", "wtp_read_f", "wtp_read_macro", "wtp_sync",
     "wtp_enable_loads", "wtp_history_moment", "wtp_moment", "wtp_surface",
     "wtp_enable_mex", "wtp_history_mex", "wtp_mex",
+    "wtp_enable_mean", "wtp_mean_sums",
 )
+
+MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
 
 _lib = None
 
@@ -77,6 +82,8 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_enable_mex": ([B, dp, dp], c_int),
         "wtp_history_mex": ([B, c_int, c_int, dp, dp, dp, ip], c_int),
         "wtp_mex": ([B, dp, dp, dp, ip], c_int),
+        "wtp_enable_mean": ([B], c_int),
+        "wtp_mean_sums": ([B, c_int, ip, dp, dp, dp, dp, dp, dp, dp], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -115,6 +122,7 @@ class PolarEngine:
         self._b = c_void_p()
         self.loads_enabled = False
         self.mex_enabled = False
+        self.mean_enabled = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -222,6 +230,21 @@ class PolarEngine:
         _check(self._lib.wtp_mex(self._b, _dp(fx), _dp(fy), _dp(mz), _ip(links)))
         return fx, fy, mz, links
 
+    def enable_mean_fields(self) -> None:
+        """Add rho, ux, uy of every cell and their products to seven running sums per member from the next sample on
+        (wt_polar.h).  Calling it again zeroes the sums and the counts.  Independent of enable_loads and
+        enable_momentum_exchange."""
+        _check(self._lib.wtp_enable_mean(self._b))
+        self.mean_enabled = True
+
+    def mean_sums(self, member: int) -> Dict[str, np.ndarray]:
+        """One member's sample count `n` and its seven sums over the samples, [NY][NX] float64 each: rho, ux, uy, rho2, ux2,
+        uy2, uxuy (see mean_flow)."""
+        n = np.zeros(1, np.int64)
+        out = {k: np.empty((self.ny, self.nx)) for k in MEAN_SUMS}
+        _check(self._lib.wtp_mean_sums(self._b, int(member), _ip(n), *(_dp(out[k]) for k in MEAN_SUMS)))
+        return {"n": int(n[0]), **out}
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -271,12 +294,15 @@ class PolarPoint:
     cm_total_mean: InitVar[Optional[float]] = None
     cm_total_std: InitVar[Optional[float]] = None
     cd_friction_mean: InitVar[Optional[float]] = None      # cd_total_mean - cd_mean
+    mean: InitVar[Optional[Dict[str, object]]] = None      # mean_flow() of this angle (None: not sampled); init-only like the totals
 
-    def __post_init__(self, cl_total_mean, cl_total_std, cd_total_mean, cd_total_std, cm_total_mean, cm_total_std, cd_friction_mean):
+    def __post_init__(self, cl_total_mean, cl_total_std, cd_total_mean, cd_total_std, cm_total_mean, cm_total_std, cd_friction_mean,
+                      mean):
         self.cl_total_mean, self.cl_total_std = cl_total_mean, cl_total_std
         self.cd_total_mean, self.cd_total_std = cd_total_mean, cd_total_std
         self.cm_total_mean, self.cm_total_std = cm_total_mean, cm_total_std
         self.cd_friction_mean = cd_friction_mean
+        self.mean = mean
 
     @property
     def converged(self) -> bool:
@@ -327,6 +353,28 @@ def surface_cp(surface: Dict[str, np.ndarray], alpha: float, u0: float) -> Dict[
         cpu = (surface["rho_upper"] / nu - 1.0) / (1.5 * u0 * u0)
         cpl = (surface["rho_lower"] / nl - 1.0) / (1.5 * u0 * u0)
     return {"x_over_c": (0.25 + (xw - 0.25) / math.cos(math.radians(alpha)))[body], "cp_upper": cpu[body], "cp_lower": cpl[body]}
+
+
+def mean_flow(sums: Dict[str, np.ndarray], u0: float) -> Dict[str, object]:
+    """The time-mean flow field and the fluctuation about it from PolarEngine.mean_sums (n samples, sums S over them), [NY][NX]
+    float64 each, solid cells included as the device holds them:
+    rho, ux, uy: the means S/n.  uu, vv, uv: the central second moments S2/n - mean * mean of (ux, ux), (uy, uy), (ux, uy), the
+    Reynolds stresses per unit density; uu and vv are floored at 0 (the difference of two roundings can fall below it where the
+    flow is steady).  rho_var: that of rho, floored likewise.  cp_mean = (mean rho - 1) / (1.5 U0^2), k_ranges' formula, as
+    surface_cp; cp_rms = sqrt(rho_var) / (1.5 U0^2).  speed = |(mean ux, mean uy)|; tke = (uu + vv) / 2.  `n` is the count.
+    Everything is NaN when n = 0."""
+    n = int(sums["n"])
+    if n == 0:
+        nan = np.full(np.shape(sums["rho"]), np.nan)
+        return {"n": 0, **{k: nan.copy() for k in ("rho", "ux", "uy", "uu", "vv", "uv", "rho_var", "cp_mean", "cp_rms", "speed", "tke")}}
+    rho, ux, uy = (np.asarray(sums[k], np.float64) / n for k in ("rho", "ux", "uy"))
+    uu = np.maximum(np.asarray(sums["ux2"], np.float64) / n - ux * ux, 0.0)
+    vv = np.maximum(np.asarray(sums["uy2"], np.float64) / n - uy * uy, 0.0)
+    uv = np.asarray(sums["uxuy"], np.float64) / n - ux * uy
+    rho_var = np.maximum(np.asarray(sums["rho2"], np.float64) / n - rho * rho, 0.0)
+    q = 1.5 * u0 * u0
+    return {"n": n, "rho": rho, "ux": ux, "uy": uy, "uu": uu, "vv": vv, "uv": uv, "rho_var": rho_var, "cp_mean": (rho - 1.0) / q,
+            "cp_rms": np.sqrt(rho_var) / q, "speed": np.hypot(ux, uy), "tke": 0.5 * (uu + vv)}
 
 
 def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp_events=(0, 0), *, mz=None, surface=None,
@@ -380,7 +428,7 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False) -> PolarResult:
+              total_forces: bool = False, mean_fields: bool = False) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -388,7 +436,10 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     surface); the forces and the flow are the same bits either way.
     `total_forces`: also sample the momentum exchange, the force of pressure and friction together and its moment about the
     quarter chord (PolarPoint.cl_total_mean ... cd_friction_mean; polar_rows(result, forces="total")).  Off by default: the
-    sweep then runs, and costs, what it did without it; every other value is the same bits either way."""
+    sweep then runs, and costs, what it did without it; every other value is the same bits either way.
+    `mean_fields`: also keep the running sums of rho, ux, uy and their products over the samples on the device and attach
+    mean_flow() of each angle as PolarPoint.mean: the time-mean field, the Reynolds stresses, the pressure r.m.s.  The warm-up
+    takes no sample, so nothing of it enters the mean.  Off by default, with the same guarantees as `total_forces`."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -410,6 +461,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_loads(*quarter_chord(nx, ny))
         if total_forces:
             eng.enable_momentum_exchange(*quarter_chord(nx, ny))
+        if mean_fields:
+            eng.enable_mean_fields()
         if warmup_steps:
             eng.step(warmup_steps, tau, u0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
@@ -417,10 +470,13 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         h = eng.history()
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
+        means = [mean_flow(eng.mean_sums(m), u0) for m in range(len(alphas))] if mean_fields else [None] * len(alphas)
     points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]),
                           mz=h["mz"][:, m] if loads else None, surface=surfaces[m],
                           **({k: h[k][:, m] for k in ("fx_mex", "fy_mex", "mz_mex", "links")} if total_forces else {}))
               for m, a in enumerate(alphas)]
+    for p, mean in zip(points, means):
+        p.mean = mean
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every))
 
 

@@ -126,6 +126,30 @@ WTP_API int wtp_history_mex(wtp_batch *b, int first, int count, double *fx, doub
 /* The momentum exchange of every member on the current lattice, [B] each: the twin of wtp_forces / wtp_moment.  Adds no
  * history row.  No output may be NULL. */
 WTP_API int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t *links);
+/*
+ * Mean fields: the running sums from which the host forms the time-mean flow field of every member and the fluctuation
+ * about it (Reynolds stresses, pressure r.m.s.), added on the device behind the force reduction of a sampled step.
+ * Definition: for member m and cell (i, j), let rho, ux, uy be what wtp_read_macro would return after a sampled step,
+ * converted exactly to double.  Solid and boundary cells are included; no cell is special-cased.  The device keeps seven
+ * running sums per cell, in double, added in sample order: sum rho, sum ux, sum uy, sum rho*rho, sum ux*ux, sum uy*uy,
+ * sum ux*uy.  Each product is one double multiplication, added as a separate operation; nothing is fused.  For fp32
+ * members the products are exact in double; for fp64 members they round once, as NumPy's do.  In both cases the seven
+ * sums are bit-identical to a NumPy loop over wtp_read_macro at the sampled steps.  The device also keeps a per-member
+ * sample count n (int64).
+ *
+ * wtp_enable_mean switches the sampling on.  It allocates [B][7] planes of doubles (7 * 8 bytes per site and member: a few
+ * GB at 320x160 with B = 1024) and zeroes them; from the next sample on, every sampled step adds to them.  Calling it again
+ * zeroes the sums and the counts.  Where the allocation fails it returns WT_ERR_OOM, holds nothing, and the batch goes on
+ * working with the read-out off.  wtp_init_equilibrium and wtp_clear_history zero the sums and the counts; wtp_set_masks
+ * zeroes those of the members it touches (a mean across a change of the body means nothing).  The on-demand calls
+ * (wtp_forces, wtp_moment, wtp_mex) add nothing.  It is independent of wtp_enable_loads and wtp_enable_mex.  A batch that
+ * never calls it behaves, and costs, as before; with it on, every other value is the same bits.
+ */
+WTP_API int wtp_enable_mean(wtp_batch *b);
+/* One member's sample count *n and its seven sums, each [NY][NX] doubles like wtp_read_macro's planes.  Any output may be
+ * NULL.  WT_ERR_ARG for a member outside the batch, before any device call; WT_ERR_STATE while the read-out is not enabled. */
+WTP_API int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy, double *rho2, double *ux2,
+                          double *uy2, double *uxuy);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

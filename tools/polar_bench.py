@@ -19,6 +19,12 @@ The same protocol for the momentum-exchange readout (wtp_enable_mex: one k_mex_b
 surface loads are on in both variants.  --lib loads another build of libwtpolar.so (such as one compiled with -DWTP_MEX_WINDOW=0,
 which visits every interior column).
 
+    python tools/polar_bench.py --mean [--loads] [--mex] [--lib PATH] [the same options]
+
+The same protocol for the mean fields (wtp_enable_mean: one k_mean_batch behind the reductions); with --loads / --mex those read-outs
+are on in both variants.  The line also gives the bytes one sample moves (3 sizeof(T) + 2 * 56 per site and member: derived, not
+measured) and what the added time per sample makes of them against 8 TB/s.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -55,7 +61,7 @@ def bench_batch(nx, ny, b, steps, warmup, masks):
         return time.perf_counter() - t0
 
 
-def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False):
+def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
     """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats."""
     out = []
     with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1) as eng:
@@ -65,6 +71,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.enable_loads(*pkg.polar.quarter_chord(nx, ny))
         if mex:
             eng.enable_momentum_exchange(*pkg.polar.quarter_chord(nx, ny))
+        if mean:
+            eng.enable_mean_fields()
         eng.step(warmup - warmup % every, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -121,6 +129,31 @@ def mex_cost(a):
             print(json.dumps(line), flush=True)
 
 
+def mean_cost(a):
+    variants = (False, True)
+    for size in a.sizes.split(","):
+        nx, ny = (int(v) for v in size.split("x"))
+        for b in (int(v) for v in a.members.split(",")):
+            masks = _masks(nx, ny, b)
+            t = {v: [] for v in variants}
+            for r in range(a.repeats):                 # in turn, so that a drift of the clocks lands on both
+                for mean in variants:
+                    t[mean] += bench_sampled(nx, ny, b, a.steps, a.warmup, masks, a.sample_every, a.loads, 1, mex=a.mex, mean=mean)
+            us = {k: np.array(v) / a.steps * 1e6 for k, v in t.items()}
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            samples = a.steps // a.sample_every
+            per_sample = (med[True] - med[False]) * a.steps / samples
+            bytes_sample = b * nx * ny * (3 * 4 + 2 * 56)
+            line = {"tool": "polar_bench --mean", "lib": a.lib or "default", "loads": bool(a.loads), "mex": bool(a.mex), "nx": nx, "ny": ny,
+                    "dtype": "float32", "members": b, "steps": a.steps, "sample_every": a.sample_every, "repeats": a.repeats,
+                    "us_per_step_plain": [round(float(v), 3) for v in us[False]], "us_per_step_plain_median": round(med[False], 3),
+                    "us_per_step_mean": [round(float(v), 3) for v in us[True]], "us_per_step_mean_median": round(med[True], 3),
+                    "mean_us_per_sample": round(per_sample, 3), "mean_fraction_of_step": round(med[True] / med[False] - 1.0, 5),
+                    "mean_bytes_per_sample": bytes_sample,
+                    "mean_fraction_of_8TBps_host_clock": round(bytes_sample / (per_sample * 1e-6) / PEAK_BPS, 4) if per_sample > 0 else None}
+            print(json.dumps(line), flush=True)
+
+
 def bench_sequential(nx, ny, b, steps, warmup, masks):
     hs = []
     try:
@@ -153,12 +186,15 @@ def main():
     ap.add_argument("--no-sequential", action="store_true", help="time the batch only")
     ap.add_argument("--loads", action="store_true", help="the sampled step with and without surface loads")
     ap.add_argument("--mex", action="store_true", help="the sampled step with and without the momentum-exchange readout")
+    ap.add_argument("--mean", action="store_true", help="the sampled step with and without the mean fields")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=7)
     a = ap.parse_args()
     if a.lib:
         pkg.polar.load_polar_library(a.lib)
+    if a.mean:
+        return mean_cost(a)
     if a.mex:
         return mex_cost(a)
     if a.loads:
