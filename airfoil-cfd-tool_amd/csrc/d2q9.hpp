@@ -332,6 +332,46 @@ __device__ __forceinline__ void collide(const T (&fin)[9], T tau, T (&fo)[9], T 
     uy = v;
 }
 
+// The collision a step kernel runs in an interior fluid cell: plain BGK (collide) or BGK with a Smagorinsky eddy viscosity (collide_les).
+enum : int { COLLIDE_BGK = 0, COLLIDE_LES = 1 };
+
+// BGK with a Smagorinsky subgrid viscosity (Hou et al. 1996; include/wt_polar.h "Smagorinsky subgrid viscosity"): operation for operation
+// collide<T> up to the equilibrium; then the relaxation time of THIS site grows with the norm of its non-equilibrium stress:
+//   n[k] = fin[k] - eq[k];  Pxx, Pyy, Pxy = the second moments of n (k = 0 adds nothing);  q = sqrt(Pxx^2 + 2 Pxy^2 + Pyy^2)
+//   te = 0.5 (tau + sqrt(tau^2 + c q / rho)),  c = 18 sqrt(2) Cs^2 rounded to T on the host;  fo[k] = fin[k] - n[k] / te
+// in the arithmetic contract of this file (left to right as written, one rounding per operation, IEEE division and square root).  The
+// division is per site, so none of the per-tau fast divisions applies.  c = 0 gives te == tau exactly (sqrt(RN(t t)) = t in binary
+// floating point), i.e. collide<T>'s bits.
+template <typename T>
+__device__ __forceinline__ void collide_les(const T (&fin)[9], T tau, T c, T (&fo)[9], T &rho, T &ux, T &uy)
+{
+    T r, u, v;
+    moments(fin, r, u, v);
+    const T uMax = T(0.35), rhoMin = T(0.5), rhoMax = T(2.0);   // html:344
+    r = (r < rhoMin) ? rhoMin : r;
+    r = (rhoMax < r) ? rhoMax : r;
+    const T spd2 = u * u + v * v;
+    if (spd2 > uMax * uMax) {
+        const T k = uMax / wt_sqrt<T>(spd2);
+        u *= k;
+        v *= k;
+    }
+    T n[9];
+    feq_all(r, u, v, n);
+#pragma unroll
+    for (int k = 0; k < 9; k++) n[k] = fin[k] - n[k];
+    const T pxx = n[1] + n[3] + n[5] + n[6] + n[7] + n[8];
+    const T pyy = n[2] + n[4] + n[5] + n[6] + n[7] + n[8];
+    const T pxy = n[5] - n[6] + n[7] - n[8];
+    const T q = wt_sqrt<T>((pxx * pxx + T(2.0) * (pxy * pxy)) + pyy * pyy);
+    const T te = T(0.5) * (tau + wt_sqrt<T>(tau * tau + (c * q) / r));
+#pragma unroll
+    for (int k = 0; k < 9; k++) fo[k] = fin[k] - n[k] / te;
+    rho = r;
+    ux = u;
+    uy = v;
+}
+
 // binary64 with the four-operation division by tau (see "Division by the relaxation time"): operation for operation collide<double> up to the
 // relaxation; the division is the fast one iff every lane of the wave holds finite populations below 2^100 (else, and with fd.on64 = 0, IEEE).
 __device__ __forceinline__ void collide_fd64(const double (&fin)[9], const FastDiv &fd, double (&fo)[9], double &rho, double &ux, double &uy)

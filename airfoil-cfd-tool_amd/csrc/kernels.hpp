@@ -35,11 +35,12 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // lane.  Correct for any site; used by the tiles that touch the body surface and by ragged
 // tiles.  (A 4-sites-per-lane vector form of this path was measured SLOWER on the 4096^2
 // body case, 213 vs 207 us per step: its 111 VGPRs cost the whole kernel two waves per SIMD.)
+// COLL selects the collision of the interior branch: COLLIDE_BGK, or COLLIDE_LES with the member's constant `cles` (collide_les).
 // --------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int COLL = COLLIDE_BGK>
 __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
-                                             T tau, T U0, bool emit)
+                                             T tau, T U0, bool emit, T cles = T(0.0))
 {
     const long c = (long)i * g.pitch + j;
     const int gi = i + g.gi0;
@@ -67,7 +68,8 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
             const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
             fin[k] = m[src] ? s[opp_of(k) * g.plane + c] : s[k * g.plane + src];
         }
-        collide(fin, tau, out, rho, ux, uy);
+        if constexpr (COLL == COLLIDE_LES) collide_les<T>(fin, tau, cles, out, rho, ux, uy);
+        else collide(fin, tau, out, rho, ux, uy);
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) d[k * g.plane + c] = out[k];

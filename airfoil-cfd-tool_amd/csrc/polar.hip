@@ -20,6 +20,10 @@
 //
 // Mean fields (wtp_enable_mean) are no reduction: k_mean_batch, launched behind the three, streams every member's emitted rho,
 // ux, uy once and adds them and their products to seven planes of running sums, one owner thread per entry.
+//
+// The Smagorinsky subgrid viscosity (wtp_enable_les) is no read-out but another collision: while it is on, wtp_step launches
+// k_step_les_batch, the same step_tile with collide_les in its interior cells and one more value per member, in place of
+// k_step_batch.  A batch that has it off launches k_step_batch with the arguments it always had.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -106,6 +110,9 @@ struct wtp_batch {
     uint8_t *tiles = nullptr;
     void *params = nullptr;              // [B][2] of T: tau, U0 of the last stepping call
     std::vector<double> params_host;     // ... as the caller gave them (doubles), to skip unchanged uploads
+    // Smagorinsky subgrid viscosity (wtp_enable_les); the pointer is null until then
+    bool les = false;
+    void *les_c = nullptr;               // [B] of T: c = 18 sqrt(2) Cs^2 of every member
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -161,6 +168,26 @@ __global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T 
     const T tau = params[2 * m], U0 = params[2 * m + 1];
     step_tile<T, EMIT, LOADMODE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask, tiles + m * ms.tiles,
                                  tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane);
+}
+
+// The same step with the Smagorinsky collision (collide_les, d2q9.hpp) in every member's interior fluid cells: k_step_batch's grid,
+// walk and arguments, and cles[m] = (T)(18 sqrt(2) Cs[m]^2) beside the member's tau and U0.  A member with cles = 0 computes
+// k_step_batch's bits.  A kernel of its own name, so that a batch with the model off runs the code object it always ran.
+template <typename T, bool EMIT, int LOADMODE>
+__global__ __launch_bounds__(256) void k_step_les_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                        const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                        int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                        const T *__restrict__ cles, int rev)
+{
+    const int lane = threadIdx.x & 63;
+    const long ntiles = (long)g.nxl * tiles_per_col;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= ntiles) return;
+    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const T tau = params[2 * m], U0 = params[2 * m + 1], c = cles[m];
+    step_tile<T, EMIT, LOADMODE, false, COLLIDE_LES>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                     tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane,
+                                                     0, 0, 0, c);
 }
 
 // "The last block of a member finishes the sum": called by every thread of a block once the block's partials of member m are
@@ -457,7 +484,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -536,7 +563,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -767,9 +794,15 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
         const int rev = (int)(b->steps_done & 1);
-        const auto k_step = emit ? k_step_batch<T, true, WT_LOADMODE> : k_step_batch<T, false, WT_LOADMODE>;
-        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                           b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
+        if (b->les) {
+            const auto k_step = emit ? k_step_les_batch<T, true, WT_LOADMODE> : k_step_les_batch<T, false, WT_LOADMODE>;
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, rev);
+        } else {
+            const auto k_step = emit ? k_step_batch<T, true, WT_LOADMODE> : k_step_batch<T, false, WT_LOADMODE>;
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
+        }
         HIP_TRY(hipGetLastError());
         b->cur = 1 - b->cur;
         b->steps_done = n;
@@ -805,6 +838,33 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
     }
     WT_TRY(upload_params<double>(b, tau, u0));
     return step_impl<double>(b, nsteps, sample_every);
+}
+
+// ------------------------------------------------------------------------------------------
+// Smagorinsky subgrid viscosity
+// ------------------------------------------------------------------------------------------
+// c = 18 sqrt(2) Cs^2 of every member: the product formed left to right in double, then rounded to T once.
+template <typename T>
+static int upload_les(wtp_batch *b, const double *cs)
+{
+    std::vector<T> v((size_t)b->members);
+    for (size_t m = 0; m < v.size(); m++) v[m] = (T)(18.0 * std::sqrt(2.0) * cs[m] * cs[m]);
+    if (!b->les_c) HIP_TRY(hipMalloc(&b->les_c, v.size() * sizeof(T)));
+    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
+    HIP_TRY(hipMemcpy(b->les_c, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return WT_OK;
+}
+
+extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
+{
+    WT_TRY(check_batch(b));
+    if (!cs) { b->les = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(cs[m]) || cs[m] < 0.0 || cs[m] > 0.5) return fail(WT_ERR_ARG, "cs[%d] must be finite and in [0, 0.5]", m);
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? upload_les<float>(b, cs) : upload_les<double>(b, cs));
+    b->les = true;
+    return WT_OK;
 }
 
 // ------------------------------------------------------------------------------------------

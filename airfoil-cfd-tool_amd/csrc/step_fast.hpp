@@ -154,11 +154,12 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // by reading what the previous step wrote last — still resident in the 256 MB Infinity Cache.
 // WIN: the tile belongs to a grid whose tiles start every `stride` rows (tile height stays 64*N) and
 // only rows in [st_lo, st_hi) are stored — the window-aligned zone passes of step_fused.hpp.
-template <typename T, bool EMIT, int LOADMODE, bool WIN = false>
+// COLL: the collision of interior fluid cells, COLLIDE_BGK or COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp).
+template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK>
 __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
-                                          int stride = 0, int st_lo = 0, int st_hi = 0)
+                                          int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0))
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
@@ -178,7 +179,7 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
 #pragma unroll 1
         for (int v = 0; v < N; v++) {
             const int j = row0 + v * 64 + lane;
-            if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) site_general<T>(s, d, macro, m, g, i, j, tau, U0, EMIT);
+            if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
         }
         return;
     }
@@ -216,7 +217,8 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             T a[9], o[9], rho, ux, uy;
 #pragma unroll
             for (int k = 0; k < 9; k++) a[k] = fin[k].v[v];
-            collide<T>(a, tau, o, rho, ux, uy);
+            if constexpr (COLL == COLLIDE_LES) collide_les<T>(a, tau, cles, o, rho, ux, uy);
+            else collide<T>(a, tau, o, rho, ux, uy);
             const int j = j0 + v;
             const bool far = (j == 0) || (j == g.ny - 1);   // top / bottom rows
 #pragma unroll

@@ -10,6 +10,8 @@ chordwise surface pressure; with the momentum exchange enabled (``PolarEngine.en
 ``run_polar(total_forces=True)``) a second force read-out that holds pressure and friction together; with the mean fields
 enabled (``PolarEngine.enable_mean_fields``, ``run_polar(mean_fields=True)``) the time-mean flow field of every angle and the
 fluctuation about it (:func:`mean_flow`: Reynolds stresses, pressure r.m.s.), from seven running sums kept on the device.
+At airfoil Reynolds numbers, where tau falls to within 1e-3 of 0.5, the Smagorinsky subgrid viscosity
+(``PolarEngine.enable_les``, ``run_polar(les=0.1)``) keeps the members off the stability net.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -39,6 +41,7 @@ EXPORTS = (
     "wtp_enable_loads", "wtp_history_moment", "wtp_moment", "wtp_surface",
     "wtp_enable_mex", "wtp_history_mex", "wtp_mex",
     "wtp_enable_mean", "wtp_mean_sums",
+    "wtp_enable_les",
 )
 
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
@@ -84,6 +87,7 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_mex": ([B, dp, dp, dp, ip], c_int),
         "wtp_enable_mean": ([B], c_int),
         "wtp_mean_sums": ([B, c_int, ip, dp, dp, dp, dp, dp, dp, dp], c_int),
+        "wtp_enable_les": ([B, dp], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -123,6 +127,7 @@ class PolarEngine:
         self.loads_enabled = False
         self.mex_enabled = False
         self.mean_enabled = False
+        self.les_enabled = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -245,6 +250,18 @@ class PolarEngine:
         _check(self._lib.wtp_mean_sums(self._b, int(member), _ip(n), *(_dp(out[k]) for k in MEAN_SUMS)))
         return {"n": int(n[0]), **out}
 
+    def enable_les(self, cs) -> None:
+        """Collide with a Smagorinsky eddy viscosity from the next step on (wt_polar.h): cs is the Smagorinsky constant, one value
+        or [B], each in [0, 0.5]; a member with cs = 0 stays a BGK member, bit for bit.  None switches the model off again.  The
+        flow state, the history and every running sum are kept; independent of the read-outs."""
+        if cs is None:
+            _check(self._lib.wtp_enable_les(self._b, None))
+            self.les_enabled = False
+            return
+        v = _f64(cs, self.members)
+        _check(self._lib.wtp_enable_les(self._b, _dp(v)))
+        self.les_enabled = True
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -318,6 +335,7 @@ class PolarResult:
     u0: float
     warmup_steps: int
     sample_every: int
+    les: Optional[float] = None          # the Smagorinsky constant of every member (None: plain BGK)
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -428,7 +446,7 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False) -> PolarResult:
+              total_forces: bool = False, mean_fields: bool = False, les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -439,7 +457,10 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     sweep then runs, and costs, what it did without it; every other value is the same bits either way.
     `mean_fields`: also keep the running sums of rho, ux, uy and their products over the samples on the device and attach
     mean_flow() of each angle as PolarPoint.mean: the time-mean field, the Reynolds stresses, the pressure r.m.s.  The warm-up
-    takes no sample, so nothing of it enters the mean.  Off by default, with the same guarantees as `total_forces`."""
+    takes no sample, so nothing of it enters the mean.  Off by default, with the same guarantees as `total_forces`.
+    `les`: the Smagorinsky constant (0.1 to 0.17 are the usual values; at most 0.5) of a subgrid eddy viscosity in every member's
+    collision, from the first warm-up step on (PolarEngine.enable_les).  For sweeps at airfoil Reynolds numbers (`re` of 20 000
+    and above), where plain BGK runs into the stability net and the angle fails.  None, the default, is plain BGK."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -447,6 +468,10 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         raise ValueError("give tau or re, not both")
     if samples < 1 or sample_every < 1:
         raise ValueError("samples and sample_every must be >= 1")
+    if les is not None:
+        les = float(les)
+        if not math.isfinite(les) or les < 0.0 or les > 0.5:
+            raise ValueError(f"les must be a finite Smagorinsky constant in [0, 0.5], got {les!r}")
     nx, ny, u0 = int(nx), int(ny), float(u0)
     tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
     if warmup_steps is None:
@@ -463,6 +488,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_momentum_exchange(*quarter_chord(nx, ny))
         if mean_fields:
             eng.enable_mean_fields()
+        if les is not None:
+            eng.enable_les(les)
         if warmup_steps:
             eng.step(warmup_steps, tau, u0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
@@ -477,7 +504,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               for m, a in enumerate(alphas)]
     for p, mean in zip(points, means):
         p.mean = mean
-    return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every))
+    return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

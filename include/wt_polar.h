@@ -150,6 +150,34 @@ WTP_API int wtp_enable_mean(wtp_batch *b);
  * NULL.  WT_ERR_ARG for a member outside the batch, before any device call; WT_ERR_STATE while the read-out is not enabled. */
 WTP_API int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy, double *rho2, double *ux2,
                           double *uy2, double *uxuy);
+/*
+ * Smagorinsky subgrid viscosity: an eddy viscosity computed per site from the non-equilibrium stress (Hou et al. 1996), for
+ * sweeps at Reynolds numbers where tau comes so close to 0.5 that plain BGK is held together by the stability net alone.
+ * It is no read-out but another collision, per member and opt-in.  Definition, for an interior fluid cell only (solid cells,
+ * the inlet column, the top and bottom rows and the outlet column are untouched): let fin[0..8] be the post-stream
+ * populations, rho, ux, uy the clamped moments and eq[k] = feq_k(rho, ux, uy), all exactly as in the BGK step; T is the
+ * batch's dtype.  Every operation below rounds once in T, evaluation is left to right as written with no contraction,
+ * division and square root are IEEE:
+ *     n[k] = fin[k] - eq[k]                                    k = 0..8
+ *     pxx  = n[1] + n[3] + n[5] + n[6] + n[7] + n[8]
+ *     pyy  = n[2] + n[4] + n[5] + n[6] + n[7] + n[8]
+ *     pxy  = n[5] - n[6] + n[7] - n[8]
+ *     q    = sqrt((pxx*pxx + 2*(pxy*pxy)) + pyy*pyy)
+ *     te   = 0.5 * (tau + sqrt(tau*tau + (c*q)/rho))
+ *     fo[k] = fin[k] - n[k] / te
+ * with c = (T)(18.0 * sqrt(2.0) * cs * cs), the product formed left to right in double on the host and then rounded to T;
+ * cs is the member's Smagorinsky constant.  The stored (rho, ux, uy) are the clamped pre-collision moments, as without the
+ * model.  With cs = 0, te == tau exactly (sqrt(RN(t*t)) = t), so such a member is bit-identical to a BGK member.
+ *
+ * wtp_enable_les switches the model on.  cs: [B], each finite and 0 <= cs <= 0.5, else WT_ERR_ARG before any device call
+ * (and the batch is left as it was).  cs == NULL switches it off again: the following steps are BGK, with the same bits as
+ * in a batch that never enabled it.  Either takes effect from the next wtp_step.  The flow state, the step count, the
+ * history and every running sum are kept.  It is independent of wtp_enable_loads, wtp_enable_mex and wtp_enable_mean: those
+ * read-outs stay defined on whatever state the step produced.  A batch that never calls it launches the kernels it always
+ * launched.  An LES member has no libwindtunnel twin: wt_step has no such collision, so the bit identity with a handle
+ * (top of this file) holds for members with cs = 0 and for batches with the model off only.
+ */
+WTP_API int wtp_enable_les(wtp_batch *b, const double *cs);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

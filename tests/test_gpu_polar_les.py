@@ -1,0 +1,295 @@
+"""GPU: the Smagorinsky subgrid viscosity of batched sweeps (k_step_les_batch, wtp_enable_les) against its definition in NumPy
+(tests/_les_reference.py).
+
+There is no tolerance on the state: the kernel and the reference round every operation of the collision once, in the same order,
+so populations and macroscopic fields are the same bits.  The read-outs on top of an LES state are held to their own features'
+checks: bits for the surface and mean sums and for a history row against the on-demand call, the derived summation bounds of
+_loads_reference / _mex_reference for the moment and the momentum exchange.  The two stabilisation tests assert facts measured
+on the reference (tests/test_polar_les_host.py), not tolerances.
+"""
+import ctypes
+import functools
+import math
+
+import numpy as np
+import pytest
+
+from conftest import bits_equal
+import lbm_numpy
+import _les_reference as les
+from _loads_reference import loads_reference, surface_sums
+from _mean_reference import SUMS, accumulate
+from _mex_reference import mex_reference
+from test_gpu_polar_mean import _block_masks
+
+pytestmark = pytest.mark.gpu
+
+WT_ERR_ARG = -1
+STEPS = 60
+EVERY = 12
+
+# Members: (shape, aoa, tau, u0, cs).  The low-tau ones (tau - 0.5 of 1e-3 .. 1e-2) are where the model acts; cs = 0 members are BGK.
+# The lattices are chosen by step_tile's classes: 96x48 has ragged tiles only (site_general); 40x300 and 37x299 fp32 a FAST tile of
+# 256 rows and a ragged one per column (and an odd NY); 24x140 fp64 a FAST tile of 128 rows and a ragged one.
+CASES = {
+    "96x48-f32": (96, 48, "float32", [("naca0012", 10.0, 0.5008, 0.08, 0.17), ("naca2412", 6.0, 0.9, 0.03, 0.1), ("naca4412", -4.0, 0.503, 0.06, 0.0)]),
+    "40x300-f32": (40, 300, "float32", [("block", 0.0, 0.5008, 0.08, 0.17), ("block", 0.0, 0.52, 0.05, 0.0), ("block", 0.0, 0.9, 0.03, 0.1)]),
+    "37x299-f32": (37, 299, "float32", [("block", 0.0, 0.5008, 0.08, 0.17), ("block", 0.0, 0.6, 0.06, 0.1), ("block", 0.0, 0.502, 0.03, 0.0)]),
+    "24x140-f64": (24, 140, "float64", [("block", 0.0, 0.5008, 0.08, 0.1), ("block", 0.0, 0.9, 0.03, 0.17), ("block", 0.0, 0.51, 0.06, 0.0)]),
+}
+LOW_TAU = 0.501           # "low-tau member": tau below this and cs > 0
+
+
+def _masks(nx, ny, members):
+    import airfoil_cfd_tool_amd as pkg
+    if members[0][0] == "block":
+        return _block_masks(nx, ny, len(members))
+    return np.stack([pkg.geometry.build_geometry(nx, ny, a, None, s).mask for s, a, _, _, _ in members])
+
+
+def _params(members):
+    return [m[2] for m in members], [m[3] for m in members], [m[4] for m in members]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name):
+    """Per member: (f, (rho, ux, uy), te) of _les_reference after STEPS steps from equilibrium, and the BGK oracle's f."""
+    nx, ny, dtype, members = CASES[name]
+    masks = _masks(nx, ny, members)
+    out = []
+    for mask, (_, _, tau, u0, cs) in zip(masks, members):
+        f, macro, te = les.run(mask, STEPS, tau, u0, les.les_constant(cs, dtype), np.dtype(dtype))
+        bgk, _ = lbm_numpy.run(mask, STEPS, tau, u0, np.dtype(dtype))
+        for a in (f, te, bgk, *macro):
+            a.setflags(write=False)
+        out.append((f, macro, te, bgk))
+    return masks, out
+
+
+def _interior_fluid(mask):
+    inner = np.zeros(mask.shape, bool)
+    inner[1:-1, 1:-1] = True
+    return inner & (mask == 0)
+
+
+# ---- 1. bit identity ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(CASES))
+def test_state_is_the_references_bits(pkg, name):
+    nx, ny, dtype, members = CASES[name]
+    tau, u0, cs = _params(members)
+    masks, ref = _reference(name)
+    # the comparison is not vacuous, on the reference itself
+    low = [m for m, (_, _, t, _, c) in enumerate(members) if t < LOW_TAU and c > 0]
+    assert low
+    for m in low:
+        f, _, te, bgk = ref[m]
+        cells = _interior_fluid(masks[m])
+        acts = float((te[cells] != te.dtype.type(tau[m])).mean())
+        differs = float((f != bgk).any(axis=0)[cells].mean())
+        print(f"{name} member {m}: te != tau at {acts:.3f} of {int(cells.sum())} interior fluid cells, max te {float(te.max()):.6f}; "
+              f"populations differ from BGK's at {differs:.3f}")
+        # te is compared at every interior fluid cell.  The populations can differ from BGK's only where a disturbance has arrived:
+        # on the tall lattices the sound front alone, 60 / sqrt(3) rows either side of the 31-row block, covers 0.33 of the rows
+        # after 60 steps (and nothing travels further than 60 rows: at most 0.51), so a quarter of the cells is what is asked.
+        assert acts > 0.5 and differs > 0.25
+    for m, (_, _, t, _, c) in enumerate(members):
+        if c == 0:
+            assert ref[m][0].tobytes() == ref[m][3].tobytes()             # a cs = 0 member of the reference is the BGK oracle
+    with pkg.PolarEngine(nx, ny, len(members), dtype=dtype) as b:
+        b.set_masks(masks)
+        b.init_equilibrium(u0)
+        b.enable_les(cs)
+        assert b.les_enabled
+        b.step(STEPS, tau, u0)
+        for m in range(len(members)):
+            f, macro = b.read_f(m), b.read_macro(m)
+            want_f, want_macro, _, _ = ref[m]
+            bad = int((f.view(np.uint8) != want_f.view(np.uint8)).reshape(9, ny, -1).any(axis=(0, 2)).sum())
+            assert bits_equal(f, want_f), (name, m, bad, "rows differ")
+            for got, want, what in zip(macro, want_macro, ("rho", "ux", "uy")):
+                assert bits_equal(got, want), (name, m, what)
+        assert b.clamp_events()[0].tolist() == [0] * len(members)
+
+
+# ---- 2. cs = 0 is BGK --------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["40x300-f32", "24x140-f64"])
+def test_a_member_with_cs_zero_is_a_bgk_member(pkg, name):
+    nx, ny, dtype, members = CASES[name]
+    tau, u0, cs = _params(members)
+    masks = _masks(nx, ny, members)
+    zero = cs.index(0.0)
+    state = {}
+    for on in (True, False):
+        with pkg.PolarEngine(nx, ny, len(members), dtype=dtype) as b:
+            b.set_masks(masks)
+            b.init_equilibrium(u0)
+            if on:
+                b.enable_les(cs)
+            assert b.les_enabled is on
+            b.step(STEPS, tau, u0)
+            state[on] = [(b.read_f(m), b.read_macro(m)) for m in range(len(members))]
+    (f_on, macro_on), (f_off, macro_off) = state[True][zero], state[False][zero]
+    assert f_on.tobytes() == f_off.tobytes()
+    assert all(a.tobytes() == c.tobytes() for a, c in zip(macro_on, macro_off))
+    other = 1 - zero if zero < 2 else 0
+    assert state[True][other][0].tobytes() != state[False][other][0].tobytes()      # (while a member with cs > 0 is not)
+
+
+# ---- 3. off again ------------------------------------------------------------------------------
+def test_switching_off_returns_to_bgk_and_keeps_the_history(pkg, oracle_np):
+    nx, ny, dtype, members = CASES["96x48-f32"]
+    tau, u0, cs = _params(members)
+    masks = _masks(nx, ny, members)
+    B = len(members)
+    with pkg.PolarEngine(nx, ny, B, dtype=dtype, history_cap=8) as b:
+        b.set_masks(masks)
+        b.init_equilibrium(u0)
+        b.enable_les(cs)
+        b.step(24, tau, u0, sample_every=EVERY)
+        first = b.history()
+        at_switch = [b.read_f(m) for m in range(B)]
+        b.enable_les(None)
+        assert not b.les_enabled
+        assert list(b.history()["step"]) == [12, 24]
+        b.step(24, tau, u0, sample_every=EVERY)
+        h = b.history()
+        assert list(h["step"]) == [12, 24, 36, 48]                          # the step count went on, the rows stayed
+        for k in ("fx", "fy", "surf", "rev"):
+            assert h[k][:2].tobytes() == first[k].tobytes(), k
+        for m in range(B):
+            want_f, want_macro = oracle_np.run(masks[m], 24, tau[m], u0[m], np.float32, f=at_switch[m])
+            assert bits_equal(b.read_f(m), want_f), m
+            assert all(bits_equal(a, c) for a, c in zip(b.read_macro(m), want_macro)), m
+        # and the first half was not BGK: the low-tau member's state at the switch is the LES reference's, not the oracle's
+        f_les, _, _ = les.run(masks[0], 24, tau[0], u0[0], les.les_constant(cs[0], np.float32))
+        f_bgk, _ = oracle_np.run(masks[0], 24, tau[0], u0[0], np.float32)
+        assert bits_equal(at_switch[0], f_les) and not bits_equal(at_switch[0], f_bgk)
+        # on again with other constants: takes effect from the next step, the state is kept
+        b.enable_les(0.1)
+        assert b.les_enabled and bits_equal(b.read_f(1), oracle_np.run(masks[1], 24, tau[1], u0[1], np.float32, f=at_switch[1])[0])
+
+
+# ---- 4. the read-outs stand on the new state ---------------------------------------------------
+def test_readouts_are_defined_on_the_les_state(pkg):
+    nx, ny, calls = 160, 80, 6
+    members = [("naca0012", 10.0, 0.5008, 0.06, 0.1), ("naca2412", 6.0, 0.51, 0.05, 0.17), ("naca4412", 11.0, 0.7, 0.07, 0.0)]
+    tau, u0, cs = _params(members)
+    masks = _masks(nx, ny, members)
+    B = len(members)
+    xr, yr = [0.3641 * nx + 1.7 * m for m in range(B)], [0.5 * ny - 0.85 * m - 3.3 for m in range(B)]
+    macros, fs, forces = [[] for _ in range(B)], [[] for _ in range(B)], []
+    with pkg.PolarEngine(nx, ny, B, history_cap=calls) as b:
+        b.set_masks(masks)
+        b.init_equilibrium(u0)
+        b.enable_loads(xr, yr)
+        b.enable_momentum_exchange(xr, yr)
+        b.enable_mean_fields()
+        b.enable_les(cs)
+        for _ in range(calls):
+            b.step(EVERY, tau, u0, sample_every=EVERY)
+            forces.append(b.forces())
+            for m in range(B):
+                macros[m].append(b.read_macro(m))
+                fs[m].append(b.read_f(m))
+        h = b.history()
+        surface = [b.surface(m) for m in range(B)]
+        sums = [b.mean_sums(m) for m in range(B)]
+    assert list(h["step"]) == [EVERY * (k + 1) for k in range(calls)]
+    for r in range(calls):                                                  # a history row is wtp_forces on that state
+        for k, v in zip(("fx", "fy", "surf", "rev"), forces[r]):
+            assert h[k][r].tobytes() == v.tobytes(), (r, k)
+    # the state under the read-outs is the model's: member 0 is the LES reference, and not the BGK oracle
+    f_les, _, te = les.run(masks[0], EVERY, tau[0], u0[0], les.les_constant(cs[0], np.float32))
+    assert bits_equal(fs[0][0], f_les) and (te != np.float32(tau[0])).any()
+    assert not bits_equal(fs[0][0], lbm_numpy.run(masks[0], EVERY, tau[0], u0[0], np.float32)[0])
+    worst = [0.0, 0.0, 0.0, 0.0]
+    for m in range(B):
+        for r in range(calls):
+            lo = loads_reference(macros[m][r][0], masks[m], xr[m], yr[m])
+            assert lo.n == int(h["surf"][r, m]) > 0
+            mx = mex_reference(fs[m][r], masks[m], xr[m], yr[m])
+            assert mx.links == int(h["links"][r, m]) > 100
+            for q, (got, want, bound) in enumerate(((h["mz"][r, m], lo.mz, lo.mz_bound), (h["fx_mex"][r, m], mx.fx, mx.fx_bound),
+                                                    (h["fy_mex"][r, m], mx.fy, mx.fy_bound), (h["mz_mex"][r, m], mx.mz, mx.mz_bound))):
+                err = abs(got - want)
+                worst[q] = max(worst[q], err / bound)
+                assert err <= bound, (m, r, q, got, want, bound)
+        su, sl, nu, nl = surface_sums([mac[0] for mac in macros[m]], masks[m])
+        assert np.array_equal(surface[m]["n_upper"], nu) and np.array_equal(surface[m]["n_lower"], nl) and int((nu > 0).sum()) > 60
+        assert bits_equal(surface[m]["rho_upper"], su) and bits_equal(surface[m]["rho_lower"], sl)
+        want = accumulate(macros[m])
+        assert sums[m]["n"] == want["n"] == calls
+        for k in SUMS:
+            assert bits_equal(sums[m][k], want[k]), (m, k)
+    print(f"worst |x - ref| / bound: Mz {worst[0]:.3g}, mex fx {worst[1]:.3g}, fy {worst[2]:.3g}, mz {worst[3]:.3g}; surface and mean sums bit-identical")
+
+
+# ---- 5. it stabilises --------------------------------------------------------------------------
+def test_the_model_keeps_re_20000_off_the_stability_net(pkg):
+    """160x80 fp32, NACA 0012 at 10 deg, U0 0.06, Re 20 000: on the reference BGK reports clamp events at step 800 and the model with
+    Cs = 0.1 none at any 50th step to 1500 (tests/test_polar_les_host.py).  The batch computes the reference's bits, so the same
+    holds of its members: cs = 0 in member 0, 0.1 in member 1."""
+    nx, ny, u0 = 160, 80, 0.06
+    tau = 0.5 + 3 * 0.06 * (160 / 1.84) / 20000
+    mask = pkg.geometry.build_geometry(nx, ny, 10.0, None, "naca0012").mask
+    events = []
+    with pkg.PolarEngine(nx, ny, 2) as b:
+        b.set_masks(np.stack([mask, mask]))
+        b.init_equilibrium(u0)
+        b.enable_les([0.0, 0.1])
+        for _ in range(30):
+            b.step(50, tau, u0)
+            rho_ev, u_ev = b.clamp_events()
+            events.append(((int(rho_ev[0]), int(u_ev[0])), (int(rho_ev[1]), int(u_ev[1]))))
+        f = b.read_f(1)
+    first = next((50 * (k + 1) for k, e in enumerate(events) if e[0] != (0, 0)), None)
+    print(f"member 0 (cs 0): first clamp events at step {first}, {events[-1][0]} at step 1500; member 1 (cs 0.1): {sorted(set(e[1] for e in events))}")
+    assert first is not None and first <= 800
+    assert all(e[1] == (0, 0) for e in events)
+    assert np.isfinite(f).all()
+
+
+# ---- 6. run_polar ------------------------------------------------------------------------------
+def test_run_polar_at_re_20000_converges_with_the_model_only(pkg):
+    kw = dict(shape="naca0012", nx=160, ny=80, re=20000, warmup_steps=1200, samples=16)
+    on = pkg.run_polar([10.0], les=0.1, **kw)
+    off = pkg.run_polar([10.0], **kw)
+    assert on.les == 0.1 and off.les is None and on.tau == off.tau == 0.5 + 3 * 0.06 * (160 / 1.84) / 20000
+    p = on.points[0]
+    row = pkg.polar_rows(on)[0]
+    print(f"les 0.1: {row}; clamp events without it: {off.points[0].clamp_events}")
+    assert p.converged and p.clamp_events == (0, 0) and p.samples == 16
+    assert all(math.isfinite(v) for v in (p.cl_mean, p.cd_mean, p.cm_mean))
+    assert row["Status"] == "✅ Converged" and all(isinstance(row[k], float) for k in ("CL", "CD", "Cm"))
+    assert p.cl_mean > 0 and p.cd_mean > 0                                  # (a lifting airfoil at 10 degrees)
+    assert not off.points[0].converged
+    assert pkg.polar_rows(off)[0]["Status"] == "❌ Failed"
+
+
+# ---- 7. argument errors ------------------------------------------------------------------------
+def test_bad_constants_are_argument_errors_and_leave_the_batch_usable(pkg, oracle_np):
+    nx, ny = 96, 48
+    mask = pkg.geometry.build_geometry(nx, ny, 6.0, None, "naca2412").mask
+    tau, u0 = 0.52, 0.06
+    with pkg.PolarEngine(nx, ny, 2) as b:
+        b.set_masks(np.stack([mask, mask]))
+        b.init_equilibrium(u0)
+        for bad in (-0.01, 0.51, float("nan")):
+            with pytest.raises(pkg.WTError) as ei:
+                b.enable_les([0.1, bad])
+            assert ei.value.code == WT_ERR_ARG and "cs[1]" in str(ei.value)
+            assert not b.les_enabled
+        cs = np.array([0.1, float("inf")])
+        assert b._lib.wtp_enable_les(b._b, cs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))) == WT_ERR_ARG
+        b.step(10, tau, u0)                                                 # still a BGK batch
+        assert bits_equal(b.read_f(1), oracle_np.run(mask, 10, tau, u0, np.float32)[0])
+        b.enable_les([0.5, 0.0])                                            # the bounds themselves are allowed
+        b.step(10, tau, u0)
+        with pytest.raises(pkg.WTError):
+            b.enable_les([0.1, -1.0])
+        assert b.les_enabled                                                # a refused call changes nothing
+        b.step(10, tau, u0)
+        f = oracle_np.run(mask, 10, tau, u0, np.float32)[0]
+        f = les.run(mask, 20, tau, u0, les.les_constant(0.5, np.float32), f=f)[0]
+        assert bits_equal(b.read_f(0), f)
+        assert bits_equal(b.read_f(1), oracle_np.run(mask, 30, tau, u0, np.float32)[0])

@@ -25,6 +25,13 @@ The same protocol for the mean fields (wtp_enable_mean: one k_mean_batch behind 
 are on in both variants.  The line also gives the bytes one sample moves (3 sizeof(T) + 2 * 56 per site and member: derived, not
 measured) and what the added time per sample makes of them against 8 TB/s.
 
+    python tools/polar_bench.py --les CS [--repeats 5] [the options of the first form]
+
+The batched step with the Smagorinsky subgrid viscosity (wtp_enable_les, Smagorinsky constant CS in every member): k_step_les_batch in
+place of k_step_batch.  The line gives `repeats` timings of the same window and their median; without --les the same repeats time the
+BGK step, so that two lines compare.  No sequential leg: a single handle has no such collision.  With --loads / --mex / --mean the
+model is on in both variants of those protocols.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -49,16 +56,25 @@ def _masks(nx, ny, b):
     return np.stack([pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412").mask for a in alphas])
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks):
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1):
+    """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK)."""
+    out = []
     with pkg.PolarEngine(nx, ny, b) as eng:
         eng.set_masks(masks)
         eng.init_equilibrium(U0)
+        if les is not None:
+            eng.enable_les(les)
         eng.step(warmup, TAU, U0)
         eng.sync()
-        t0 = time.perf_counter()
-        eng.step(steps, TAU, U0)
-        eng.sync()
-        return time.perf_counter() - t0
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            eng.step(steps, TAU, U0)
+            eng.sync()
+            out.append(time.perf_counter() - t0)
+    return out
+
+
+LES = None      # --les: the Smagorinsky constant the sampled protocols run with (None: BGK)
 
 
 def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
@@ -73,6 +89,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.enable_momentum_exchange(*pkg.polar.quarter_chord(nx, ny))
         if mean:
             eng.enable_mean_fields()
+        if LES is not None:
+            eng.enable_les(LES)
         eng.step(warmup - warmup % every, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -187,12 +205,18 @@ def main():
     ap.add_argument("--loads", action="store_true", help="the sampled step with and without surface loads")
     ap.add_argument("--mex", action="store_true", help="the sampled step with and without the momentum-exchange readout")
     ap.add_argument("--mean", action="store_true", help="the sampled step with and without the mean fields")
+    ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
-    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
     a = ap.parse_args()
+    plain = not (a.mean or a.mex or a.loads)
+    if a.repeats is None:
+        a.repeats = 1 if plain else 7
     if a.lib:
         pkg.polar.load_polar_library(a.lib)
+    global LES
+    LES = a.les
     if a.mean:
         return mean_cost(a)
     if a.mex:
@@ -204,14 +228,18 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            t = bench_batch(nx, ny, b, a.steps, a.warmup, masks)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats)
+            t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
             bytes_step = b * sites * (72 + 12 / a.steps)
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if not a.no_sequential:
+            if a.les is not None or a.repeats > 1:
+                line["les"] = a.les
+                line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
+            if not a.no_sequential and a.les is None:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
