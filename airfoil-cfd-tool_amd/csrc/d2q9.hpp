@@ -372,6 +372,31 @@ __device__ __forceinline__ void collide_les(const T (&fin)[9], T tau, T c, T (&f
     uy = v;
 }
 
+// What a step kernel does with a population whose source cell is solid: half-way bounce-back (the page's), or linear interpolated
+// bounce-back with a wall distance per link (wall_incoming).
+enum : int { WALL_HALFWAY = 0, WALL_INTERP = 1 };
+
+// Linear interpolated bounce-back (Bouzidi, Firdaouss and Lallemand 2001; include/wt_polar.h "Interpolated bounce-back").  A link is an
+// interior fluid cell x and a direction k whose neighbour x + e_k is solid; q in (0, 1] is the fraction of the link at which it crosses
+// the true surface.  The incoming population fin[opp(k)] of x, which half-way bounce-back sets to a = s[k](x), becomes, with
+// g = s[k](x - e_k), h = s[opp(k)](x) and s the source lattice,
+//   two = 2*q
+//   q <  0.5:  fin = two*a + (1 - two)*g      if x - e_k is not solid, else fin = a
+//   q >= 0.5:  inv = 1/two;  fin = inv*a + (1 - inv)*h
+// in the arithmetic contract of this file (left to right as written, one rounding per operation, IEEE division).  With q = 0.5, two = 1,
+// so fin equals a as a number.  g and h are passed by address: each is loaded only on the branch that uses it.
+template <typename T>
+__device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bool g_solid, const T *__restrict__ h)
+{
+    const T two = T(2.0) * q;
+    if (q < T(0.5)) {
+        if (g_solid) return a;
+        return two * a + (T(1.0) - two) * *g;
+    }
+    const T inv = T(1.0) / two;
+    return inv * a + (T(1.0) - inv) * *h;
+}
+
 // binary64 with the four-operation division by tau (see "Division by the relaxation time"): operation for operation collide<double> up to the
 // relaxation; the division is the fast one iff every lane of the wave holds finite populations below 2^100 (else, and with fd.on64 = 0, IEEE).
 __device__ __forceinline__ void collide_fd64(const double (&fin)[9], const FastDiv &fd, double (&fo)[9], double &rho, double &ux, double &uy)

@@ -36,11 +36,14 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // tiles.  (A 4-sites-per-lane vector form of this path was measured SLOWER on the 4096^2
 // body case, 213 vs 207 us per step: its 111 VGPRs cost the whole kernel two waves per SIMD.)
 // COLL selects the collision of the interior branch: COLLIDE_BGK, or COLLIDE_LES with the member's constant `cles` (collide_les).
+// WALL selects what the interior branch does with a population whose source cell is solid: WALL_HALFWAY, or WALL_INTERP with the wall
+// distances `wq` (wall_incoming, d2q9.hpp): eight planes laid out like population planes 1..8, plane k - 1 holding q of direction k
+// at the link's fluid cell; `wq` points at column 0 of plane 0, as `s` does.  q is read only on lanes whose source cell is solid.
 // --------------------------------------------------------------------------------------
-template <typename T, int COLL = COLLIDE_BGK>
+template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY>
 __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
-                                             T tau, T U0, bool emit, T cles = T(0.0))
+                                             T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr)
 {
     const long c = (long)i * g.pitch + j;
     const int gi = i + g.gi0;
@@ -63,10 +66,28 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
         feq_all(rho, ux, uy, out);
     } else {                                                       // html:324-359 interior fluid
         T fin[9];
+        [[maybe_unused]] unsigned wall = 0;                        // WALL_INTERP: bit k, fin[k]'s source cell is solid
 #pragma unroll
         for (int k = 0; k < 9; k++) {
             const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
+            if constexpr (WALL == WALL_INTERP) wall |= k > 0 && m[src] ? 1u << k : 0u;
             fin[k] = m[src] ? s[opp_of(k) * g.plane + c] : s[k * g.plane + src];
+        }
+        if constexpr (WALL == WALL_INTERP) {
+            // The gather above is the half-way one, nine loads in flight together, and on a link it has fetched a = s[o](x), o = opp(k),
+            // the link's direction: x + e_o = src is solid and x - e_o = `behind` is the cell the link comes from.  Waves that touch
+            // no wall (nearly all) skip the correction on one ballot; with a branch per direction inside the gather instead, every
+            // load waited for the one before it and the step took twice as long (profiles/polar_ibb_cost.txt).
+            if (__ballot(wall != 0u) != 0ULL) {
+#pragma unroll
+                for (int k = 1; k < 9; k++) {
+                    if (!(wall >> k & 1u)) continue;
+                    const int o = opp_of(k);
+                    const long behind = c + (long)ex_of(k) * g.pitch + ey_of(k);
+                    fin[k] = wall_incoming<T>(wq[(o - 1) * g.plane + c], fin[k], s + o * g.plane + behind, m[behind] != 0,
+                                              s + k * g.plane + c);
+                }
+            }
         }
         if constexpr (COLL == COLLIDE_LES) collide_les<T>(fin, tau, cles, out, rho, ux, uy);
         else collide(fin, tau, out, rho, ux, uy);

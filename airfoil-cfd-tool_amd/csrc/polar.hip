@@ -24,6 +24,11 @@
 // The Smagorinsky subgrid viscosity (wtp_enable_les) is no read-out but another collision: while it is on, wtp_step launches
 // k_step_les_batch, the same step_tile with collide_les in its interior cells and one more value per member, in place of
 // k_step_batch.  A batch that has it off launches k_step_batch with the arguments it always had.
+//
+// Interpolated bounce-back (wtp_enable_ibb) is another wall rule: while it is on, wtp_step launches k_step_ibb_batch, the same
+// step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
+// collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction with the interpolated link term.  A
+// batch that has it off launches the kernels it always launched, with the arguments they always had.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -113,6 +118,10 @@ struct wtp_batch {
     // Smagorinsky subgrid viscosity (wtp_enable_les); the pointer is null until then
     bool les = false;
     void *les_c = nullptr;               // [B] of T: c = 18 sqrt(2) Cs^2 of every member
+    // interpolated bounce-back (wtp_enable_ibb); the pointer is null until then
+    bool ibb = false;
+    void *wq = nullptr;                  // [B][8] planes of T laid out like population planes 1..8, members q_stride elements apart
+    long q_stride = 0;
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -188,6 +197,29 @@ __global__ __launch_bounds__(256) void k_step_les_batch(const T *__restrict__ fs
     step_tile<T, EMIT, LOADMODE, false, COLLIDE_LES>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
                                                      tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane,
                                                      0, 0, 0, c);
+}
+
+// The same step with interpolated bounce-back (wall_incoming, d2q9.hpp) at every member's links, and with either collision:
+// k_step_batch's grid, walk and arguments, the members' wall distances wq (eight planes each, qstride elements apart) and, for
+// COLLIDE_LES, cles as in k_step_les_batch (not read otherwise).  A member whose distances are all 0.5 computes k_step_batch's
+// (k_step_les_batch's) numbers.  A kernel of its own name, so that a batch with the model off runs the code object it always ran.
+template <typename T, bool EMIT, int LOADMODE, int COLL>
+__global__ __launch_bounds__(256) void k_step_ibb_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                        const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                        int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                        const T *__restrict__ cles, const T *__restrict__ wq, long qstride, int rev)
+{
+    const int lane = threadIdx.x & 63;
+    const long ntiles = (long)g.nxl * tiles_per_col;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= ntiles) return;
+    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const T tau = params[2 * m], U0 = params[2 * m + 1];
+    T c = T(0.0);
+    if constexpr (COLL == COLLIDE_LES) c = cles[m];
+    step_tile<T, EMIT, LOADMODE, false, COLL, WALL_INTERP>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                           tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t,
+                                                           lane, 0, 0, 0, c, wq + m * qstride);
 }
 
 // "The last block of a member finishes the sum": called by every thread of a block once the block's partials of member m are
@@ -333,6 +365,8 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
 // 64 rows, one row per lane: the mask bytes of columns i-1, i, i+1 at rows j-1, j, j+1, then a population only on the lanes that
 // own a link in its direction.  The column's terms are added by wave_sum; the member's last block (member_done) adds the
 // columns' partials in column order, each of the four sums on a wave of its own.
+// KEEP IN STEP: k_mex_ibb_batch below is this kernel with another link term, body included.  The link bits, the walk, the ticket
+// and the final sum through LDS are the same text in both: a change to any of them here is made there too.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
@@ -412,6 +446,104 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restr
     }
 }
 
+// The momentum exchange of members that step with interpolated bounce-back (include/wt_polar.h "Interpolated bounce-back"):
+// k_mex_batch's grid, walk, arguments and final sum, with the link's term ((double)a + (double)b) e_k, a = f*_k(x) and b the value the
+// next step will reflect (wall_incoming of the current lattice, in T), and the link's point the wall point
+// r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky), q converted exactly.  wq holds the members' wall distances (eight planes each, laid out
+// like population planes 1..8, qstride elements apart), read, like the populations, only on the lanes that own a link.  At q = 0.5
+// both are k_mex_batch's.  A kernel of its own, body included, so that k_mex_batch compiles to the code it always compiled to.
+// KEEP IN STEP: everything but the three lines that form q, fa and fb and the two that use them (t, rx / ry) is k_mex_batch's text,
+// the ticket (member_done) and the final sum through LDS after it included: a change to either kernel's copy is made in the other.
+template <typename T>
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
+                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
+                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
+                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
+                                                   long long *__restrict__ links, const T *__restrict__ wq, long qstride)
+{
+    const long m = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int nx = g.nxl, ny = g.ny;
+    const int width = win[2 * m + 1];
+    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
+    if (c < width) {                                                // (wave-uniform)
+        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
+        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
+        const T *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;               // column i of population plane 0
+        const T *qc = wq + m * qstride + g.pitch + (long)i * g.pitch;             // column i of the plane of direction 1
+        const double xr = ref[2 * m], yr = ref[2 * m + 1];
+        double sx = 0.0, sy = 0.0, sm = 0.0;
+        long long n = 0;
+        for (int j0 = 0; j0 < ny; j0 += 64) {
+            const int j = j0 + lane;
+            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
+            if (j >= 1 && j <= ny - 2 && !mk[j]) {
+                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
+                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
+                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
+            }
+            if (__ballot(s != 0) == 0ULL) continue;
+#pragma unroll
+            for (int k = 1; k <= 8; k++) {
+                if (!(s >> k & 1u)) continue;
+                const long back = j - ey_of(k) - (long)ex_of(k) * g.pitch;      // x - e_k, from column i
+                const T q = qc[(k - 1) * g.plane + j], fa = fc[k * g.plane + j];
+                const T fb = wall_incoming<T>(q, fa, fc + k * g.plane + back, mk[back] != 0, fc + opp_of(k) * g.plane + j);
+                const double t = (double)fa + (double)fb, hq = (double)q;
+                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
+                const double rx = ((double)i + 0.5) + hq * (double)ex_of(k), ry = ((double)j + 0.5) + hq * (double)ey_of(k);
+                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
+                sx += flx;
+                sy += fly;
+                sm += a - b;
+                n += 1;
+            }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
+        if (lane == 0) {
+            MexPartial p;
+            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
+            col[m * nx + c] = p;
+        }
+    }
+    constexpr int NT = kLoadsWaves * 64;
+    __shared__ double sh[3][NT];
+    __shared__ long long shn[NT];
+    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
+    const volatile MexPartial *vc = col + m * nx;
+    const int w = (int)(threadIdx.x >> 6);
+    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
+    long long sn = 0;                                               // lane 0 of wave 3: links
+    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
+        const int q = c0 + (int)threadIdx.x;
+        const bool in = q < width;
+        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
+        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
+        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
+        shn[threadIdx.x] = in ? vc[q].links : 0;
+        __syncthreads();
+        if (lane == 0 && w < 4) {
+            const int cnt = width - c0 < NT ? width - c0 : NT;
+            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
+            else for (int k = 0; k < cnt; k++) sn += shn[k];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
+        else if (w == 1) fy[m] = s;
+        else if (w == 2) mz[m] = s;
+        else if (w == 3) links[m] = sn;
+    }
+}
+
+// Every element of p[0, n) set to v: the wall distances' default.
+template <typename T>
+__global__ __launch_bounds__(256) void k_fill_value(T *__restrict__ p, long n, T v)
+{
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) p[t] = v;
+}
+
 // Mean fields of every member in one launch: grid (ceil(NX * ceil(NY / R) / 256), B), R = WTP_MEAN_ROWS; one lane per run of R
 // consecutive rows of one column.  Definition (include/wt_polar.h): for member m and cell (i, j), let rho, ux, uy be what
 // wtp_read_macro would return after a sampled step, converted exactly to double.  Solid and boundary cells are included; no cell
@@ -484,7 +616,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -563,7 +695,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -627,6 +759,20 @@ static int zero_mean_sums(wtp_batch *b, int first, int count)
     return WT_OK;
 }
 
+// The wall distances of members [first, first+count) back to 0.5 (half-way), in stream order.  Nothing to do while they are not held.
+static int reset_wall_q(wtp_batch *b, int first, int count)
+{
+    if (!b->wq) return WT_OK;
+    const long n = (long)count * b->q_stride;
+    const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+    if (b->dtype == WT_F32)
+        hipLaunchKernelGGL(k_fill_value<float>, dim3(blocks), dim3(256), 0, b->st, (float *)b->wq + (long)first * b->q_stride, n, 0.5f);
+    else
+        hipLaunchKernelGGL(k_fill_value<double>, dim3(blocks), dim3(256), 0, b->st, (double *)b->wq + (long)first * b->q_stride, n, 0.5);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 // What restarts the time statistics of members [first, first+count): the surface sums and the mean fields, each if enabled.
 static int clear_sums(wtp_batch *b, int first, int count)
 {
@@ -652,6 +798,7 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
         surface_rows(b, first + k, m01.data());
         mex_window(b, first + k, m01.data());
         WT_TRY(clear_sums(b, first + k, 1));                    // the member's surface cells moved; a mean across two bodies means nothing
+        WT_TRY(reset_wall_q(b, first + k, 1));                  // a wall distance belongs to a mask
         HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
         uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
         dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
@@ -752,10 +899,15 @@ static int launch_mex(wtp_batch *b, int row)
     int widest = 1;                              // (a batch without a body still runs one block per member, which writes zeros)
     for (int m = 0; m < b->members; m++) widest = std::max(widest, (int)b->mex_win[2 * (size_t)m + 1]);
     const SampleTable &t = b->xforces;
-    hipLaunchKernelGGL(k_mex_batch<T>, dim3((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), dim3(kLoadsWaves * 64), 0,
-                       b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms, (const double *)b->x_ref,
-                       (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row), t.at<double>(1, row), t.at<double>(2, row),
-                       t.at<long long>(3, row));
+    const dim3 grid((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), block(kLoadsWaves * 64);
+    if (b->ibb)
+        hipLaunchKernelGGL(k_mex_ibb_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
+                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
+                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), (const T *)b->wq, b->q_stride);
+    else
+        hipLaunchKernelGGL(k_mex_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
+                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
+                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row));
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -794,7 +946,12 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
         const int rev = (int)(b->steps_done & 1);
-        if (b->les) {
+        if (b->ibb) {
+            const auto k_step = b->les ? (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_LES> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_LES>)
+                                       : (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_BGK> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_BGK>);
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride, rev);
+        } else if (b->les) {
             const auto k_step = emit ? k_step_les_batch<T, true, WT_LOADMODE> : k_step_les_batch<T, false, WT_LOADMODE>;
             hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
                                b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, rev);
@@ -865,6 +1022,67 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
     WT_TRY(b->dtype == WT_F32 ? upload_les<float>(b, cs) : upload_les<double>(b, cs));
     b->les = true;
     return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// interpolated bounce-back
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_ibb(wtp_batch *b, int on)
+{
+    WT_TRY(check_batch(b));
+    if (!on) { b->ibb = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->wq) {
+        const long stride = member_stride((size_t)8 * b->g.plane * b->esz, b->esz);
+        const size_t bytes = (size_t)b->members * stride * b->esz;
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // (the batch goes on with half-way walls: later launches must not see this error)
+            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the wall distances (%zu bytes) could not be allocated: %s", bytes,
+                        hipGetErrorString(e));
+        }
+        b->wq = p; b->q_stride = stride;
+        WT_TRY(reset_wall_q(b, 0, b->members));
+    }
+    b->ibb = true;
+    return WT_OK;
+}
+
+template <typename T>
+static int set_wall_q_impl(wtp_batch *b, int first, int count, const T *q)
+{
+    const size_t n = (size_t)b->nx * b->ny;
+    for (size_t e = 0; e < (size_t)count * 8 * n; e++)
+        if (!(q[e] > T(0.0) && q[e] <= T(1.0)))       // (false for a NaN)
+            return fail(WT_ERR_ARG, "wall distance %zu of member %d is not in (0, 1]", e % (8 * n), first + (int)(e / (8 * n)));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(ensure_stage(b, 8 * n * sizeof(T)));
+    const Geom &g = b->g;
+    for (int k = 0; k < count; k++) {
+        HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old distances
+        HIP_TRY(hipMemcpy(b->stage, q + (size_t)k * 8 * n, 8 * n * sizeof(T), hipMemcpyHostToDevice));
+        T *dst = reinterpret_cast<T *>(b->wq) + (long)(first + k) * b->q_stride;
+        dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
+        for (int p = 0; p < 8; p++) {
+            // [NY][NX] rows -> column i at row i + 1 of the padded plane (pad columns and rows past NY keep 0.5; nothing reads them)
+            hipLaunchKernelGGL(k_rows_to_cols<T>, grd, blk, 0, b->st, reinterpret_cast<const T *>(b->stage) + (size_t)p * n,
+                               dst + p * g.plane + g.pitch, 0, b->nx, b->ny, g.pitch, (long)b->nx);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(b->st));
+    return WT_OK;
+}
+
+extern "C" int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q)
+{
+    WT_TRY(check_batch(b));
+    if (!q) return fail(WT_ERR_ARG, "q is null");
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    if (!b->wq) return fail(WT_ERR_STATE, "interpolated bounce-back has never been enabled (wtp_enable_ibb)");
+    return b->dtype == WT_F32 ? set_wall_q_impl<float>(b, first, count, (const float *)q) : set_wall_q_impl<double>(b, first, count, (const double *)q);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -155,11 +155,13 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // WIN: the tile belongs to a grid whose tiles start every `stride` rows (tile height stays 64*N) and
 // only rows in [st_lo, st_hi) are stored — the window-aligned zone passes of step_fused.hpp.
 // COLL: the collision of interior fluid cells, COLLIDE_BGK or COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp).
-template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK>
+// WALL: the wall rule of interior fluid cells, WALL_HALFWAY or WALL_INTERP with the wall distances `wq`, eight planes laid out like
+// population planes 1..8, pad column included (wall_incoming, d2q9.hpp).  Only TILE_GENERAL tiles can own a link: no other path reads them.
+template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY>
 __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
-                                          int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0))
+                                          int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr)
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
@@ -179,7 +181,10 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
 #pragma unroll 1
         for (int v = 0; v < N; v++) {
             const int j = row0 + v * 64 + lane;
-            if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
+            if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) {
+                if constexpr (WALL == WALL_INTERP) site_general<T, COLL, WALL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch);
+                else site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
+            }
         }
         return;
     }

@@ -178,3 +178,49 @@ def build_geometry(nx: int, ny: int, a_deg: float, user_coords=None, shape: str 
         base = SHAPES[shape]()
     xp, yp = panelise(rotate(base, a_deg))
     return Geometry(xp=xp, yp=yp, mask=raster_mask(xp, yp, nx, ny, y_half), a_deg=float(a_deg))
+
+
+# D2Q9 directions 1..8 (csrc/d2q9.hpp, html:238-248)
+_LINK_DIRS = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))
+
+
+def wall_distances(xp: np.ndarray, yp: np.ndarray, mask: np.ndarray, nx: int, ny: int, y_half: Optional[float] = None) -> np.ndarray:
+    """The wall distances of interpolated bounce-back (include/wt_polar.h): float64 [8][NY][NX], plane k - 1 for direction k.
+
+    A link is an interior fluid cell (i, j) (1 <= i <= NX-2, 1 <= j <= NY-2, not solid) and a direction k whose neighbour
+    (i, j) + e_k is solid in `mask`.  Its entry is the fraction q in (0, 1] of the link at which the ray P + t e_k from the
+    cell centre P = (i + 0.5, j + 0.5) first crosses the panel polygon: the 160 panels of (xp, yp) plus the closing segment
+    from the last point to the first, in lattice units as raster_mask maps them, X = (x - DX0) / (DX1 - DX0) * nx,
+    Y = (y + y_half) / (2 y_half) * ny.  A crossing with segment A + u (B - A) counts with a non-zero denominator,
+    0 < t <= 1 and 0 <= u <= 1; q is the smallest such t.  A link without a crossing keeps 0.5, half-way bounce-back: the
+    rasteriser tests row centres and integer cell indices, so its staircase is not exactly "centre inside the polygon".
+    Entries that are no link are 0.5."""
+    if y_half is None:
+        y_half = domain_y_half(nx, ny)
+    solid = np.asarray(mask) != 0
+    if solid.shape != (ny, nx):
+        raise ValueError(f"mask must have shape [NY][NX] = {(ny, nx)}, got {solid.shape}")
+    X = (np.asarray(xp, np.float64) - DX0) / (DX1 - DX0) * nx
+    Y = (np.asarray(yp, np.float64) + y_half) / (2 * y_half) * ny
+    ax, ay = X, Y                                           # segment s runs from point s to point s + 1, the last one to point 0
+    dx, dy = np.roll(X, -1) - X, np.roll(Y, -1) - Y
+    q = np.full((8, ny, nx), 0.5)
+    interior = np.zeros_like(solid)
+    interior[1:ny - 1, 1:nx - 1] = True
+    for k, (ex, ey) in enumerate(_LINK_DIRS):
+        nb = np.zeros_like(solid)
+        nb[1:ny - 1, 1:nx - 1] = solid[1 + ey:ny - 1 + ey, 1 + ex:nx - 1 + ex]
+        jj, ii = np.nonzero(interior & ~solid & nb)
+        if jj.size == 0:
+            continue
+        # P + t e = A + u d:  t = ((A - P) x d) / (e x d),  u = ((A - P) x e) / (e x d),  [links][segments]
+        rx, ry = ax[None, :] - (ii[:, None] + 0.5), ay[None, :] - (jj[:, None] + 0.5)
+        den = ex * dy - ey * dx
+        ok = den != 0.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (rx * dy[None, :] - ry * dx[None, :]) / den[None, :]
+            u = (rx * ey - ry * ex) / den[None, :]
+        hit = ok[None, :] & (t > 0.0) & (t <= 1.0) & (u >= 0.0) & (u <= 1.0)
+        first = np.where(hit, t, np.inf).min(axis=1)
+        q[k, jj, ii] = np.where(np.isfinite(first), first, 0.5)
+    return q

@@ -11,7 +11,9 @@ chordwise surface pressure; with the momentum exchange enabled (``PolarEngine.en
 enabled (``PolarEngine.enable_mean_fields``, ``run_polar(mean_fields=True)``) the time-mean flow field of every angle and the
 fluctuation about it (:func:`mean_flow`: Reynolds stresses, pressure r.m.s.), from seven running sums kept on the device.
 At airfoil Reynolds numbers, where tau falls to within 1e-3 of 0.5, the Smagorinsky subgrid viscosity
-(``PolarEngine.enable_les``, ``run_polar(les=0.1)``) keeps the members off the stability net.
+(``PolarEngine.enable_les``, ``run_polar(les=0.1)``) keeps the members off the stability net.  With interpolated bounce-back
+(``PolarEngine.enable_interpolated_walls``, ``run_polar(walls="interpolated")``) the wall of every member is the panel polygon
+itself, through a wall distance per link (``geometry.wall_distances``), and not the staircase of its raster mask.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -42,8 +44,10 @@ EXPORTS = (
     "wtp_enable_mex", "wtp_history_mex", "wtp_mex",
     "wtp_enable_mean", "wtp_mean_sums",
     "wtp_enable_les",
+    "wtp_enable_ibb", "wtp_set_wall_q",
 )
 
+WALLS = ("staircase", "interpolated")                              # run_polar's wall rules
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
 
 _lib = None
@@ -88,6 +92,8 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_enable_mean": ([B], c_int),
         "wtp_mean_sums": ([B, c_int, ip, dp, dp, dp, dp, dp, dp, dp], c_int),
         "wtp_enable_les": ([B, dp], c_int),
+        "wtp_enable_ibb": ([B, c_int], c_int),
+        "wtp_set_wall_q": ([B, c_int, c_int, c_void_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -128,6 +134,7 @@ class PolarEngine:
         self.mex_enabled = False
         self.mean_enabled = False
         self.les_enabled = False
+        self.interpolated_walls = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -262,6 +269,25 @@ class PolarEngine:
         _check(self._lib.wtp_enable_les(self._b, _dp(v)))
         self.les_enabled = True
 
+    def enable_interpolated_walls(self, on: bool = True) -> None:
+        """Reflect at the walls by linear interpolated bounce-back from the next step on (wt_polar.h): every link uses its wall
+        distance, 0.5 (half-way, the staircase) until set_wall_distances gives the true ones.  on=False switches back to the
+        half-way kernels and keeps the distances.  The flow state, the history and every running sum are kept; combines with
+        enable_les, independent of the read-outs."""
+        _check(self._lib.wtp_enable_ibb(self._b, 1 if on else 0))
+        self.interpolated_walls = bool(on)
+
+    def set_wall_distances(self, q, first: int = 0) -> None:
+        """q [count][8][NY][NX] (or one [8][NY][NX]) for members first .. first+count-1, each value in (0, 1], plane k - 1 for
+        direction k (geometry.wall_distances); converted to the batch's dtype.  After set_masks, which resets the distances of
+        the members it touches to 0.5."""
+        a = np.ascontiguousarray(q, dtype=self.dtype)
+        if a.ndim == 3:
+            a = a[None]
+        if a.ndim != 4 or a.shape[1:] != (8, self.ny, self.nx):
+            raise ValueError(f"wall distances must have shape [count][8][NY][NX] = [count]{(8, self.ny, self.nx)}, got {a.shape}")
+        _check(self._lib.wtp_set_wall_q(self._b, int(first), int(a.shape[0]), a.ctypes.data_as(c_void_p)))
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -336,6 +362,12 @@ class PolarResult:
     warmup_steps: int
     sample_every: int
     les: Optional[float] = None          # the Smagorinsky constant of every member (None: plain BGK)
+    # The wall rule of the sweep, "staircase" (half-way bounce-back on the raster mask) or "interpolated".  Init-only, as
+    # PolarPoint's totals are: accepted by the constructor after the fields above and kept as an attribute.
+    walls: InitVar[str] = "staircase"
+
+    def __post_init__(self, walls):
+        self.walls = walls
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -446,7 +478,8 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False, les: Optional[float] = None) -> PolarResult:
+              total_forces: bool = False, mean_fields: bool = False, walls: str = "staircase",
+              les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -460,7 +493,11 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     takes no sample, so nothing of it enters the mean.  Off by default, with the same guarantees as `total_forces`.
     `les`: the Smagorinsky constant (0.1 to 0.17 are the usual values; at most 0.5) of a subgrid eddy viscosity in every member's
     collision, from the first warm-up step on (PolarEngine.enable_les).  For sweeps at airfoil Reynolds numbers (`re` of 20 000
-    and above), where plain BGK runs into the stability net and the angle fails.  None, the default, is plain BGK."""
+    and above), where plain BGK runs into the stability net and the angle fails.  None, the default, is plain BGK.
+    `walls`: "staircase", the default, reflects half-way to the next cell of the raster mask, with the bits it always had;
+    "interpolated" reflects by linear interpolated bounce-back at the panel polygon of each angle, through the wall distances
+    geometry.wall_distances computes from the Geometry the mask came from, from the first warm-up step on
+    (PolarEngine.enable_interpolated_walls).  The momentum exchange (`total_forces`) then uses the interpolated link term."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -472,15 +509,22 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         les = float(les)
         if not math.isfinite(les) or les < 0.0 or les > 0.5:
             raise ValueError(f"les must be a finite Smagorinsky constant in [0, 0.5], got {les!r}")
+    if walls not in WALLS:
+        raise ValueError(f"walls must be one of {WALLS}, got {walls!r}")
     nx, ny, u0 = int(nx), int(ny), float(u0)
     tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
     if warmup_steps is None:
         warmup_steps = int(math.ceil(2 * nx / u0))
     warmup_steps = int(warmup_steps)
     user = geo.round_coords(coords) if coords is not None and len(coords) else []
-    masks = np.stack([geo.build_geometry(nx, ny, a, user, shape).mask for a in alphas])
+    geoms = [geo.build_geometry(nx, ny, a, user, shape) for a in alphas]
+    masks = np.stack([g.mask for g in geoms])
     with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device) as eng:
         eng.set_masks(masks)
+        if walls == "interpolated":
+            eng.enable_interpolated_walls()
+            for m, g in enumerate(geoms):                      # (one member at a time: eight float64 planes each on the host)
+                eng.set_wall_distances(geo.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
         eng.init_equilibrium(u0)
         if loads:
             eng.enable_loads(*quarter_chord(nx, ny))
@@ -504,7 +548,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               for m, a in enumerate(alphas)]
     for p, mean in zip(points, means):
         p.mean = mean
-    return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les)
+    return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
+                       walls=walls)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

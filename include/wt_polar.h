@@ -178,6 +178,46 @@ WTP_API int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, dou
  * (top of this file) holds for members with cs = 0 and for batches with the model off only.
  */
 WTP_API int wtp_enable_les(wtp_batch *b, const double *cs);
+/*
+ * Interpolated bounce-back: curved walls.  A member's wall is a raster mask, and half-way bounce-back puts the surface half a
+ * cell from every fluid cell next to it, whatever the true distance is.  Linear interpolated bounce-back (Bouzidi, Firdaouss
+ * and Lallemand 2001) gives every wall link the fraction q of the link at which it crosses the true surface and interpolates
+ * the reflected population accordingly.  It is another wall rule, per batch and opt-in.  Definition:
+ *   The directions e_k, k = 1..8, and opp(k) are those of d2q9.hpp.
+ *   The wall distance.  Member m holds, per cell (i, j) and direction k, a wall distance q_k(i, j) of the batch's dtype T, with
+ *   0 < q <= 1.  It is stored as eight planes per member.  It is used only where x = (i, j) is an interior fluid cell (the cells
+ *   that take STEP_FS's interior branch) and x + e_k is solid.  Such a pair is a link, exactly as in the momentum exchange.
+ *   The incoming population.  In the step, the incoming population fin[opp(k)] of x, which half-way bounce-back sets to
+ *   s[k](x), becomes the following.  Here a = s[k](x), g = s[k](x - e_k), h = s[opp(k)](x), and s is the source lattice.  Every
+ *   operation rounds once in T.  Evaluation is left to right as written, with no contraction.  The division is IEEE.
+ *     two = 2*q
+ *     q <  0.5:  fin = two*a + (1 - two)*g      if x - e_k is not solid, else fin = a
+ *     q >= 0.5:  inv = 1/two;  fin = inv*a + (1 - inv)*h
+ *   Everything else in the step is unchanged: pull-stream, moments, the clamp, the collision (BGK or the Smagorinsky one), the
+ *   stored (rho, ux, uy), and the solid, inlet, outlet and far-field branches.  With q = 0.5, two = 1, so fin equals a as a
+ *   number.  A batch with the model on and every q at 0.5 equals a plain batch under np.array_equal.
+ *   The momentum exchange with the model on.  The link's term becomes (double)a + (double)b, times e_k, where b is the value the
+ *   next step will reflect.  b is computed from the current lattice by the formulas above in T and then converted.  The link's
+ *   point for the moment becomes the wall point r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky).  Here q is converted exactly to double.
+ *   links is unchanged.  At q = 0.5 both reduce to the half-way definition above.  The pressure forces, the loads and the mean
+ *   fields read the macroscopic planes and are untouched.
+ * The device holds the distances as eight planes per member, each laid out like a population plane: 8 * (NX + 2) * pitch *
+ * sizeof(T) bytes per member with pitch = NY rounded up to 256, rounded up like every per-member array (2.6 MB at 320x160 fp32).
+ *
+ * wtp_enable_ibb with on != 0 switches the model on: on first use it allocates the planes of all members, filled with 0.5, and
+ * from the next wtp_step the interpolating kernels run.  Where the allocation fails it returns WT_ERR_OOM, holds nothing, and
+ * the batch goes on as before.  on == 0 switches back to the original kernels, with the same bits as in a batch that never
+ * enabled it; the planes are kept.  The flow state, the step count, the history and every running sum are kept either way.
+ * It combines with wtp_enable_les and is independent of the read-outs.  A batch that never calls it launches the kernels it
+ * always launched.  A member with interpolated walls has no libwindtunnel twin.
+ */
+WTP_API int wtp_enable_ibb(wtp_batch *b, int on);
+/* The wall distances of members [first, first+count): q is [count][8][NY][NX] of the batch's dtype, plane k - 1 holds
+ * direction k.  Every value must be finite and in (0, 1], else WT_ERR_ARG before any device call, and the batch is left as
+ * it was; so for a member range outside the batch.  WT_ERR_STATE while the model has never been enabled.  Entries that are no
+ * link are never read.  wtp_set_masks resets the distances of the members it touches to 0.5: a distance belongs to a mask, so
+ * upload the distances after the masks. */
+WTP_API int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -32,6 +32,12 @@ place of k_step_batch.  The line gives `repeats` timings of the same window and 
 BGK step, so that two lines compare.  No sequential leg: a single handle has no such collision.  With --loads / --mex / --mean the
 model is on in both variants of those protocols.
 
+    python tools/polar_bench.py --ibb [--les CS] [--repeats 5] [the options of the first form]
+
+The batched step with interpolated bounce-back (wtp_enable_ibb, every member with the wall distances of its own airfoil):
+k_step_ibb_batch in place of k_step_batch (or, with --les, of k_step_les_batch).  The line has the shape of --les's; no sequential
+leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -51,19 +57,33 @@ PEAK_BPS = 8.0e12
 TAU, U0 = 0.58, 0.06
 
 
+def _alphas(b):
+    return np.linspace(-4.0, 12.0, b) if b > 1 else np.array([6.0])
+
+
 def _masks(nx, ny, b):
-    alphas = np.linspace(-4.0, 12.0, b) if b > 1 else np.array([6.0])
-    return np.stack([pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412").mask for a in alphas])
+    return np.stack([pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412").mask for a in _alphas(b)])
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1):
-    """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK)."""
+def _interpolated_walls(eng, nx, ny, b):
+    """Switch interpolated bounce-back on and give every member the wall distances of its airfoil (_masks' geometries)."""
+    eng.enable_interpolated_walls()
+    for m, a in enumerate(_alphas(b)):
+        g = pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412")
+        eng.set_wall_distances(pkg.geometry.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
+
+
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False):
+    """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
+    ibb: interpolated bounce-back with every airfoil's wall distances."""
     out = []
     with pkg.PolarEngine(nx, ny, b) as eng:
         eng.set_masks(masks)
         eng.init_equilibrium(U0)
         if les is not None:
             eng.enable_les(les)
+        if ibb:
+            _interpolated_walls(eng, nx, ny, b)
         eng.step(warmup, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -75,6 +95,7 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1):
 
 
 LES = None      # --les: the Smagorinsky constant the sampled protocols run with (None: BGK)
+IBB = False     # --ibb: the sampled protocols run with interpolated bounce-back
 
 
 def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
@@ -91,6 +112,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.enable_mean_fields()
         if LES is not None:
             eng.enable_les(LES)
+        if IBB:
+            _interpolated_walls(eng, nx, ny, b)
         eng.step(warmup - warmup % every, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -206,6 +229,7 @@ def main():
     ap.add_argument("--mex", action="store_true", help="the sampled step with and without the momentum-exchange readout")
     ap.add_argument("--mean", action="store_true", help="the sampled step with and without the mean fields")
     ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
+    ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
@@ -215,8 +239,8 @@ def main():
         a.repeats = 1 if plain else 7
     if a.lib:
         pkg.polar.load_polar_library(a.lib)
-    global LES
-    LES = a.les
+    global LES, IBB
+    LES, IBB = a.les, a.ibb
     if a.mean:
         return mean_cost(a)
     if a.mex:
@@ -228,7 +252,7 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
@@ -236,10 +260,12 @@ def main():
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.repeats > 1:
+            if a.les is not None or a.ibb or a.repeats > 1:
                 line["les"] = a.les
+                if a.ibb:
+                    line["ibb"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None:
+            if not a.no_sequential and a.les is None and not a.ibb:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
