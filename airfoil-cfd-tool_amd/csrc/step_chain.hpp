@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
         // chain blocks (step_chain.hpp): the four waves of this workgroup share the edge columns of their units through LDS.  The flag is
         // per block (set by chain_blocks on the host for all four units or none), so the barriers inside are workgroup-uniform.
         if (uflags & MU_CHAIN) {
-            constexpr int FDP = (DEPTH == 4 && sizeof(T) == 4) ? (FD | MARCH_FD_PACKED) : FD;
+            constexpr int FDP = (DEPTH == 4 && sizeof(T) == 4) ? (FD | MARCH_FD_PACKED | (EMIT ? 0 : MARCH_FD_VELSHARED)) : FD;
             ChainLds<T, S, DEPTH> &chain_lds = lds_pool.chain;
             const bool end_shared = (uflags & MU_END_SHARED) != 0;
             if (lane < 2 * (DEPTH - 1)) chain_lds.flag[lane / (DEPTH - 1)][lane % (DEPTH - 1)][u & 3] = 0;     // my own hand-over flags ...
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
         }
     }
     if (DEPTH == 4) {
-        constexpr int FDP = sizeof(T) == 4 ? (FD | MARCH_FD_PACKED) : FD;     // fp32: the packed two-site collision (step_march.hpp)
+        constexpr int FDP = sizeof(T) == 4 ? (FD | MARCH_FD_PACKED | (EMIT ? 0 : MARCH_FD_VELSHARED)) : FD;     // fp32: the packed two-site collision (step_march.hpp)
         if (lean) march_unit4<false, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, no_m, no_m, feq0);
         else march_unit4<true, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
     } else if (DEPTH == 3) {

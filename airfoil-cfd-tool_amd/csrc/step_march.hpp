@@ -380,6 +380,10 @@ __device__ __forceinline__ SiteBytes site_bytes_load(const MarchParams<T> &p, in
 // (MARCH_FD_PACKED): measured in alternating runs on one box it gains 3.4 % in the four-step kernel (158 -> 163 GLUPS), which
 // is bound by its instruction stream, and loses 1-1.5 % in the three-step kernel on slab-sized lattices.
 static constexpr int MARCH_FD_PACKED = 4;
+// bit 6 of FD, set beside MARCH_FD_PACKED by the four-step kernel's NON-EMITTING instantiations (step_chain.hpp k_march3): the plain columns' collision
+// shares one reciprocal between the two velocity divisions (collide2_shared below).  The emitting ones — one pass per readout — stand at 255 of 256
+// registers as they are, and the decision's two momenta would spill there.
+static constexpr int MARCH_FD_VELSHARED = 64;
 typedef float f2v __attribute__((ext_vector_type(2)));
 // a / b for two sites at once, operation for operation hipcc's own expansion of the IEEE binary32 division (LLVM AMDGPUTargetLowering::LowerFDIV32 with
 // fp32 denormals on: v_div_scale x2, v_rcp, fma, fma, mul, fma, fma, fma, v_div_fmas, v_div_fixup) — the same instructions on the same values, so the same
@@ -402,6 +406,136 @@ __device__ __forceinline__ f2v div2_ieee(f2v a, f2v b)
     q[0] = __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(f4[0], f1[0], f3[0], s0), b[0], a[0]);
     q[1] = __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(f4[1], f1[1], f3[1], s1), b[1], a[1]);
     return q;
+}
+
+// nu / rs and nv / rs for two sites on ONE reciprocal per site: the operations of div2_ieee without its v_div_scale, v_div_fmas and v_div_fixup, the
+// reciprocal and its two refinements — which see the denominator alone — computed once for both numerators.  The same bits as two div2_ieee calls
+// wherever veldiv_guard (below) holds; operand by operand, from the definitions of the three instructions (b = rs the denominator, a a numerator):
+//   v_div_scale_f32 returns its operand unchanged and clears VCC unless one of these holds, tested in this order: a or b is zero (NaN: see +0 below);
+//     exponent(a) - exponent(b) >= 96 (here a < 12, b >= 0.5: at most 4); b subnormal (b >= 0.5); 1 / b subnormal (b < 18); a / b subnormal
+//     (|a| >= 2^-103, b < 18: |a / b| > 2^-108); biased exponent of a <= 23, i.e. |a| < 2^-103 (excluded).  So ds = b, ns = a, and rc, f0 .. f4 below are
+//     div2_ieee's values.
+//   v_div_fmas_f32 is fma(f4, f1, f3), times 2^32 only where VCC is set: here the plain fma.
+//   v_div_fixup_f32(q, b, a) returns q with the sign of a / b for finite non-zero a and b unless exponent(a) - exponent(b) is below -150 or the
+//     exponent of b is 255 (neither here); q is within an ulp of a / b, of magnitude above 2^-108, hence non-zero, normal and of that sign already.
+//   a = +0: v_div_fixup_f32 returns (sign a xor sign b) 0 = +0 whatever the NaN chain before it computed; here mu = +0 f1 = +0 (f1 > 0), f2 = fma(-b, +0, +0)
+//     = -0 + +0 = +0, f3 = fma(+0, f1, +0) = +0, f4 = +0, q = +0.  (a = -0 would give +0 as well where the division gives -0: the guard keeps it out.)
+// tools/veldiv_check.c runs the chain on the CPU with every float within one ulp of 1 / b in place of v_rcp_f32's against the correctly rounded quotient;
+// k_check_veldiv below compares it with the division on the device.
+__device__ __forceinline__ void div2_shared(f2v nu, f2v nv, f2v rs, f2v &u, f2v &v)
+{
+    const f2v rc = {__builtin_amdgcn_rcpf(rs[0]), __builtin_amdgcn_rcpf(rs[1])};
+    const f2v one = {1.0f, 1.0f};
+    const f2v f0 = __builtin_elementwise_fma(-rs, rc, one);
+    const f2v f1 = __builtin_elementwise_fma(f0, rc, rc);
+    const f2v mu = nu * f1, mv = nv * f1;
+    const f2v f2u = __builtin_elementwise_fma(-rs, mu, nu), f2w = __builtin_elementwise_fma(-rs, mv, nv);
+    const f2v f3u = __builtin_elementwise_fma(f2u, f1, mu), f3v = __builtin_elementwise_fma(f2w, f1, mv);
+    const f2v f4u = __builtin_elementwise_fma(-rs, f3u, nu), f4v = __builtin_elementwise_fma(-rs, f3v, nv);
+    u = __builtin_elementwise_fma(f4u, f1, f3u);
+    v = __builtin_elementwise_fma(f4v, f1, f3v);
+}
+
+// Pair number i of the self-test's stream (tools/veldiv_check.c builds the same on the CPU), inside the ranges veldiv_guard admits.  Even i, pseudo-random:
+// b uniform in significand over the binades of [0.5, 18), a over the binades of [2^-103, 12), either sign.  Odd i, built: a = +0; a and b a few ulps inside
+// either end of their ranges; else a = RN(m b) -3 .. +3 ulps for the midpoint m above a float q (as k_check_fastdiv64 builds them), q in [2^-101, 2^-1).
+__device__ __forceinline__ void veldiv_pair(unsigned long long seed, unsigned long long i, float &a, float &b)
+{
+    auto mix = [](unsigned long long z) { z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL; z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL; return z ^ (z >> 31); };
+    constexpr unsigned A_MIN = 0x0c000000u, A_END = 0x41400000u, B_MIN = 0x3f000000u, B_END = 0x41900000u;      // 2^-103, 12, 0.5, 18
+    const unsigned long long z = mix(seed + 0x9e3779b97f4a7c15ULL * (i + 1)), y = mix(z);
+    const unsigned eb = 126u + (unsigned)((z >> 23) % 6u);
+    unsigned bb = (eb << 23) | (unsigned)(z & 0x7fffffu);
+    if (bb >= B_END) bb = (eb << 23) | (unsigned)(z & 0xfffffu);
+    const unsigned sign = (unsigned)(z >> 63) << 31;
+    unsigned ab;
+    if (!(i & 1)) {
+        const unsigned ea = 24u + (unsigned)((z >> 32) % 107u);
+        ab = (ea << 23) | (unsigned)(y & 0x7fffffu);
+        if (ab >= A_END) ab = (ea << 23) | (unsigned)(y & 0x3fffffu);
+        ab |= sign;
+    } else if ((i & 14) == 2) {
+        ab = 0;
+    } else if ((i & 14) == 4) {
+        const unsigned da = (unsigned)(y & 7u), db = (unsigned)((y >> 3) & 7u);
+        ab = (((y >> 6) & 1u) ? A_END - 1u - da : A_MIN + da) | sign;
+        bb = ((y >> 7) & 1u) ? B_END - 1u - db : B_MIN + db;
+    } else {
+        const unsigned eq = (unsigned)(26u + (z >> 32) % 100u) << 23;
+        const float q = __uint_as_float(eq | (unsigned)(y & 0x7fffffu)), bf = __uint_as_float(bb);
+        const float xm = __builtin_fmaf(q, bf, (__uint_as_float(eq) * 0x1p-24f) * bf);       // (2^e 2^-24: half an ulp of q; times b: exact)
+        ab = (__float_as_uint(xm) + (unsigned)((y >> 60) & 7u) - 3u) | sign;
+    }
+    a = __uint_as_float(ab);
+    b = __uint_as_float(bb);
+}
+// option "selftest_veldiv": mismatches of div2_shared against the division, 4 n pairs per thread (tests/test_gpu_veldiv.py)
+__global__ void k_check_veldiv(unsigned long long seed, int n, unsigned int *__restrict__ nbad)
+{
+    const unsigned long long t = (unsigned long long)(blockIdx.x * blockDim.x + threadIdx.x);
+    unsigned int bad = 0;
+    for (int it = 0; it < n; it++) {
+        float a[4], b[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) veldiv_pair(seed, (t * (unsigned long long)n + (unsigned long long)it) * 4ULL + (unsigned long long)j, a[j], b[j]);
+        // two sites: denominators b[0], b[1] (those of pairs 2, 3 go unused), numerators a[0], a[1] and a[2], a[3]
+        f2v u, v;
+        div2_shared(f2v{a[0], a[1]}, f2v{a[2], a[3]}, f2v{b[0], b[1]}, u, v);
+        bad += (__float_as_uint(u[0]) != __float_as_uint(a[0] / b[0])) + (__float_as_uint(u[1]) != __float_as_uint(a[1] / b[1]));
+        bad += (__float_as_uint(v[0]) != __float_as_uint(a[2] / b[0])) + (__float_as_uint(v[1]) != __float_as_uint(a[3] / b[1]));
+    }
+    if (bad) atomicAdd(nbad, bad);
+}
+
+// This lane's two sites may take div2_shared, the one-sided density clamp and the fast division by tau.  Decided before the velocities exist, on the raw
+// bits, as unsigned integers (a non-negative float orders like its bits; a set sign bit or a NaN lies above every finite non-negative one):
+//   every population in [+0, 2): no NaN, no infinity, nothing negative and no -0; so 0 <= rho < 18, the momenta are finite and below 12 in magnitude, and
+//     no momentum is -0 — a sum of six terms is -0 only if every term is, which takes fin[1] (fin[2]) = -0;
+//   rho >= 0.5 (so the lower density clamp does nothing);
+//   each of the four momenta +0 or of magnitude >= 2^-103: (bits << 1) - 1 puts +0 on top and orders the rest by magnitude.
+__device__ __forceinline__ bool veldiv_guard(const f2v (&fin)[9], f2v rs, f2v nu, f2v nv)
+{
+    auto bits = [](float x) { return __builtin_bit_cast(unsigned, x); };
+    auto max3 = [](unsigned a, unsigned b, unsigned c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); };
+    auto mag = [&](float x) { return (bits(x) << 1) - 1u; };
+    unsigned top[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+        top[i] = max3(max3(bits(fin[0][i]), bits(fin[1][i]), bits(fin[2][i])), max3(bits(fin[3][i]), bits(fin[4][i]), bits(fin[5][i])),
+                      max3(bits(fin[6][i]), bits(fin[7][i]), bits(fin[8][i])));
+    const unsigned a = mag(nu[0]), b = mag(nu[1]), c = mag(nv[0]), d = mag(nv[1]);
+    const unsigned low3 = a < b ? (a < c ? a : c) : (b < c ? b : c), low = low3 < d ? low3 : d;
+    return top[0] < 0x40000000u && top[1] < 0x40000000u && rs[0] >= 0.5f && rs[1] >= 0.5f && low >= 2u * 0x0c000000u - 1u;
+}
+
+// fo = fin - (fin - eq) / tau for two sites, the division in two / three operations (d2q9.hpp div_by_tau_fast)
+template <bool TWO_OP>
+__device__ __forceinline__ void relax2_fast(const f2v (&fin)[9], const f2v (&eq)[9], const FastDiv &fdv, f2v (&fo)[9])
+{
+    const f2v rt = {fdv.rtau, fdv.rtau}, ta = {fdv.tau, fdv.tau}, rl = {fdv.rlo, fdv.rlo};
+    // three directions abreast: a packed fp32 instruction whose result the very next instruction needs costs a wait state (s_nop) —
+    // written chain by chain the nine relaxations were a fifth of the loop's issue slots in nops
+#pragma unroll
+    for (int g = 0; g < 9; g += 3) {
+        f2v x[3], q0[3], e[3], t[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) x[j] = fin[g + j] - eq[g + j];
+        if constexpr (TWO_OP) {      // div_by_tau_fast<true>: p = x rlo, q = fma(x, r, p)
+#pragma unroll
+            for (int j = 0; j < 3; j++) q0[j] = x[j] * rl;
+#pragma unroll
+            for (int j = 0; j < 3; j++) t[j] = __builtin_elementwise_fma(x[j], rt, q0[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 3; j++) q0[j] = x[j] * rt;
+#pragma unroll
+            for (int j = 0; j < 3; j++) e[j] = __builtin_elementwise_fma(-q0[j], ta, x[j]);
+#pragma unroll
+            for (int j = 0; j < 3; j++) t[j] = __builtin_elementwise_fma(e[j], rt, q0[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++) fo[g + j] = fin[g + j] - t[j];
+    }
 }
 
 template <int FD, bool TWO_OP>
@@ -448,30 +582,7 @@ __device__ __forceinline__ void collide2_packed(const f2v (&fin)[9], const FastD
     f2v eq[9];
     feq_all<f2v>(r, u, v, eq);
     if (FD != 0 && fast) {
-        const f2v rt = {fdv.rtau, fdv.rtau}, ta = {fdv.tau, fdv.tau}, rl = {fdv.rlo, fdv.rlo};
-        // three directions abreast: a packed fp32 instruction whose result the very next instruction needs costs a wait state (s_nop) —
-        // written chain by chain the nine relaxations were a fifth of the loop's issue slots in nops
-#pragma unroll
-        for (int g = 0; g < 9; g += 3) {
-            f2v x[3], q0[3], e[3], t[3];
-#pragma unroll
-            for (int j = 0; j < 3; j++) x[j] = fin[g + j] - eq[g + j];
-            if constexpr (TWO_OP) {      // div_by_tau_fast<true>: p = x rlo, q = fma(x, r, p)
-#pragma unroll
-                for (int j = 0; j < 3; j++) q0[j] = x[j] * rl;
-#pragma unroll
-                for (int j = 0; j < 3; j++) t[j] = __builtin_elementwise_fma(x[j], rt, q0[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 3; j++) q0[j] = x[j] * rt;
-#pragma unroll
-                for (int j = 0; j < 3; j++) e[j] = __builtin_elementwise_fma(-q0[j], ta, x[j]);
-#pragma unroll
-                for (int j = 0; j < 3; j++) t[j] = __builtin_elementwise_fma(e[j], rt, q0[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 3; j++) fo[g + j] = fin[g + j] - t[j];
-        }
+        relax2_fast<TWO_OP>(fin, eq, fdv, fo);
     } else {
 #pragma unroll
         for (int k = 0; k < 9; k++) {
@@ -484,8 +595,43 @@ __device__ __forceinline__ void collide2_packed(const f2v (&fin)[9], const FastD
     rho = r; ux = u; uy = v;
 }
 
-// collide S sites per lane; fp32: one wave-uniform decision between the fast and the IEEE division by tau
-template <typename T, int S, int FD>
+// collide2_packed for the plain columns, with ONE wave-uniform decision per collision, taken before the velocities exist: every lane's two sites in the
+// ranges of veldiv_guard — div2_shared, the upper density clamp alone, the fast division by tau —, or the whole wave through collide2_packed as it stands.
+// The same bits either way (div2_shared, d2q9.hpp): the decision is a matter of speed alone.  FD = 1 only; the general (body) columns keep
+// collide2_packed: their loop holds every input population across the collision and stands at 255 of 256 registers without the two momenta.
+template <bool TWO_OP>
+__device__ __forceinline__ void collide2_shared(const f2v (&fin)[9], const FastDiv &fdv, f2v (&fo)[9], f2v &rho, f2v &ux, f2v &uy)
+{
+    f2v rs = fin[0];                     // (as collide2_packed)
+#pragma unroll
+    for (int k = 1; k < 9; k++) rs += fin[k];
+    const f2v nu = fin[1] + fin[5] + fin[8] - fin[3] - fin[6] - fin[7], nv = fin[2] + fin[5] + fin[6] - fin[4] - fin[7] - fin[8];
+    unsigned long long out = __ballot(!veldiv_guard(fin, rs, nu, nv));       // lanes with a site outside the guard's ranges
+    asm("" : "+s"(out));                 // a scalar compare and branch on the mask itself (hipcc otherwise branches on VCC, the rare path laid out first)
+    if (__builtin_expect(out == 0ULL, 1)) {
+        const float rhoMax = 2.0f, uMax = 0.35f;                   // html:344
+        f2v r, u, v;
+        div2_shared(nu, nv, rs, u, v);
+        r[0] = __builtin_fminf(rs[0], rhoMax); r[1] = __builtin_fminf(rs[1], rhoMax);           // (0.5 <= rho, no NaN: the clamp's upper half is all of it)
+        const f2v spd2 = u * u + v * v;                                                          // (finite: |u|, |v| < 24)
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            if (spd2[i] > uMax * uMax) {
+                const float k = uMax / wt_sqrt<float>(spd2[i]);
+                u[i] *= k;
+                v[i] *= k;
+            }
+        }
+        f2v eq[9];
+        feq_all<f2v>(r, u, v, eq);
+        relax2_fast<TWO_OP>(fin, eq, fdv, fo);
+        rho = r; ux = u; uy = v;
+    } else collide2_packed<1, TWO_OP>(fin, fdv, fo, rho, ux, uy);
+}
+
+// collide S sites per lane; fp32: one wave-uniform decision between the fast and the IEEE division by tau — and, VEL_SHARED (MARCH_FD_VELSHARED on a plain
+// column, with a proved division by tau), the velocity divisions: collide2_shared
+template <typename T, int S, int FD, bool VEL_SHARED = false>
 __device__ __forceinline__ void march_collide_sites(const MV<T, S> (&fin)[9], const FastDiv &fdv, T tau, MV<T, S> (&o)[9], MV<T, S> &rho4, MV<T, S> &ux4,
                                                     MV<T, S> &uy4)
 {
@@ -506,7 +652,8 @@ __device__ __forceinline__ void march_collide_sites(const MV<T, S> (&fin)[9], co
         f2v a[9], f[9], r, u, w;
 #pragma unroll
         for (int k = 0; k < 9; k++) a[k] = f2v{fin[k].v[0], fin[k].v[1]};
-        collide2_packed<FDV, TWO>(a, fdv, f, r, u, w);
+        if constexpr (VEL_SHARED && FDV == 1) collide2_shared<TWO>(a, fdv, f, r, u, w);
+        else collide2_packed<FDV, TWO>(a, fdv, f, r, u, w);
 #pragma unroll
         for (int k = 0; k < 9; k++) { o[k].v[0] = f[k][0]; o[k].v[1] = f[k][1]; }
         rho4.v[0] = r[0]; rho4.v[1] = r[1]; ux4.v[0] = u[0]; ux4.v[1] = u[1]; uy4.v[0] = w[0]; uy4.v[1] = w[1];
@@ -552,7 +699,7 @@ template <typename T, int S, int FD, bool WANT_MACRO>
 __device__ __forceinline__ void march_collide(const MV<T, S> (&fin)[9], const FastDiv &fdv, T tau, MV<T, S> (&G)[9], MV<T, S> (&mac)[3])
 {
     MV<T, S> rho4, ux4, uy4;
-    march_collide_sites<T, S, FD>(fin, fdv, tau, G, rho4, ux4, uy4);
+    march_collide_sites<T, S, FD, (FD & MARCH_FD_VELSHARED) != 0>(fin, fdv, tau, G, rho4, ux4, uy4);
     if (WANT_MACRO) { mac[0] = rho4; mac[1] = ux4; mac[2] = uy4; }
 }
 

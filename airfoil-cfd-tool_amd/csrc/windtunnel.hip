@@ -1020,6 +1020,20 @@ extern "C" int wt_get_option(const wt_handle *h, const char *name, double *value
     if (strcmp(name, "canvas_scale") == 0) { *value = h->cv_scale; return WT_OK; }                    // 0: no canvas allocated yet
     if (strcmp(name, "canvas_text_set") == 0) { *value = h->cv_text_set ? 1.0 : 0.0; return WT_OK; }  // the label map of the present canvas has been uploaded
     if (strcmp(name, "canvas_layer_live") == 0) { *value = h->cv_layer_live ? 1.0 : 0.0; return WT_OK; }
+    if (strcmp(name, "selftest_veldiv") == 0) {
+        // mismatches of the marching kernel's shared-reciprocal velocity divisions (step_march.hpp div2_shared) against the IEEE quotient on 2^28 pseudo-random
+        // and built (numerator, density) pairs inside the ranges its guard admits, counted on the device (tests/test_gpu_veldiv.py)
+        wt_handle *hm = const_cast<wt_handle *>(h);
+        if (hipSetDevice(h->device) != hipSuccess) return fail(WT_ERR_HIP, "hipSetDevice");
+        if (!hm->d_nbad && hipMalloc((void **)&hm->d_nbad, 2 * sizeof(unsigned int)) != hipSuccess) return fail(WT_ERR_HIP, "selftest: hipMalloc");
+        if (hipMemsetAsync(hm->d_nbad, 0, 2 * sizeof(unsigned int), h->s_compute) != hipSuccess) return fail(WT_ERR_HIP, "selftest: memset");
+        hipLaunchKernelGGL(k_check_veldiv, dim3(1024), dim3(256), 0, h->s_compute, 0x5eedULL, 256, hm->d_nbad);
+        unsigned int nbad = 1;
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nbad, hm->d_nbad, sizeof(nbad), hipMemcpyDeviceToHost, h->s_compute) != hipSuccess ||
+            hipStreamSynchronize(h->s_compute) != hipSuccess) return fail(WT_ERR_HIP, "selftest: launch");
+        *value = (double)nbad;
+        return WT_OK;
+    }
     if (strncmp(name, "selftest_fastdiv", 16) == 0) {
         // mismatches of the fast divisions by "selftest_tau" against the IEEE quotient, counted on the device (tests/test_gpu_fastdiv.py):
         //   selftest_fastdiv32_3 / _2: the three- / two-operation binary32 forms over all 2^23 significands and both signs (the library's own proof);

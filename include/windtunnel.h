@@ -134,6 +134,9 @@ WT_API const char *wt_version(void);
  *   "selftest_tau" + the read-only "selftest_fastdiv32_3" / "selftest_fastdiv32_2" / "selftest_fastdiv64": mismatches of the three fast
  *       divisions against the IEEE quotient for that tau, counted on the device — the binary32 forms over all 2^23 significands and both
  *       signs, the binary64 form on 2^28 pseudo-random and boundary-hugging numerators (tests/test_gpu_fastdiv.py).
+ *   "selftest_veldiv" (read-only): mismatches of the four-step fp32 kernel's two velocity divisions on one shared reciprocal
+ *       (csrc/step_march.hpp div2_shared) against the IEEE quotient, counted on the device over 2^28 pseudo-random and built
+ *       (momentum, density) pairs inside the ranges the kernel's guard admits (tests/test_gpu_veldiv.py).
  *   "fast_math" (default 0, fp32, OPT-IN, NOT bit-identical): the marching kernels collide with contracted arithmetic — fused
  *       multiply-adds, v_rcp / v_rsq for the divisions and the square root (csrc/d2q9.hpp collide_contracted).  Held to BASELINE.md's
  *       tolerance against the oracle (|d rho| <= 1e-5, |d u| <= 5e-6; tests/test_gpu_fast_math.py), +19 % on 4096^2, +36 % on a
