@@ -397,6 +397,10 @@ __device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bo
     return inv * a + (T(1.0) - inv) * *h;
 }
 
+// What a step kernel writes into a far-field cell (inlet column, top and bottom rows): the equilibrium of the axial free stream (U0, 0)
+// (the page's), or that of an inclined one (U0, V0) (include/wt_polar.h "Inclined free stream").
+enum : int { FAR_AXIAL = 0, FAR_INCLINED = 1 };
+
 // binary64 with the four-operation division by tau (see "Division by the relaxation time"): operation for operation collide<double> up to the
 // relaxation; the division is the fast one iff every lane of the wave holds finite populations below 2^100 (else, and with fd.on64 = 0, IEEE).
 __device__ __forceinline__ void collide_fd64(const double (&fin)[9], const FastDiv &fd, double (&fo)[9], double &rho, double &ux, double &uy)

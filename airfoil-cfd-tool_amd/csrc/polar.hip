@@ -29,6 +29,11 @@
 // step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
 // collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction with the interpolated link term.  A
 // batch that has it off launches the kernels it always launched, with the arguments they always had.
+//
+// The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_wind_batch, the same
+// step_tile with feq(1, U0, V0) in its far-field cells and one more value per member, with either collision and either wall rule,
+// and wtp_init_equilibrium fills the members by k_fill_wind.  A batch that has it off launches the kernels it always launched, with
+// the arguments they always had.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -122,6 +127,10 @@ struct wtp_batch {
     bool ibb = false;
     void *wq = nullptr;                  // [B][8] planes of T laid out like population planes 1..8, members q_stride elements apart
     long q_stride = 0;
+    // inclined free stream (wtp_enable_wind); the pointer is null until then
+    bool wind = false;
+    void *wind_v = nullptr;              // [B] of T: the cross-flow V0 of every member
+    std::vector<double> wind_host;       // ... as the caller gave them (doubles), for wtp_init_equilibrium
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -220,6 +229,55 @@ __global__ __launch_bounds__(256) void k_step_ibb_batch(const T *__restrict__ fs
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL_INTERP>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
                                                            tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t,
                                                            lane, 0, 0, 0, c, wq + m * qstride);
+}
+
+// The same step with an inclined free stream (include/wt_polar.h "Inclined free stream"), with either collision and either wall rule:
+// k_step_ibb_batch's grid, walk and arguments, and vwind[m] = V0 of the member beside its tau and U0.  In the step, a far-field cell is
+// one that is not solid, not in the outlet column, and lies in column 0, row 0 or row NY-1.  Such a cell writes feq_k(1, U0, V0) and
+// stores (1, U0, V0), feq being feq_all.  The branch order (solid, then outlet, then far field, then interior) does not change, and
+// nothing else in the step changes.  With V0 = 0 every value has k_step_batch's (k_step_les_batch's, k_step_ibb_batch's) bits, because
+// ex*U0 + ey*0 and U0*U0 + 0*0 are exact.  cles is read only for COLLIDE_LES and wq only for WALL_INTERP.  A kernel of its own name, so
+// that a batch with the model off runs the code object it always ran.
+// Waves per SIMD: left to itself the compiler gives every kernel with this many arguments 109 to 124 VGPRs in fp32 (4 waves), whatever the
+// far field, the collision or the wall rule is; an unused pointer argument added to k_step_batch does the same.  Asked for k_step_batch's
+// (k_step_les_batch's) occupancy it allocates 79 to 95 VGPRs, theirs within 2, without scratch, interpolated walls included.
+template <typename T, bool EMIT, int COLL>
+constexpr int wind_waves() { return sizeof(T) == 8 ? 4 : (EMIT || COLL == COLLIDE_LES ? 5 : 6); }
+
+template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wind_waves<T, EMIT, COLL>()))) void k_step_wind_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
+                                                         const T *__restrict__ vwind, int rev)
+{
+    const int lane = threadIdx.x & 63;
+    const long ntiles = (long)g.nxl * tiles_per_col;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= ntiles) return;
+    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const T tau = params[2 * m], U0 = params[2 * m + 1], V0 = vwind[m];
+    T c = T(0.0);
+    if constexpr (COLL == COLLIDE_LES) c = cles[m];
+    const T *q = nullptr;
+    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
+    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t,
+                                                                  lane, 0, 0, 0, c, q, V0);
+}
+
+// The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
+// the nine values of wind_init and (1, u0, v0) in the macroscopic planes.
+template <typename T>
+__global__ void k_fill_wind(T *__restrict__ f0, T *__restrict__ f1, T *__restrict__ macro, Geom g, Init9<T> iv, T v0)
+{
+    const long n = g.plane;
+    const long mp = (long)g.nxl * g.pitch;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) { f0[k * n + t] = iv.v[k]; f1[k * n + t] = iv.v[k]; }
+        if (t < mp) { macro[t] = T(1.0); macro[mp + t] = iv.u0; macro[2 * mp + t] = v0; }
+    }
 }
 
 // "The last block of a member finishes the sum": called by every thread of a block once the block's partials of member m are
@@ -616,7 +674,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -695,7 +753,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -817,13 +875,35 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
     return WT_OK;
 }
 
+// The equilibrium populations of a uniform flow (u0, v0) at rho = 1, evaluated in double as equilibrium_init evaluates them and rounded
+// to T once: w (1 + 3 eu + 4.5 eu eu - 1.5 uu) with eu = ex u0 + ey v0 and uu = u0 u0 + v0 v0.  With v0 = 0 these are equilibrium_init's bits.
+template <typename T>
+static Init9<T> wind_init(double u0, double v0)
+{
+    const double w0 = 4.0 / 9.0, ws = 1.0 / 9.0, wd = 1.0 / 36.0;
+    Init9<T> iv;
+    for (int k = 0; k < 9; k++) {
+        const double w = (k == 0) ? w0 : (k <= 4 ? ws : wd);
+        const double eu = ex_of(k) * u0 + ey_of(k) * v0, uu = u0 * u0 + v0 * v0;
+        iv.v[k] = (T)(w * (1 + 3 * eu + 4.5 * eu * eu - 1.5 * uu));
+    }
+    iv.u0 = (T)u0;
+    return iv;
+}
+
 template <typename T>
 static int init_impl(wtp_batch *b, const double *u0)
 {
     for (int m = 0; m < b->members; m++) {
-        const Init9<T> iv = equilibrium_init<T>(u0[m]);          // wt_init_equilibrium's values
-        hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m),
-                           b->g, iv);
+        if (b->wind) {
+            const double v0 = b->wind_host[(size_t)m];
+            hipLaunchKernelGGL(k_fill_wind<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m), b->g,
+                               wind_init<T>(u0[m], v0), (T)v0);
+        } else {
+            const Init9<T> iv = equilibrium_init<T>(u0[m]);      // wt_init_equilibrium's values
+            hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m),
+                               b->g, iv);
+        }
         HIP_TRY(hipGetLastError());
     }
     return WT_OK;
@@ -934,6 +1014,13 @@ static int sample_into(wtp_batch *b, int row)
     return WT_OK;
 }
 
+// k_step_wind_batch of one collision and one wall rule, emitting or not: all of them take the same arguments.
+template <typename T, int COLL, int WALL>
+static auto wind_kernel(bool emit)
+{
+    return emit ? k_step_wind_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_wind_batch<T, false, WT_LOADMODE, COLL, WALL>;
+}
+
 template <typename T>
 static int step_impl(wtp_batch *b, int nsteps, int sample_every)
 {
@@ -946,7 +1033,13 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
         const int rev = (int)(b->steps_done & 1);
-        if (b->ibb) {
+        if (b->wind) {
+            const auto k_step = b->ibb ? (b->les ? wind_kernel<T, COLLIDE_LES, WALL_INTERP>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_INTERP>(emit))
+                                       : (b->les ? wind_kernel<T, COLLIDE_LES, WALL_HALFWAY>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_HALFWAY>(emit));
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
+                               (const T *)b->wind_v, rev);
+        } else if (b->ibb) {
             const auto k_step = b->les ? (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_LES> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_LES>)
                                        : (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_BGK> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_BGK>);
             hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
@@ -1021,6 +1114,34 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? upload_les<float>(b, cs) : upload_les<double>(b, cs));
     b->les = true;
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// inclined free stream
+// ------------------------------------------------------------------------------------------
+// V0 of every member, rounded to T once.
+template <typename T>
+static int upload_wind(wtp_batch *b, const double *v0)
+{
+    std::vector<T> v((size_t)b->members);
+    for (size_t m = 0; m < v.size(); m++) v[m] = (T)v0[m];
+    if (!b->wind_v) HIP_TRY(hipMalloc(&b->wind_v, v.size() * sizeof(T)));
+    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
+    HIP_TRY(hipMemcpy(b->wind_v, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return WT_OK;
+}
+
+extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
+{
+    WT_TRY(check_batch(b));
+    if (!v0) { b->wind = false; return WT_OK; }  // (steps already enqueued were launched with the model on: stream order)
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(v0[m]) || std::fabs(v0[m]) > 0.35) return fail(WT_ERR_ARG, "v0[%d] must be finite and in [-0.35, 0.35]", m);
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? upload_wind<float>(b, v0) : upload_wind<double>(b, v0));
+    b->wind_host.assign(v0, v0 + b->members);
+    b->wind = true;
     return WT_OK;
 }
 

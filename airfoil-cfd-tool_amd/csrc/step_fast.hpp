@@ -157,11 +157,14 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // COLL: the collision of interior fluid cells, COLLIDE_BGK or COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp).
 // WALL: the wall rule of interior fluid cells, WALL_HALFWAY or WALL_INTERP with the wall distances `wq`, eight planes laid out like
 // population planes 1..8, pad column included (wall_incoming, d2q9.hpp).  Only TILE_GENERAL tiles can own a link: no other path reads them.
-template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY>
+// FAR: what a far-field cell holds, FAR_AXIAL (feq(1, U0, 0)) or FAR_INCLINED with the cross-flow `V0` (feq(1, U0, V0)); the three places
+// that form the far field take it: site_general, the top and bottom rows of a TILE_FAST tile, and TILE_INLET.
+template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR = FAR_AXIAL>
 __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
-                                          int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr)
+                                          int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr,
+                                          T V0 = T(0.0))
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
@@ -182,7 +185,9 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
         for (int v = 0; v < N; v++) {
             const int j = row0 + v * 64 + lane;
             if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) {
-                if constexpr (WALL == WALL_INTERP) site_general<T, COLL, WALL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch);
+                if constexpr (FAR == FAR_INCLINED)
+                    site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0);
+                else if constexpr (WALL == WALL_INTERP) site_general<T, COLL, WALL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch);
                 else site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
             }
         }
@@ -216,7 +221,8 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             fin[8] = shift_from_above<T>(r8, p8, lane);
         }
         T feq0[9];
-        feq_all<T>(T(1.0), U0, T(0.0), feq0);      // far-field populations (html:314-322)
+        if constexpr (FAR == FAR_INCLINED) feq_all<T>(T(1.0), U0, V0, feq0);
+        else feq_all<T>(T(1.0), U0, T(0.0), feq0);      // far-field populations (html:314-322)
 #pragma unroll
         for (int v = 0; v < N; v++) {
             T a[9], o[9], rho, ux, uy;
@@ -230,7 +236,8 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             for (int k = 0; k < 9; k++) out[k].v[v] = far ? feq0[k] : o[k];
             mrho.v[v] = far ? T(1.0) : rho;
             mux.v[v] = far ? U0 : ux;
-            muy.v[v] = far ? T(0.0) : uy;
+            if constexpr (FAR == FAR_INCLINED) muy.v[v] = far ? V0 : uy;
+            else muy.v[v] = far ? T(0.0) : uy;
         }
     } else if (cls == TILE_SOLID) {
 #pragma unroll
@@ -239,13 +246,18 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
         for (int v = 0; v < N; v++) { mrho.v[v] = T(1.0); mux.v[v] = T(0.0); muy.v[v] = T(0.0); }
     } else if (cls == TILE_INLET) {
         T feq0[9];
-        feq_all<T>(T(1.0), U0, T(0.0), feq0);
+        if constexpr (FAR == FAR_INCLINED) feq_all<T>(T(1.0), U0, V0, feq0);
+        else feq_all<T>(T(1.0), U0, T(0.0), feq0);
 #pragma unroll
         for (int k = 0; k < 9; k++)
 #pragma unroll
             for (int v = 0; v < N; v++) out[k].v[v] = feq0[k];
 #pragma unroll
-        for (int v = 0; v < N; v++) { mrho.v[v] = T(1.0); mux.v[v] = U0; muy.v[v] = T(0.0); }
+        for (int v = 0; v < N; v++) {
+            mrho.v[v] = T(1.0); mux.v[v] = U0;
+            if constexpr (FAR == FAR_INCLINED) muy.v[v] = V0;
+            else muy.v[v] = T(0.0);
+        }
     } else {   // TILE_OUTLET: copy the un-streamed populations of column i-1 (html:301-312)
 #pragma unroll
         for (int k = 0; k < 9; k++) out[k] = vload<T, NT>(s + k * P + c - g.pitch);

@@ -13,7 +13,9 @@ fluctuation about it (:func:`mean_flow`: Reynolds stresses, pressure r.m.s.), fr
 At airfoil Reynolds numbers, where tau falls to within 1e-3 of 0.5, the Smagorinsky subgrid viscosity
 (``PolarEngine.enable_les``, ``run_polar(les=0.1)``) keeps the members off the stability net.  With interpolated bounce-back
 (``PolarEngine.enable_interpolated_walls``, ``run_polar(walls="interpolated")``) the wall of every member is the panel polygon
-itself, through a wall distance per link (``geometry.wall_distances``), and not the staircase of its raster mask.
+itself, through a wall distance per link (``geometry.wall_distances``), and not the staircase of its raster mask.  With an
+inclined free stream (``PolarEngine.enable_wind``, ``run_polar(frame="wind")``) every member holds the same body at 0 degrees
+and the angle of attack turns its free stream, so the polar carries no raster jump from angle to angle.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -45,9 +47,12 @@ EXPORTS = (
     "wtp_enable_mean", "wtp_mean_sums",
     "wtp_enable_les",
     "wtp_enable_ibb", "wtp_set_wall_q",
+    "wtp_enable_wind",
 )
 
 WALLS = ("staircase", "interpolated")                              # run_polar's wall rules
+FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
+WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
 
 _lib = None
@@ -94,6 +99,7 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_enable_les": ([B, dp], c_int),
         "wtp_enable_ibb": ([B, c_int], c_int),
         "wtp_set_wall_q": ([B, c_int, c_int, c_void_p], c_int),
+        "wtp_enable_wind": ([B, dp], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -135,6 +141,7 @@ class PolarEngine:
         self.mean_enabled = False
         self.les_enabled = False
         self.interpolated_walls = False
+        self._wind = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
@@ -288,6 +295,24 @@ class PolarEngine:
             raise ValueError(f"wall distances must have shape [count][8][NY][NX] = [count]{(8, self.ny, self.nx)}, got {a.shape}")
         _check(self._lib.wtp_set_wall_q(self._b, int(first), int(a.shape[0]), a.ctypes.data_as(c_void_p)))
 
+    def enable_wind(self, v0) -> None:
+        """Incline the free stream (wt_polar.h): v0 is the cross-flow of the far field, one value or [B], each finite with
+        |v0| <= 0.35; the far-field cells hold the equilibrium of (u0, v0) from the next step on, and the next init_equilibrium
+        starts every member from it.  A member with v0 = 0 stays an axial member, bit for bit.  None switches the model off
+        again.  The flow state, the history and every running sum are kept; combines with enable_les and
+        enable_interpolated_walls, independent of the read-outs, which stay in lattice axes (wind_axes)."""
+        if v0 is None:
+            _check(self._lib.wtp_enable_wind(self._b, None))
+            self._wind = False
+            return
+        v = _f64(v0, self.members)
+        _check(self._lib.wtp_enable_wind(self._b, _dp(v)))
+        self._wind = True
+
+    @property
+    def wind_enabled(self) -> bool:
+        return self._wind
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -323,7 +348,8 @@ class PolarPoint:
     samples: int                 # samples with a body surface (surf > 0)
     finite: bool                 # every sample finite
     clamp_events: Tuple[int, int]
-    history: Dict[str, np.ndarray] = field(repr=False, default_factory=dict)   # step, fx, fy, surf, rev of this angle
+    # step, fx, fy, surf, rev of this angle; fx, fy (and fx_mex, fy_mex) are wind-axis forces in a run_polar(frame="wind") sweep
+    history: Dict[str, np.ndarray] = field(repr=False, default_factory=dict)
     cm_mean: Optional[float] = None      # pitching-moment coefficient about the quarter chord, nose-up positive (None: not sampled)
     cm_std: Optional[float] = None
     surface: Optional[Dict[str, np.ndarray]] = field(repr=False, default=None)   # x_over_c, cp_upper, cp_lower per body column
@@ -365,9 +391,12 @@ class PolarResult:
     # The wall rule of the sweep, "staircase" (half-way bounce-back on the raster mask) or "interpolated".  Init-only, as
     # PolarPoint's totals are: accepted by the constructor after the fields above and kept as an attribute.
     walls: InitVar[str] = "staircase"
+    # How the angles were set: "body" (a rotated body per angle) or "wind" (one body at 0 degrees, the free stream turned).  Init-only too.
+    frame: InitVar[str] = "body"
 
-    def __post_init__(self, walls):
+    def __post_init__(self, walls, frame):
         self.walls = walls
+        self.frame = frame
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -384,6 +413,15 @@ def moment_coefficient(mz, u0: float, nx: int):
     """Cm = -Mz / (U0^2/2 * chord_cells(nx)^2): Mz is counter-clockwise positive and the nose points in -x, so nose-up is clockwise."""
     c = chord_cells(nx)
     return -np.asarray(mz, np.float64) / (0.5 * u0 * u0 * (c * c))
+
+
+def wind_axes(fx, fy, alpha):
+    """Lattice-axis forces of a member whose free stream is inclined by `alpha` degrees, in wind axes: float64
+    (drag-axis, lift-axis) = (fx cos a + fy sin a, -fx sin a + fy cos a), elementwise."""
+    fx, fy = np.asarray(fx, np.float64), np.asarray(fy, np.float64)
+    a = np.radians(np.asarray(alpha, np.float64))
+    c, s = np.cos(a), np.sin(a)
+    return fx * c + fy * s, -fx * s + fy * c
 
 
 def quarter_chord(nx: int, ny: int) -> Tuple[float, float]:
@@ -478,7 +516,7 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False, walls: str = "staircase",
+              total_forces: bool = False, mean_fields: bool = False, walls: str = "staircase", frame: str = "body",
               les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
@@ -497,7 +535,16 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     `walls`: "staircase", the default, reflects half-way to the next cell of the raster mask, with the bits it always had;
     "interpolated" reflects by linear interpolated bounce-back at the panel polygon of each angle, through the wall distances
     geometry.wall_distances computes from the Geometry the mask came from, from the first warm-up step on
-    (PolarEngine.enable_interpolated_walls).  The momentum exchange (`total_forces`) then uses the interpolated link term."""
+    (PolarEngine.enable_interpolated_walls).  The momentum exchange (`total_forces`) then uses the interpolated link term.
+    `frame`: "body", the default, rasterises a body rotated by each angle, with the bits it always had.  "wind" keeps one body at
+    0 degrees in every member (one mask, and with walls="interpolated" one set of wall distances) and inclines the member's free
+    stream instead: member m runs at (u0 cos a, u0 sin a), from the start state on (PolarEngine.enable_wind); tau and `re` are
+    formed from the magnitude u0.  The sampled forces are turned into wind axes (wind_axes) before the statistics, so CL is
+    across the free stream and CD along it, and PolarPoint.history then holds wind-axis fx, fy, fx_mex, fy_mex; the moment, its
+    reference point and the surface pressure (x/c of the unrotated body) are unchanged.  Every |angle| must be at most 30
+    degrees: the trailing edge sits 0.42 chords from the outlet and the half height is 0.46 chords, so up to there the wake
+    leaves through the outlet.  The top and bottom rows stay equilibrium rows, now with inflow and outflow, and no blockage
+    correction is made: the level of CL and CD differs from the body frame's (README)."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -511,21 +558,35 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             raise ValueError(f"les must be a finite Smagorinsky constant in [0, 0.5], got {les!r}")
     if walls not in WALLS:
         raise ValueError(f"walls must be one of {WALLS}, got {walls!r}")
+    if frame not in FRAMES:
+        raise ValueError(f"frame must be one of {FRAMES}, got {frame!r}")
+    wind = frame == "wind"
+    if wind and any(not abs(a) <= WIND_ALPHA_MAX for a in alphas):
+        raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
     nx, ny, u0 = int(nx), int(ny), float(u0)
     tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
     if warmup_steps is None:
         warmup_steps = int(math.ceil(2 * nx / u0))
     warmup_steps = int(warmup_steps)
     user = geo.round_coords(coords) if coords is not None and len(coords) else []
-    geoms = [geo.build_geometry(nx, ny, a, user, shape) for a in alphas]
+    if wind:                                                   # one body, at 0 degrees, in every member
+        geoms = [geo.build_geometry(nx, ny, 0.0, user, shape)] * len(alphas)
+        ux0 = np.array([u0 * math.cos(math.radians(a)) for a in alphas])
+        vy0 = np.array([u0 * math.sin(math.radians(a)) for a in alphas])
+    else:
+        geoms = [geo.build_geometry(nx, ny, a, user, shape) for a in alphas]
+        ux0 = u0
     masks = np.stack([g.mask for g in geoms])
     with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device) as eng:
         eng.set_masks(masks)
         if walls == "interpolated":
             eng.enable_interpolated_walls()
+            q = geo.wall_distances(geoms[0].xp, geoms[0].yp, geoms[0].mask, nx, ny) if wind else None
             for m, g in enumerate(geoms):                      # (one member at a time: eight float64 planes each on the host)
-                eng.set_wall_distances(geo.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
-        eng.init_equilibrium(u0)
+                eng.set_wall_distances(q if wind else geo.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
+        if wind:
+            eng.enable_wind(vy0)
+        eng.init_equilibrium(ux0)
         if loads:
             eng.enable_loads(*quarter_chord(nx, ny))
         if total_forces:
@@ -535,13 +596,17 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         if les is not None:
             eng.enable_les(les)
         if warmup_steps:
-            eng.step(warmup_steps, tau, u0)
+            eng.step(warmup_steps, tau, ux0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
-        eng.step(samples * sample_every, tau, u0, sample_every=sample_every)
+        eng.step(samples * sample_every, tau, ux0, sample_every=sample_every)
         h = eng.history()
         rho_ev, u_ev = eng.clamp_events()
-        surfaces = [surface_cp(eng.surface(m), a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
+        surfaces = [surface_cp(eng.surface(m), 0.0 if wind else a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
         means = [mean_flow(eng.mean_sums(m), u0) for m in range(len(alphas))] if mean_fields else [None] * len(alphas)
+    if wind:                                                   # lattice axes -> wind axes, every sample of every member
+        h["fx"], h["fy"] = wind_axes(h["fx"], h["fy"], alphas)
+        if total_forces:
+            h["fx_mex"], h["fy_mex"] = wind_axes(h["fx_mex"], h["fy_mex"], alphas)
     points = [polar_point(a, h["step"], h["fx"][:, m], h["fy"][:, m], h["surf"][:, m], h["rev"][:, m], u0, nx, (rho_ev[m], u_ev[m]),
                           mz=h["mz"][:, m] if loads else None, surface=surfaces[m],
                           **({k: h[k][:, m] for k in ("fx_mex", "fy_mex", "mz_mex", "links")} if total_forces else {}))
@@ -549,7 +614,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     for p, mean in zip(points, means):
         p.mean = mean
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
-                       walls=walls)
+                       walls=walls, frame=frame)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

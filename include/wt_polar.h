@@ -218,6 +218,35 @@ WTP_API int wtp_enable_ibb(wtp_batch *b, int on);
  * link are never read.  wtp_set_masks resets the distances of the members it touches to 0.5: a distance belongs to a mask, so
  * upload the distances after the masks. */
 WTP_API int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q);
+/*
+ * Inclined free stream: the angle of attack set by turning the free stream, not the body.  Each angle of a sweep otherwise
+ * rasterises a rotated body into its own mask, and between neighbouring angles the body jumps by whole cells.  With one body
+ * at 0 degrees in every member and the member's free stream inclined, the mask, the links and the wall distances are the
+ * same at every angle.  It is another far field, per member and opt-in.  Definition:
+ *   Far field.  Member m holds a cross-flow V0[m] of the batch's dtype T, rounded once from the caller's double.  In the
+ *   step, a far-field cell is one that is not solid, not in the outlet column, and lies in column 0, row 0 or row NY-1.
+ *   Without the model such a cell writes feq_k(1, U0, 0) and stores (1, U0, 0).  With the model on it writes
+ *   feq_k(1, U0, V0) and stores (1, U0, V0).  feq is the step's own: oracle/lbm_numpy.feq's order, one rounding per
+ *   operation in T, no contraction.  U0 is wtp_step's u0[m].  The branch order (solid, then outlet, then far field, then
+ *   interior) does not change.  Nothing else in the step changes: the interior branch with either collision and either
+ *   wall rule, the outlet, the solid cells and the stability net all stay as they are.  With V0 = 0 every value has the
+ *   bits it has without the model, because ex*U0 + ey*0 and U0*U0 + 0*0 are exact.
+ *   Start.  While the model is on, wtp_init_equilibrium fills every cell of member m with feq_k(1, u0, v0), evaluated in
+ *   double on the host: w*(1 + 3*eu + 4.5*eu*eu - 1.5*uu) with eu = ex*u0 + ey*v0 and uu = u0*u0 + v0*v0, rounded to T
+ *   once.  The macroscopic planes become (1, (T)u0, (T)v0).  With v0 = 0 these are the bits of the start without the model.
+ *   Read-outs.  Forces, loads, momentum exchange and mean fields are unchanged.  They stay in lattice axes: the caller
+ *   turns (fx, fy) into the wind axes (drag along the free stream, lift across it).  The top and bottom rows now carry
+ *   inflow and outflow; they stay equilibrium rows.
+ *
+ * wtp_enable_wind switches the model on.  v0: [B], each finite with |v0| <= 0.35 (the velocity bound of the stability net),
+ * else WT_ERR_ARG before any device call (and the batch is left as it was).  v0 == NULL switches it off again: the following
+ * steps launch the kernels, and compute the bits, of a batch that never enabled it.  The far field changes from the next
+ * wtp_step, the start state from the next wtp_init_equilibrium.  The flow state, the step count, the history and every
+ * running sum are kept.  Calling it again replaces the values.  It combines with wtp_enable_les and wtp_enable_ibb and is
+ * independent of the read-outs.  A batch that never calls it launches the kernels it always launched.  A member with
+ * V0 != 0 has no libwindtunnel twin.
+ */
+WTP_API int wtp_enable_wind(wtp_batch *b, const double *v0);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -1,0 +1,207 @@
+"""The inclined free stream of batched sweeps (wtp_enable_wind, polar.py): what needs no GPU."""
+import ctypes
+import dataclasses
+import inspect
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import _polar_isa
+import _wind_reference as wind
+
+WT_ERR_ARG = -1
+
+
+# ---- the C-ABI without a GPU -------------------------------------------------------------------
+def test_new_entry_point_is_declared_exported_and_bound(pkg):
+    from airfoil_cfd_tool_amd.polar import EXPORTS, POLAR_LIB_PATH
+    with open(os.path.join(ROOT, "include", "wt_polar.h")) as fh:
+        text = fh.read()
+    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = subprocess.run(["nm", "-D", "--defined-only", POLAR_LIB_PATH], check=True, capture_output=True, text=True).stdout
+    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    lib = pkg.polar.load_polar_library()
+    name = "wtp_enable_wind"
+    assert re.search(r"\bint\s+%s\s*\(\s*wtp_batch\s*\*\s*b\s*,\s*const\s+double\s*\*\s*v0\s*\)" % name, header)
+    assert name in syms and name in EXPORTS
+    assert lib.wtp_enable_wind.argtypes == [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+
+    # the header, the kernel's comment and the reference carry one definition of the far-field cell
+    def words(path):
+        with open(path) as fh:
+            return " ".join(" ".join(re.sub(r"^\s*(/?\*+/?|//)", "", line) for line in fh.read().splitlines()).split())
+    for path in (os.path.join(ROOT, "include", "wt_polar.h"), os.path.join(ROOT, "airfoil-cfd-tool_amd", "csrc", "polar.hip"),
+                 os.path.join(ROOT, "tests", "_wind_reference.py")):
+        doc = words(path)
+        for needle in ("a far-field cell is one that is not solid, not in the outlet column, and lies in column 0, row 0 or row NY-1",
+                       "feq_k(1, U0, V0) and stores (1, U0, V0)"):
+            assert needle in doc, (path, needle)
+    assert "no libwindtunnel twin" in words(os.path.join(ROOT, "include", "wt_polar.h")).split("Inclined free stream")[1]
+    v = lib.wtp_version()
+    for phrase in (b"inclined free stream", b"interpolated bounce-back", b"Smagorinsky", b"mean fields", b"momentum exchange", b"surface loads"):
+        assert phrase in v, phrase
+
+
+def test_null_batch_is_an_argument_error(pkg):
+    lib = pkg.polar.load_polar_library()
+    v0 = (ctypes.c_double * 4)(0.0, 0.01, 0.02, 0.03)
+    assert lib.wtp_enable_wind(None, v0) == WT_ERR_ARG
+    assert b"null batch" in lib.wtp_last_error()
+    assert lib.wtp_enable_wind(None, None) == WT_ERR_ARG
+
+
+# ---- run_polar, PolarEngine, PolarResult -------------------------------------------------------
+def _no_engine(pkg, monkeypatch):
+    def no_engine(*a, **k):
+        raise AssertionError("the engine was created")
+    monkeypatch.setattr(pkg.polar, "PolarEngine", no_engine)
+
+
+@pytest.mark.parametrize("bad", ["stream", "", None, 1, "Wind"])
+def test_run_polar_validates_frame_before_creating_the_engine(pkg, monkeypatch, bad):
+    _no_engine(pkg, monkeypatch)
+    with pytest.raises(ValueError, match="frame"):
+        pkg.run_polar([4.0], nx=96, ny=48, frame=bad)
+
+
+@pytest.mark.parametrize("alphas", [[30.5], [4.0, -31.0], [float("nan")]])
+def test_run_polar_rejects_wind_angles_beyond_30_degrees_before_creating_the_engine(pkg, monkeypatch, alphas):
+    _no_engine(pkg, monkeypatch)
+    with pytest.raises(ValueError, match="30"):
+        pkg.run_polar(alphas, nx=96, ny=48, frame="wind")
+    if not any(math.isnan(a) for a in alphas):
+        with pytest.raises(AssertionError, match="engine was created"):      # (the body frame takes them, as it always did)
+            pkg.run_polar(alphas, nx=96, ny=48, frame="body")
+
+
+def test_run_polar_engine_and_result_expose_the_switch(pkg):
+    from airfoil_cfd_tool_amd.polar import FRAMES, PolarResult
+    assert FRAMES == ("body", "wind")
+    sig = inspect.signature(pkg.run_polar)
+    assert sig.parameters["frame"].default == "body" and sig.parameters["frame"].kind is inspect.Parameter.KEYWORD_ONLY
+    assert list(sig.parameters)[-2:] == ["frame", "les"]
+    assert callable(pkg.PolarEngine.enable_wind) and isinstance(pkg.PolarEngine.wind_enabled, property)
+    names = [f.name for f in dataclasses.fields(PolarResult)]
+    assert names == ["points", "nx", "ny", "tau", "u0", "warmup_steps", "sample_every", "les"]
+    r = PolarResult(points=[], nx=320, ny=160, tau=0.58, u0=0.06, warmup_steps=0, sample_every=12)
+    assert r.frame == "body" and r.walls == "staircase"
+    r = PolarResult(points=[], nx=320, ny=160, tau=0.58, u0=0.06, warmup_steps=0, sample_every=12, walls="interpolated", frame="wind")
+    assert (r.walls, r.frame) == ("interpolated", "wind")
+    assert PolarResult([], 320, 160, 0.58, 0.06, 0, 12, None, "staircase", "wind").frame == "wind"      # (after walls)
+
+
+def test_wind_axes(pkg):
+    wind_axes = pkg.polar.wind_axes
+    rng = np.random.default_rng(5)
+    fx, fy = rng.normal(size=(7, 3)), rng.normal(size=(7, 3))
+    d, l = wind_axes(fx, fy, 0.0)
+    assert d.dtype == l.dtype == np.float64 and np.array_equal(d, fx) and np.array_equal(l, fy)
+    d, l = wind_axes(fx, fy, 90.0)
+    assert np.abs(d - fy).max() <= 1e-15 and np.abs(l + fx).max() <= 1e-15
+    alphas = np.array([4.0, -11.5, 30.0])                                   # one angle per member (the last axis)
+    d, l = wind_axes(fx.astype(np.float32), fy.astype(np.float32), alphas)
+    assert d.dtype == np.float64 and d.shape == (7, 3)
+    f32x, f32y = fx.astype(np.float32).astype(np.float64), fy.astype(np.float32).astype(np.float64)
+    assert np.allclose(np.hypot(d, l), np.hypot(f32x, f32y), rtol=1e-14, atol=0)
+    a = math.radians(4.0)
+    assert d[2, 0] == f32x[2, 0] * math.cos(a) + f32y[2, 0] * math.sin(a) and l[2, 0] == -f32x[2, 0] * math.sin(a) + f32y[2, 0] * math.cos(a)
+    # a pure lift across a stream inclined by alpha: lattice force (-L sin a, L cos a) -> (0, L)
+    d, l = wind_axes(-2.0 * math.sin(a), 2.0 * math.cos(a), 4.0)
+    assert abs(d) < 1e-15 and abs(l - 2.0) < 1e-15
+
+
+# ---- the reference -----------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_reference_with_v0_zero_is_the_oracle(pkg, oracle_np, dtype):
+    nx, ny, u0, tau = 96, 48, 0.06, 0.58
+    mask = pkg.geometry.build_geometry(nx, ny, 6.0, None, "naca2412").mask
+    f, macro = oracle_np.equilibrium_init(nx, ny, u0, dtype)
+    g, mg = wind.wind_init(nx, ny, u0, 0.0, dtype)
+    assert f.tobytes() == g.tobytes() and all(a.tobytes() == b.tobytes() for a, b in zip(macro, mg))
+    for _ in range(100):
+        f, mf = oracle_np.step(f, mask, tau, u0)
+        g, mg = wind.wind_step(oracle_np.step, g, mask, tau, u0, 0.0)
+    assert f.tobytes() == g.tobytes()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(mf, mg))
+    assert np.ptp(f[1]) > 1e-3                                           # (a flow, not the initial state)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_reference_with_v0_differs_from_the_axial_step_in_far_field_cells_only(pkg, oracle_np, dtype):
+    nx, ny, u0, v0, tau = 96, 48, 0.0598, 0.0042, 0.58
+    mask = pkg.geometry.build_geometry(nx, ny, 0.0, None, "naca2412").mask.copy()
+    mask[0, 40:44] = 255                                                 # solid cells in a far-field row: the solid branch wins
+    mask[20:24, 0] = 255
+    f, (rho, ux, uy) = wind.wind_init(nx, ny, u0, v0, dtype)
+    assert (uy == dtype(v0)).all() and (ux == dtype(u0)).all() and (rho == 1).all()
+    assert not np.array_equal(f[2], f[4]) and not np.array_equal(f[5], f[8])         # (a cross-flow)
+    a, ma = oracle_np.step(f, mask, tau, u0)
+    b, mb = wind.wind_step(oracle_np.step, f, mask, tau, u0, v0)
+    far = wind.far_field(mask)
+    assert int(far.sum()) == ny + 2 * (nx - 2) - 8 and not far[:, nx - 1].any() and not far[mask != 0].any()
+    diff = (a != b).any(axis=0)
+    assert diff[far].all() and not diff[~far].any()
+    assert (mb[2][far] == dtype(v0)).all() and np.array_equal(mb[2][~far], ma[2][~far])
+    assert np.array_equal(ma[0], mb[0]) and np.array_equal(ma[1], mb[1])
+
+
+def test_the_wind_frame_removes_the_saw_tooth_on_the_reference(pkg, oracle_np):
+    """NACA 2412 at 96x48, fp32, tau 0.58, |U| 0.06, angles 4, 5, 6 degrees; warm-up 3200 steps, then the pressure forces every 12th
+    of 600 steps, in both frames.  Measured when the feature was proposed: |CL(4) - 2 CL(5) + CL(6)| 0.0015 with the free stream
+    turned against 0.239 with the body turned, slopes 0.0978 and 0.0979 per degree."""
+    nx, ny, u0, tau = 96, 48, 0.06, 0.58
+    alphas = [4.0, 5.0, 6.0]
+    q = 0.5 * u0 * u0 * (nx / (oracle_np.DX1 - oracle_np.DX0))
+    still = pkg.geometry.build_geometry(nx, ny, 0.0, None, "naca2412").mask
+    cl = {"body": [], "wind": []}
+    for frame in cl:
+        for alpha in alphas:
+            a = math.radians(alpha)
+            if frame == "wind":
+                mask, ux0, vy0 = still, u0 * math.cos(a), u0 * math.sin(a)
+            else:
+                mask, ux0, vy0 = pkg.geometry.build_geometry(nx, ny, alpha, None, "naca2412").mask, u0, 0.0
+            f, _ = wind.wind_init(nx, ny, ux0, vy0, np.float32)
+            fx, fy = [], []
+            for s in range(1, 3801):
+                f, macro = wind.wind_step(oracle_np.step, f, mask, tau, ux0, vy0)
+                if s > 3200 and s % 12 == 0:
+                    assert oracle_np.clamp_events(*macro, mask) == (0, 0), (frame, alpha, s)
+                    x, y, surf, _ = oracle_np.compute_forces_raw(macro[0], macro[1], mask)
+                    assert surf > 0
+                    fx.append(x)
+                    fy.append(y)
+            assert len(fx) == 50 and np.isfinite(f).all()
+            drag, lift = pkg.polar.wind_axes(fx, fy, alpha if frame == "wind" else 0.0)
+            assert np.isfinite(lift).all() and np.isfinite(drag).all()
+            cl[frame].append(float(lift.mean() / q))
+    second = {k: abs(v[0] - 2.0 * v[1] + v[2]) for k, v in cl.items()}
+    slope = {k: (v[2] - v[0]) / 2.0 for k, v in cl.items()}
+    print(f"CL body {cl['body']}, wind {cl['wind']}; |second difference| body {second['body']:.5f}, wind {second['wind']:.5f}; "
+          f"slopes {slope['body']:.5f}, {slope['wind']:.5f} per degree")
+    assert second["wind"] < 0.1 * second["body"]
+    assert abs(slope["wind"] - slope["body"]) <= 0.2 * min(abs(slope["wind"]), abs(slope["body"]))
+
+
+# ---- the kernel's code object ------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def polar_isa():
+    return _polar_isa.polar_isa()
+
+
+def test_wind_step_has_sixteen_instantiations_and_no_scratch(polar_isa):
+    """fp32 and fp64, emitting and not, BGK and Smagorinsky, half-way and interpolated walls.  No spill."""
+    chk, files = polar_isa
+    seen = {}
+    for f in files:
+        for name, r in chk.resources(f).items():
+            if "k_step_wind_batch" in name:
+                seen[name] = r
+                assert r.get("private_seg_size", 0) == 0, (name, r)
+    print({k: (v.get("num_vgpr"), v.get("num_sgpr")) for k, v in seen.items()})
+    assert len(seen) == 16, sorted(seen)

@@ -38,6 +38,12 @@ The batched step with interpolated bounce-back (wtp_enable_ibb, every member wit
 k_step_ibb_batch in place of k_step_batch (or, with --les, of k_step_les_batch).  The line has the shape of --les's; no sequential
 leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
 
+    python tools/polar_bench.py --wind [--les CS] [--ibb] [--repeats 5] [the options of the first form]
+
+The batched step with an inclined free stream (wtp_enable_wind): k_step_wind_batch in place of the kernel the other switches select.
+The masks stay those of the other forms, so that the tile classes are the same; member m's cross-flow is U0 sin(alpha_m).  The line
+has the shape of --les's; no sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -73,12 +79,18 @@ def _interpolated_walls(eng, nx, ny, b):
         eng.set_wall_distances(pkg.geometry.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False):
+def _cross_flow(b):
+    return U0 * np.sin(np.radians(_alphas(b)))
+
+
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False):
     """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
-    ibb: interpolated bounce-back with every airfoil's wall distances."""
+    ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across."""
     out = []
     with pkg.PolarEngine(nx, ny, b) as eng:
         eng.set_masks(masks)
+        if wind:
+            eng.enable_wind(_cross_flow(b))
         eng.init_equilibrium(U0)
         if les is not None:
             eng.enable_les(les)
@@ -96,6 +108,7 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False)
 
 LES = None      # --les: the Smagorinsky constant the sampled protocols run with (None: BGK)
 IBB = False     # --ibb: the sampled protocols run with interpolated bounce-back
+WIND = False    # --wind: the sampled protocols run with an inclined free stream
 
 
 def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
@@ -103,6 +116,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
     out = []
     with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1) as eng:
         eng.set_masks(masks)
+        if WIND:
+            eng.enable_wind(_cross_flow(b))
         eng.init_equilibrium(U0)
         if loads:
             eng.enable_loads(*pkg.polar.quarter_chord(nx, ny))
@@ -230,6 +245,7 @@ def main():
     ap.add_argument("--mean", action="store_true", help="the sampled step with and without the mean fields")
     ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
     ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
+    ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
@@ -239,8 +255,8 @@ def main():
         a.repeats = 1 if plain else 7
     if a.lib:
         pkg.polar.load_polar_library(a.lib)
-    global LES, IBB
-    LES, IBB = a.les, a.ibb
+    global LES, IBB, WIND
+    LES, IBB, WIND = a.les, a.ibb, a.wind
     if a.mean:
         return mean_cost(a)
     if a.mex:
@@ -252,7 +268,7 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
@@ -260,12 +276,14 @@ def main():
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.ibb or a.repeats > 1:
+            if a.les is not None or a.ibb or a.wind or a.repeats > 1:
                 line["les"] = a.les
                 if a.ibb:
                     line["ibb"] = True
+                if a.wind:
+                    line["wind"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None and not a.ibb:
+            if not a.no_sequential and a.les is None and not a.ibb and not a.wind:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
