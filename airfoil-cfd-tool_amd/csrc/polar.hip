@@ -34,6 +34,13 @@
 // step_tile with feq(1, U0, V0) in its far-field cells and one more value per member, with either collision and either wall rule,
 // and wtp_init_equilibrium fills the members by k_fill_wind.  A batch that has it off launches the kernels it always launched, with
 // the arguments they always had.
+//
+// Half-precision population storage (wtp_create_stored with WTP_STORE_HALF) is another storage of an fp32 batch: its lattices hold
+// each population as the binary16 deviation from its lattice weight, in wt_create's layout with 2-byte elements.  wtp_step launches
+// k_step_half_batch, site_general's branches with a Load in front and a Store behind, fp32 between, with either collision and either
+// far field; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
+// read-outs read the fp32 macroscopic planes and run unchanged.  A native batch launches the kernels it always launched, with the
+// arguments they always had.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -110,6 +117,8 @@ struct SampleTable {
 struct wtp_batch {
     int nx = 0, ny = 0, dtype = WT_F32, device = 0, members = 0, cap = 0;
     size_t esz = 4;
+    int storage = WTP_STORE_NATIVE;      // WTP_STORE_HALF: the lattices hold binary16 deviations from the weights (fp32 batches only)
+    size_t lat_esz = 4;                  // bytes of one stored population: esz, or 2 in a half batch
     Geom g{};
     int tiles_per_col = 0;
     MemberStrides ms{};
@@ -280,6 +289,150 @@ __global__ void k_fill_wind(T *__restrict__ f0, T *__restrict__ f1, T *__restric
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// half-precision population storage (wtp_create_stored with WTP_STORE_HALF; include/wt_polar.h "Half-precision population storage")
+// ------------------------------------------------------------------------------------------
+// Definition:
+//   Weights.  w_k are the fp32 weights as feq_all forms them: 4.0f/9.0f for k = 0, 1.0f/9.0f for k = 1..4, 1.0f/36.0f for
+//   k = 5..8, each one fp32 division.
+//   Store.  h = RN16(f - w_k): one fp32 subtraction, then one conversion to IEEE binary16, round-to-nearest-even.  Subnormal
+//   halves are kept; nothing is flushed and nothing is scaled.
+//   Load.  f = (float)h + w_k: an exact conversion and one fp32 addition.
+//   Step.  Every population a step reads goes through Load and every population it writes goes through Store, in every branch:
+//   solid (the swap), outlet (the copy), far field (the equilibrium), interior.  Everything between is the fp32 step, operation
+//   for operation: gather, half-way bounce-back, moments, the net, the collision.  The macroscopic planes stay fp32 and hold what
+//   the fp32 arithmetic produced.
+//   Start.  wtp_init_equilibrium stores Store(v_k) of the fp32 start values it forms without the mode, including the
+//   inclined-stream start; the macroscopic planes are unchanged.
+typedef _Float16 half_t;
+
+__host__ __device__ __forceinline__ constexpr float half_w(int k) { return k == 0 ? 4.0f / 9.0f : (k <= 4 ? 1.0f / 9.0f : 1.0f / 36.0f); }
+__device__ __forceinline__ float half_load(const half_t *__restrict__ p, int k) { return (float)*p + half_w(k); }
+__device__ __forceinline__ half_t half_store(float f, int k) { return (half_t)(f - half_w(k)); }
+
+// One site of a half batch: site_general's branches in site_general's order (solid, then outlet, then far field, then interior)
+// with Load and Store around them.  s, d, m point at column 0 of the member's lattices and mask, mm at its macroscopic planes.
+// KEEP IN STEP: the four branches are site_general's text (kernels.hpp) with half_load in place of each read of s and half_store in
+// place of each write of d; a change to a branch there is made here too.
+template <bool EMIT, int COLL, int FAR>
+__device__ __forceinline__ void site_half(const half_t *__restrict__ s, half_t *__restrict__ d, float *__restrict__ mm,
+                                          const uint8_t *__restrict__ m, const Geom &g, int i, int j, float tau, float U0, float c_les,
+                                          float V0)
+{
+    const long P = g.plane;
+    const long c = (long)i * g.pitch + j;
+    float out[9], rho, ux, uy;
+    if (m[c]) {                                                    // solid
+#pragma unroll
+        for (int k = 0; k < 9; k++) out[k] = half_load(s + opp_of(k) * P + c, opp_of(k));
+        rho = 1.0f; ux = 0.0f; uy = 0.0f;
+    } else if (i == g.nxl - 1) {                                   // outlet
+        float q[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) q[k] = half_load(s + k * P + c - g.pitch, k);
+        rho = q[0] + q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7] + q[8];
+        ux = (q[1] + q[5] + q[8] - q[3] - q[6] - q[7]) / rho;
+        uy = (q[2] + q[5] + q[6] - q[4] - q[7] - q[8]) / rho;
+#pragma unroll
+        for (int k = 0; k < 9; k++) out[k] = q[k];
+    } else if (i == 0 || j == g.ny - 1 || j == 0) {                // far field
+        rho = 1.0f; ux = U0;
+        if constexpr (FAR == FAR_INCLINED) uy = V0;
+        else uy = 0.0f;
+        feq_all(rho, ux, uy, out);
+    } else {                                                       // interior fluid
+        float fin[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
+            fin[k] = m[src] ? half_load(s + opp_of(k) * P + c, opp_of(k)) : half_load(s + k * P + src, k);
+        }
+        if constexpr (COLL == COLLIDE_LES) collide_les<float>(fin, tau, c_les, out, rho, ux, uy);
+        else collide(fin, tau, out, rho, ux, uy);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) d[k * P + c] = half_store(out[k], k);
+    if (EMIT) {
+        const long mp = (long)g.nxl * g.pitch;
+        mm[c] = rho; mm[mp + c] = ux; mm[2 * mp + c] = uy;
+    }
+}
+
+// Blocks of one member's k_step_half_batch grid.
+static unsigned half_step_blocks(const Geom &g)
+{
+    const long nruns = (long)g.nxl * (g.pitch / 256);
+    return (unsigned)((nruns + 3) / 4);
+}
+
+// One step of every member of a half batch: one site per lane and load, so that a wave loads 64 consecutive halves of a plane (128
+// bytes) at a time.  Grid (ceil(NX * pitch / 256 / 4), B): blockIdx.y is the member, blockIdx.x * 4 + wave a run of 256 rows of one
+// column, whose four chunks of 64 rows the wave walks one after the other, as k_step_batch walks a ragged tile; rev walks members and
+// runs backwards on every other step, as k_step_batch walks its tiles.  There are no tile classes: every site takes site_half.
+// Two rows per lane with packed halves (dword loads of two rows, packed conversion, a clean pair's two sites collided in one lane,
+// every other pair through site_half) was built, computed the same bits and measured slower in every walk tried, 26.9 us at best
+// against 21.7 at 320x160 with 32 members (profiles/polar_half_cost.txt), and is not kept.
+// COLL is the collision of the interior branch (collide or collide_les with cles[m]), FAR the far field (feq(1, U0, 0), or
+// feq(1, U0, V0) with vwind[m]); cles is read only for COLLIDE_LES and vwind only for FAR_INCLINED.  fp32 arithmetic only.  ms.lat
+// counts halves, ms.macro floats.
+template <bool EMIT, int COLL, int FAR>
+__global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restrict__ fs, half_t *__restrict__ fd, float *__restrict__ macro,
+                                                         const uint8_t *__restrict__ mask, Geom g, MemberStrides ms,
+                                                         const float *__restrict__ params, const float *__restrict__ cles,
+                                                         const float *__restrict__ vwind, int rev)
+{
+    const int runs = (int)(g.pitch / 256);                          // runs of 256 rows in a column
+    const long nruns = (long)g.nxl * runs;
+    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nruns) return;
+    const long t = rev ? nruns - 1 - q : q;
+    const int i = (int)(t / runs), j0 = (int)(t % runs) * 256;
+    const long mb = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const float tau = params[2 * mb], U0 = params[2 * mb + 1];
+    float c_les = 0.0f, V0 = 0.0f;
+    if constexpr (COLL == COLLIDE_LES) c_les = cles[mb];
+    if constexpr (FAR == FAR_INCLINED) V0 = vwind[mb];
+    const half_t *s = fs + mb * ms.lat + g.pitch;
+    half_t *d = fd + mb * ms.lat + g.pitch;
+    const uint8_t *m = mask + mb * ms.mask + g.pitch;
+    float *mm = macro + mb * ms.macro;
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (int v = 0; v < 4; v++) {
+        const int j = j0 + v * 64 + lane;
+        if (j < g.ny) site_half<EMIT, COLL, FAR>(s, d, mm, m, g, i, j, tau, U0, c_les, V0);
+    }
+}
+
+// The start state of a member of a half batch: k_fill_equilibrium's (k_fill_wind's) walk and stores, both lattices, pad columns
+// included, with Store(v_k) of the nine fp32 start values and (1, u0, v0) in the macroscopic planes.
+__global__ void k_fill_half(half_t *__restrict__ f0, half_t *__restrict__ f1, float *__restrict__ macro, Geom g, Init9<float> iv, float v0)
+{
+    const long n = g.plane;
+    const long mp = (long)g.nxl * g.pitch;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) { const half_t h = half_store(iv.v[k], k); f0[k * n + t] = h; f1[k * n + t] = h; }
+        if (t < mp) { macro[t] = 1.0f; macro[mp + t] = iv.u0; macro[2 * mp + t] = v0; }
+    }
+}
+
+// k_cols_to_rows for population plane k of a half batch: Load on the way, dst[j*W + x] = (float)src[(i0+x)*pitch + j] + w.
+__global__ void k_half_cols_to_rows(const half_t *__restrict__ src, float *__restrict__ dst, int i0, int W, int ny, long pitch, float w)
+{
+    __shared__ float tile[32][33];
+    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;   // bx: j block, by: x block
+    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
+        const int x = by + r, j = bx + threadIdx.x;
+        if (x < W && j < ny) tile[r][threadIdx.x] = (float)src[(long)(i0 + x) * pitch + j] + w;
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
+        const int j = bx + r, x = by + threadIdx.x;
+        if (x < W && j < ny) dst[(long)j * W + x] = tile[threadIdx.x][r];
+    }
+}
+
 // "The last block of a member finishes the sum": called by every thread of a block once the block's partials of member m are
 // written.  tickets[m * STRIDE] counts the member's blocks that have got here in this launch (0 between launches), nblocks is
 // how many there are.  Block-uniform; true in exactly one block per member and launch, the one that drew the last ticket, which
@@ -423,8 +576,9 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
 // 64 rows, one row per lane: the mask bytes of columns i-1, i, i+1 at rows j-1, j, j+1, then a population only on the lanes that
 // own a link in its direction.  The column's terms are added by wave_sum; the member's last block (member_done) adds the
 // columns' partials in column order, each of the four sums on a wave of its own.
-// KEEP IN STEP: k_mex_ibb_batch below is this kernel with another link term, body included.  The link bits, the walk, the ticket
-// and the final sum through LDS are the same text in both: a change to any of them here is made there too.
+// KEEP IN STEP: k_mex_ibb_batch below is this kernel with another link term, body included, and k_mex_half_batch this kernel with
+// the loaded value of a half batch.  The link bits, the walk, the ticket and the final sum through LDS are the same text in all
+// three: a change to any of them here is made there too.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
@@ -595,6 +749,89 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__r
     }
 }
 
+// The momentum exchange of members of a half batch: k_mex_batch's grid, walk, arguments and final sum, with the loaded value
+// (float)h + w_k (half_load) as f*_k(x), converted exactly to double.  ms.lat counts halves.  A kernel of its own, body included, so
+// that k_mex_batch compiles to the code it always compiled to.
+// KEEP IN STEP: everything but the line that forms t is k_mex_batch's text, the ticket (member_done) and the final sum through LDS
+// after it included: a change to either kernel's copy is made in the other.
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_half_batch(const half_t *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
+                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
+                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
+                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
+                                                   long long *__restrict__ links)
+{
+    const long m = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int nx = g.nxl, ny = g.ny;
+    const int width = win[2 * m + 1];
+    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
+    if (c < width) {                                                // (wave-uniform)
+        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
+        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
+        const half_t *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;          // column i of population plane 0
+        const double xr = ref[2 * m], yr = ref[2 * m + 1];
+        double sx = 0.0, sy = 0.0, sm = 0.0;
+        long long n = 0;
+        for (int j0 = 0; j0 < ny; j0 += 64) {
+            const int j = j0 + lane;
+            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
+            if (j >= 1 && j <= ny - 2 && !mk[j]) {
+                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
+                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
+                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
+            }
+            if (__ballot(s != 0) == 0ULL) continue;
+#pragma unroll
+            for (int k = 1; k <= 8; k++) {
+                if (!(s >> k & 1u)) continue;
+                const double t = 2.0 * (double)half_load(fc + k * g.plane + j, k);
+                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
+                const double rx = ((double)i + 0.5) + 0.5 * (double)ex_of(k), ry = ((double)j + 0.5) + 0.5 * (double)ey_of(k);
+                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
+                sx += flx;
+                sy += fly;
+                sm += a - b;
+                n += 1;
+            }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
+        if (lane == 0) {
+            MexPartial p;
+            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
+            col[m * nx + c] = p;
+        }
+    }
+    constexpr int NT = kLoadsWaves * 64;
+    __shared__ double sh[3][NT];
+    __shared__ long long shn[NT];
+    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
+    const volatile MexPartial *vc = col + m * nx;
+    const int w = (int)(threadIdx.x >> 6);
+    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
+    long long sn = 0;                                               // lane 0 of wave 3: links
+    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
+        const int q = c0 + (int)threadIdx.x;
+        const bool in = q < width;
+        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
+        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
+        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
+        shn[threadIdx.x] = in ? vc[q].links : 0;
+        __syncthreads();
+        if (lane == 0 && w < 4) {
+            const int cnt = width - c0 < NT ? width - c0 : NT;
+            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
+            else for (int k = 0; k < cnt; k++) sn += shn[k];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
+        else if (w == 1) fy[m] = s;
+        else if (w == 2) mz[m] = s;
+        else if (w == 3) links[m] = sn;
+    }
+}
+
 // Every element of p[0, n) set to v: the wall distances' default.
 template <typename T>
 __global__ __launch_bounds__(256) void k_fill_value(T *__restrict__ p, long n, T v)
@@ -685,11 +922,19 @@ extern "C" int wtp_destroy(wtp_batch *b)
 
 extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_cap, int device, wtp_batch **out)
 {
+    return wtp_create_stored(nx, ny, dtype, WTP_STORE_NATIVE, members, history_cap, device, out);
+}
+
+extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int members, int history_cap, int device, wtp_batch **out)
+{
     if (!out) return fail(WT_ERR_ARG, "out is null");
     *out = nullptr;
     if (nx < 3 || ny < 3) return fail(WT_ERR_ARG, "lattice must be at least 3x3 (got %dx%d)", nx, ny);
     if ((long long)nx * ny > (1LL << 33)) return fail(WT_ERR_ARG, "lattice too large");
     if (dtype != WT_F32 && dtype != WT_F64) return fail(WT_ERR_ARG, "dtype must be WT_F32 or WT_F64");
+    if (storage != WTP_STORE_NATIVE && storage != WTP_STORE_HALF)
+        return fail(WT_ERR_ARG, "storage must be WTP_STORE_NATIVE or WTP_STORE_HALF (got %d)", storage);
+    if (storage == WTP_STORE_HALF && dtype != WT_F32) return fail(WT_ERR_ARG, "storage WTP_STORE_HALF needs dtype WT_F32");
     if (members < 1 || members > WTP_MAX_MEMBERS) return fail(WT_ERR_ARG, "members must be in [1, %d] (got %d)", WTP_MAX_MEMBERS, members);
     if (history_cap < 0) return fail(WT_ERR_ARG, "history_cap must be >= 0 (got %d)", history_cap);
     int ndev = 0;
@@ -704,12 +949,14 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
     if (!b) return fail(WT_ERR_OOM, "host allocation failed");
     b->nx = nx; b->ny = ny; b->dtype = dtype; b->device = device; b->members = members; b->cap = history_cap;
     b->esz = dtype == WT_F32 ? 4 : 8;
+    b->storage = storage;
+    b->lat_esz = storage == WTP_STORE_HALF ? 2 : b->esz;
     Geom &g = b->g;                              // wt_create's geometry of a whole lattice
     g.nxl = nx; g.ny = ny; g.gi0 = 0; g.nx_g = nx;
     g.pitch = ((long)ny + 255) / 256 * 256;
     g.plane = (((long)(g.nxl + 2) * g.pitch * (long)b->esz + 4095) / 4096 * 4096 + 17408) / (long)b->esz;
     b->tiles_per_col = (int)(g.pitch / tile_j_of(b->esz));
-    b->ms.lat = member_stride((size_t)9 * g.plane * b->esz, b->esz);
+    b->ms.lat = member_stride((size_t)9 * g.plane * b->lat_esz, b->lat_esz);      // (a half batch keeps pitch and plane, in 2-byte elements)
     b->ms.macro = member_stride((size_t)3 * g.nxl * g.pitch * b->esz, b->esz);
     b->ms.mask = member_stride((size_t)(g.nxl + 2) * g.pitch, 1);
     b->ms.tiles = member_stride((size_t)g.nxl * b->tiles_per_col, 1);
@@ -727,7 +974,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
                                 #expr, hipGetErrorString(e_)));                                        \
     } while (0)
     const size_t B = (size_t)members;
-    const size_t lat_bytes = B * b->ms.lat * b->esz, macro_bytes = B * b->ms.macro * b->esz;
+    const size_t lat_bytes = B * b->ms.lat * b->lat_esz, macro_bytes = B * b->ms.macro * b->esz;
     const size_t mask_bytes = B * b->ms.mask, tile_bytes = B * b->ms.tiles;
     CREATE_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
     CREATE_TRY(hipMalloc(&b->f[0], lat_bytes));
@@ -753,7 +1000,7 @@ extern "C" int wtp_create(int nx, int ny, int dtype, int members, int history_ca
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -909,6 +1156,19 @@ static int init_impl(wtp_batch *b, const double *u0)
     return WT_OK;
 }
 
+// The start state of a half batch: the fp32 start values of init_impl<float>, stored through Store by k_fill_half.
+static int init_half(wtp_batch *b, const double *u0)
+{
+    for (int m = 0; m < b->members; m++) {
+        const double v0 = b->wind ? b->wind_host[(size_t)m] : 0.0;
+        const Init9<float> iv = b->wind ? wind_init<float>(u0[m], v0) : equilibrium_init<float>(u0[m]);
+        hipLaunchKernelGGL(k_fill_half, dim3(2048), dim3(256), 0, b->st, fptr<half_t>(b, 0, m), fptr<half_t>(b, 1, m), macro_of<float>(b, m),
+                           b->g, iv, (float)v0);
+        HIP_TRY(hipGetLastError());
+    }
+    return WT_OK;
+}
+
 extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
 {
     WT_TRY(check_batch(b));
@@ -916,7 +1176,8 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
     for (int m = 0; m < b->members; m++)
         if (!std::isfinite(u0[m])) return fail(WT_ERR_ARG, "u0[%d] must be finite", m);
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? init_impl<float>(b, u0) : init_impl<double>(b, u0));
+    if (b->storage == WTP_STORE_HALF) WT_TRY(init_half(b, u0));
+    else WT_TRY(b->dtype == WT_F32 ? init_impl<float>(b, u0) : init_impl<double>(b, u0));
     b->cur = 0;
     b->inited = true;
     b->steps_done = 0;
@@ -980,7 +1241,11 @@ static int launch_mex(wtp_batch *b, int row)
     for (int m = 0; m < b->members; m++) widest = std::max(widest, (int)b->mex_win[2 * (size_t)m + 1]);
     const SampleTable &t = b->xforces;
     const dim3 grid((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), block(kLoadsWaves * 64);
-    if (b->ibb)
+    if (b->storage == WTP_STORE_HALF)
+        hipLaunchKernelGGL(k_mex_half_batch, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), (const uint8_t *)b->mask, b->g,
+                           b->ms, (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
+                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row));
+    else if (b->ibb)
         hipLaunchKernelGGL(k_mex_ibb_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
                            (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
                            t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), (const T *)b->wq, b->q_stride);
@@ -1019,6 +1284,37 @@ template <typename T, int COLL, int WALL>
 static auto wind_kernel(bool emit)
 {
     return emit ? k_step_wind_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_wind_batch<T, false, WT_LOADMODE, COLL, WALL>;
+}
+
+// k_step_half_batch of one collision and one far field, emitting or not: all of them take the same arguments.
+template <int COLL, int FAR>
+static auto half_kernel(bool emit)
+{
+    return emit ? k_step_half_batch<true, COLL, FAR> : k_step_half_batch<false, COLL, FAR>;
+}
+
+// step_impl<float> for a half batch: the same loop, samples included, around k_step_half_batch.
+static int step_half(wtp_batch *b, int nsteps, int sample_every)
+{
+    const dim3 grid(half_step_blocks(b->g), (unsigned)b->members), block(256);
+    for (int s = 0; s < nsteps; s++) {
+        const long long n = b->steps_done + 1;
+        const bool sample = sample_every > 0 && n % sample_every == 0;
+        const bool emit = sample || s + 1 == nsteps;
+        const auto k_step = b->wind ? (b->les ? half_kernel<COLLIDE_LES, FAR_INCLINED>(emit) : half_kernel<COLLIDE_BGK, FAR_INCLINED>(emit))
+                                    : (b->les ? half_kernel<COLLIDE_LES, FAR_AXIAL>(emit) : half_kernel<COLLIDE_BGK, FAR_AXIAL>(emit));
+        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
+                           macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
+                           (const float *)b->wind_v, (int)(b->steps_done & 1));
+        HIP_TRY(hipGetLastError());
+        b->cur = 1 - b->cur;
+        b->steps_done = n;
+        if (sample) {
+            WT_TRY(sample_into<float>(b, (int)b->h_step.size()));
+            b->h_step.push_back(n);
+        }
+    }
+    return WT_OK;
 }
 
 template <typename T>
@@ -1084,7 +1380,7 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
     HIP_TRY(hipSetDevice(b->device));
     if (b->dtype == WT_F32) {
         WT_TRY(upload_params<float>(b, tau, u0));
-        return step_impl<float>(b, nsteps, sample_every);
+        return b->storage == WTP_STORE_HALF ? step_half(b, nsteps, sample_every) : step_impl<float>(b, nsteps, sample_every);
     }
     WT_TRY(upload_params<double>(b, tau, u0));
     return step_impl<double>(b, nsteps, sample_every);
@@ -1151,6 +1447,7 @@ extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
 extern "C" int wtp_enable_ibb(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "interpolated bounce-back is not available in a half batch");
     if (!on) { b->ibb = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
     HIP_TRY(hipSetDevice(b->device));
     if (!b->wq) {
@@ -1199,6 +1496,7 @@ static int set_wall_q_impl(wtp_batch *b, int first, int count, const T *q)
 extern "C" int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q)
 {
     WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "interpolated bounce-back is not available in a half batch");
     if (!q) return fail(WT_ERR_ARG, "q is null");
     if (first < 0 || count < 1 || first + count > b->members)
         return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
@@ -1439,12 +1737,43 @@ static int read_f_impl(wtp_batch *b, int member, void *out)
     return WT_OK;
 }
 
+// wtp_read_f of a half batch: Load of every stored population, plane by plane through the stage.
+static int read_f_half(wtp_batch *b, int member, float *out)
+{
+    const Geom &g = b->g;
+    const size_t n = (size_t)b->nx * g.ny;
+    WT_TRY(ensure_stage(b, n * sizeof(float)));
+    dim3 blk(32, 8), grd((g.ny + 31) / 32, (b->nx + 31) / 32);
+    for (int k = 0; k < 9; k++) {
+        hipLaunchKernelGGL(k_half_cols_to_rows, grd, blk, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, member) + k * g.plane + g.pitch,
+                           reinterpret_cast<float *>(b->stage), 0, b->nx, g.ny, g.pitch, half_w(k));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out + k * n, b->stage, n * sizeof(float), hipMemcpyDeviceToHost, b->st));
+        HIP_TRY(hipStreamSynchronize(b->st));
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_read_stored(wtp_batch *b, int member, uint16_t *h)
+{
+    WT_TRY(check_batch(b));
+    if (!h) return fail(WT_ERR_ARG, "h is null");
+    if (b->storage != WTP_STORE_HALF) return fail(WT_ERR_STATE, "the batch stores its populations natively (wtp_create_stored)");
+    WT_TRY(check_member(b, member));
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t n = (size_t)b->nx * b->ny;
+    for (int k = 0; k < 9; k++)
+        WT_TRY(read_plane<uint16_t>(b, fptr<uint16_t>(b, b->cur, member) + k * b->g.plane + b->g.pitch, b->g.pitch, h + k * n));
+    return WT_OK;
+}
+
 extern "C" int wtp_read_f(wtp_batch *b, int member, void *f_out)
 {
     WT_TRY(check_batch(b));
     if (!f_out) return fail(WT_ERR_ARG, "f_out is null");
     WT_TRY(check_member(b, member));
     HIP_TRY(hipSetDevice(b->device));
+    if (b->storage == WTP_STORE_HALF) return read_f_half(b, member, reinterpret_cast<float *>(f_out));
     return b->dtype == WT_F32 ? read_f_impl<float>(b, member, f_out) : read_f_impl<double>(b, member, f_out);
 }
 

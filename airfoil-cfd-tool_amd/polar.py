@@ -15,7 +15,9 @@ At airfoil Reynolds numbers, where tau falls to within 1e-3 of 0.5, the Smagorin
 (``PolarEngine.enable_interpolated_walls``, ``run_polar(walls="interpolated")``) the wall of every member is the panel polygon
 itself, through a wall distance per link (``geometry.wall_distances``), and not the staircase of its raster mask.  With an
 inclined free stream (``PolarEngine.enable_wind``, ``run_polar(frame="wind")``) every member holds the same body at 0 degrees
-and the angle of attack turns its free stream, so the polar carries no raster jump from angle to angle.
+and the angle of attack turns its free stream, so the polar carries no raster jump from angle to angle.  With half-precision
+population storage (``PolarEngine(storage="half")``, ``run_polar(storage="half")``) a float32 batch keeps every population as the
+binary16 deviation from its lattice weight and computes in fp32: half the bytes per step and per batch, at a small bias of CL and CD.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -48,9 +50,12 @@ EXPORTS = (
     "wtp_enable_les",
     "wtp_enable_ibb", "wtp_set_wall_q",
     "wtp_enable_wind",
+    "wtp_create_stored", "wtp_read_stored",
 )
 
+WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
 WALLS = ("staircase", "interpolated")                              # run_polar's wall rules
+STORAGES = ("native", "half")                                      # how a batch stores its populations: in its dtype, or as binary16 deviations from the weights
 FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
 WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
@@ -100,6 +105,8 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_enable_ibb": ([B, c_int], c_int),
         "wtp_set_wall_q": ([B, c_int, c_int, c_void_p], c_int),
         "wtp_enable_wind": ([B, dp], c_int),
+        "wtp_create_stored": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(B)], c_int),
+        "wtp_read_stored": ([B, c_int, c_void_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -113,6 +120,17 @@ def _check(rc: int) -> int:
     if rc < WT_OK:
         raise WTError(rc, load_polar_library().wtp_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def _check_storage(storage, dtype, walls: str = "staircase") -> None:
+    """ValueError for a storage outside STORAGES, and for "half" with a dtype other than float32 or with interpolated walls."""
+    if not isinstance(storage, str) or storage not in STORAGES:
+        raise ValueError(f"storage must be one of {STORAGES}, got {storage!r}")
+    if storage == "half":
+        if _np_dtype(dtype) != np.float32:
+            raise ValueError('storage="half" stores float32 batches only')
+        if walls == "interpolated":
+            raise ValueError('storage="half" does not combine with walls="interpolated"')
 
 
 def _f64(a, n: int) -> np.ndarray:
@@ -131,9 +149,13 @@ def _ip(a: np.ndarray):
 class PolarEngine:
     """One libwtpolar batch: `members` whole tunnels of nx x ny, each with its own mask, tau and U0."""
 
-    def __init__(self, nx: int, ny: int, members: int, dtype="float32", history_cap: int = 0, device: int = 0):
+    def __init__(self, nx: int, ny: int, members: int, dtype="float32", history_cap: int = 0, device: int = 0, storage: str = "native"):
+        """storage: "native" keeps the populations in `dtype`; "half" (float32 only) keeps each as the binary16 deviation from its
+        lattice weight, with fp32 arithmetic (wt_polar.h "Half-precision population storage"): half the bytes per step and per batch."""
+        _check_storage(storage, dtype)
         self._lib = load_polar_library()
         self.dtype = _np_dtype(dtype)
+        self.storage = storage
         self.nx, self.ny, self.members, self.history_cap = int(nx), int(ny), int(members), int(history_cap)
         self._b = c_void_p()
         self.loads_enabled = False
@@ -143,7 +165,11 @@ class PolarEngine:
         self.interpolated_walls = False
         self._wind = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
-        _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
+        if storage == "half":
+            _check(self._lib.wtp_create_stored(self.nx, self.ny, code, WTP_STORE_HALF, self.members, self.history_cap, int(device),
+                                               ctypes.byref(self._b)))
+        else:
+            _check(self._lib.wtp_create(self.nx, self.ny, code, self.members, self.history_cap, int(device), ctypes.byref(self._b)))
 
     def close(self) -> None:
         if getattr(self, "_b", None) is not None and self._b:
@@ -324,6 +350,13 @@ class PolarEngine:
         _check(self._lib.wtp_read_f(self._b, int(member), f.ctypes.data_as(c_void_p)))
         return f
 
+    def read_stored(self, member: int) -> np.ndarray:
+        """The raw binary16 bit patterns of one member's lattice in a storage="half" batch, [9][NY][NX] uint16 (view them as
+        float16 for the stored deviations); read_f returns the loaded fp32 values.  WTError (WT_ERR_STATE) on a native batch."""
+        h = np.empty((9, self.ny, self.nx), dtype=np.uint16)
+        _check(self._lib.wtp_read_stored(self._b, int(member), h.ctypes.data_as(c_void_p)))
+        return h
+
     def read_macro(self, member: int):
         rho, ux, uy = (np.empty((self.ny, self.nx), dtype=self.dtype) for _ in range(3))
         _check(self._lib.wtp_read_macro(self._b, int(member), rho.ctypes.data_as(c_void_p), ux.ctypes.data_as(c_void_p),
@@ -393,10 +426,13 @@ class PolarResult:
     walls: InitVar[str] = "staircase"
     # How the angles were set: "body" (a rotated body per angle) or "wind" (one body at 0 degrees, the free stream turned).  Init-only too.
     frame: InitVar[str] = "body"
+    # How the batch stored its populations: "native" (in its dtype) or "half" (binary16 deviations from the weights).  Init-only too.
+    storage: InitVar[str] = "native"
 
-    def __post_init__(self, walls, frame):
+    def __post_init__(self, walls, frame, storage):
         self.walls = walls
         self.frame = frame
+        self.storage = storage
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -516,7 +552,7 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False, walls: str = "staircase", frame: str = "body",
+              total_forces: bool = False, mean_fields: bool = False, storage: str = "native", walls: str = "staircase", frame: str = "body",
               les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
@@ -532,6 +568,12 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     `les`: the Smagorinsky constant (0.1 to 0.17 are the usual values; at most 0.5) of a subgrid eddy viscosity in every member's
     collision, from the first warm-up step on (PolarEngine.enable_les).  For sweeps at airfoil Reynolds numbers (`re` of 20 000
     and above), where plain BGK runs into the stability net and the angle fails.  None, the default, is plain BGK.
+    `storage`: "native", the default, keeps the populations in `dtype`, with the bits they always had.  "half" (float32 only, not
+    with walls="interpolated") keeps each as the binary16 deviation from its lattice weight and computes in fp32
+    (PolarEngine(storage="half"), wt_polar.h "Half-precision population storage"): a step moves half the bytes and the batch takes
+    half the memory.  It is no free lunch: on NACA 2412 at 320x160, 4 to 6 degrees, the mean CL comes out 0.006 to 0.007 higher
+    (1.2 to 1.5 %) and CD 0.0006 to 0.0008 higher (0.5 to 0.6 %), many times their standard deviation over the samples (README,
+    profiles/polar_half_sweep.txt).
     `walls`: "staircase", the default, reflects half-way to the next cell of the raster mask, with the bits it always had;
     "interpolated" reflects by linear interpolated bounce-back at the panel polygon of each angle, through the wall distances
     geometry.wall_distances computes from the Geometry the mask came from, from the first warm-up step on
@@ -560,6 +602,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         raise ValueError(f"walls must be one of {WALLS}, got {walls!r}")
     if frame not in FRAMES:
         raise ValueError(f"frame must be one of {FRAMES}, got {frame!r}")
+    _check_storage(storage, dtype, walls)
     wind = frame == "wind"
     if wind and any(not abs(a) <= WIND_ALPHA_MAX for a in alphas):
         raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
@@ -577,7 +620,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         geoms = [geo.build_geometry(nx, ny, a, user, shape) for a in alphas]
         ux0 = u0
     masks = np.stack([g.mask for g in geoms])
-    with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device) as eng:
+    with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device, storage=storage) as eng:
         eng.set_masks(masks)
         if walls == "interpolated":
             eng.enable_interpolated_walls()
@@ -614,7 +657,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     for p, mean in zip(points, means):
         p.mean = mean
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
-                       walls=walls, frame=frame)
+                       walls=walls, frame=frame, storage=storage)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

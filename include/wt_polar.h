@@ -247,6 +247,38 @@ WTP_API int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q);
  * V0 != 0 has no libwindtunnel twin.
  */
 WTP_API int wtp_enable_wind(wtp_batch *b, const double *v0);
+/*
+ * Half-precision population storage: an fp32 batch whose lattices hold every population as a binary16 deviation from its lattice
+ * weight.  A batched step is a stream over the populations, so storing them in two bytes halves the bytes a step moves (37
+ * against 73 per site) and the memory of a batch.  The arithmetic stays fp32.  It is a storage mode, per batch, chosen at creation
+ * and opt-in.  Definition:
+ *   Weights.  w_k are the fp32 weights as feq_all forms them: 4.0f/9.0f for k = 0, 1.0f/9.0f for k = 1..4, 1.0f/36.0f for
+ *   k = 5..8, each one fp32 division.
+ *   Store.  h = RN16(f - w_k): one fp32 subtraction, then one conversion to IEEE binary16, round-to-nearest-even.  Subnormal
+ *   halves are kept; nothing is flushed and nothing is scaled.
+ *   Load.  f = (float)h + w_k: an exact conversion and one fp32 addition.
+ *   Step.  Every population a step reads goes through Load and every population it writes goes through Store, in every branch:
+ *   solid (the swap), outlet (the copy), far field (the equilibrium), interior.  Everything between is the fp32 step, operation
+ *   for operation: gather, half-way bounce-back, moments, the net, the collision.  The macroscopic planes stay fp32 and hold what
+ *   the fp32 arithmetic produced.
+ *   Start.  wtp_init_equilibrium stores Store(v_k) of the fp32 start values it forms without the mode, including the
+ *   inclined-stream start; the macroscopic planes are unchanged.
+ * In NumPy the whole model is a wrapper around any base step: out = base(h.astype(f32) + W, ...); h' = (out[0] - W).astype(float16).
+ *
+ * wtp_create_stored is wtp_create with a storage argument: WTP_STORE_NATIVE gives the batch wtp_create gives, which launches the
+ * kernels it always launched.  WTP_STORE_HALF with WT_F64, or any other storage value, fails with WT_ERR_ARG before any device call.
+ * A half batch keeps the layout's element counts (pitch, pad columns, plane stride in elements) with 2-byte elements; the members'
+ * strides are rounded by bytes as always.  It combines with wtp_enable_les and wtp_enable_wind.  The forces, the loads and the mean
+ * fields read the fp32 macroscopic planes and are unchanged; the momentum exchange takes the loaded value as f*_k.  wtp_read_f
+ * returns the loaded fp32 values.  A member of a half batch has no libwindtunnel twin.
+ * Out of scope: interpolated bounce-back.  wtp_enable_ibb and wtp_set_wall_q on a half batch return WT_ERR_STATE and leave the
+ * batch working.
+ */
+#define WTP_STORE_NATIVE 0
+#define WTP_STORE_HALF 1
+WTP_API int wtp_create_stored(int nx, int ny, int dtype, int storage, int members, int history_cap, int device, wtp_batch **out);
+/* The raw halves of one member's current lattice, [9][NY][NX] binary16 bit patterns.  WT_ERR_STATE on a native batch. */
+WTP_API int wtp_read_stored(wtp_batch *b, int member, uint16_t *h);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -44,6 +44,13 @@ The batched step with an inclined free stream (wtp_enable_wind): k_step_wind_bat
 The masks stay those of the other forms, so that the tile classes are the same; member m's cross-flow is U0 sin(alpha_m).  The line
 has the shape of --les's; no sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.
 
+    python tools/polar_bench.py --storage half [--les CS] [--wind] [--repeats 5] [the options of the first form]
+
+The batched step of a half batch (PolarEngine(storage="half")): k_step_half_batch in place of the kernel the other switches select,
+on lattices of binary16 deviations from the weights.  The line has the shape of --les's and counts 37 B per site (nine 2-byte loads,
+nine 2-byte stores and the mask byte) in place of 72; no sequential leg.  Not with --ibb.  With --loads / --mex / --mean the batch is
+a half batch in both variants of those protocols (and --mex then times k_mex_half_batch).
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -83,11 +90,11 @@ def _cross_flow(b):
     return U0 * np.sin(np.radians(_alphas(b)))
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False):
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native"):
     """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
     ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across."""
     out = []
-    with pkg.PolarEngine(nx, ny, b) as eng:
+    with pkg.PolarEngine(nx, ny, b, storage=storage) as eng:
         eng.set_masks(masks)
         if wind:
             eng.enable_wind(_cross_flow(b))
@@ -109,12 +116,13 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False,
 LES = None      # --les: the Smagorinsky constant the sampled protocols run with (None: BGK)
 IBB = False     # --ibb: the sampled protocols run with interpolated bounce-back
 WIND = False    # --wind: the sampled protocols run with an inclined free stream
+STORAGE = "native"      # --storage: the sampled protocols run on a batch of this storage
 
 
 def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
     """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats."""
     out = []
-    with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1) as eng:
+    with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1, storage=STORAGE) as eng:
         eng.set_masks(masks)
         if WIND:
             eng.enable_wind(_cross_flow(b))
@@ -174,7 +182,7 @@ def mex_cost(a):
             us = {k: np.array(v) / a.steps * 1e6 for k, v in t.items()}
             med = {k: float(np.median(v)) for k, v in us.items()}
             samples = a.steps // a.sample_every
-            line = {"tool": "polar_bench --mex", "lib": a.lib or "default", "loads": bool(a.loads), "nx": nx, "ny": ny, "dtype": "float32",
+            line = {"tool": "polar_bench --mex", "lib": a.lib or "default", "storage": a.storage, "loads": bool(a.loads), "nx": nx, "ny": ny, "dtype": "float32",
                     "members": b, "steps": a.steps, "sample_every": a.sample_every, "repeats": a.repeats,
                     "us_per_step_plain_median": round(med[False], 3),
                     "us_per_step_plain_range": [round(float(us[False].min()), 3), round(float(us[False].max()), 3)],
@@ -200,7 +208,7 @@ def mean_cost(a):
             samples = a.steps // a.sample_every
             per_sample = (med[True] - med[False]) * a.steps / samples
             bytes_sample = b * nx * ny * (3 * 4 + 2 * 56)
-            line = {"tool": "polar_bench --mean", "lib": a.lib or "default", "loads": bool(a.loads), "mex": bool(a.mex), "nx": nx, "ny": ny,
+            line = {"tool": "polar_bench --mean", "lib": a.lib or "default", "storage": a.storage, "loads": bool(a.loads), "mex": bool(a.mex), "nx": nx, "ny": ny,
                     "dtype": "float32", "members": b, "steps": a.steps, "sample_every": a.sample_every, "repeats": a.repeats,
                     "us_per_step_plain": [round(float(v), 3) for v in us[False]], "us_per_step_plain_median": round(med[False], 3),
                     "us_per_step_mean": [round(float(v), 3) for v in us[True]], "us_per_step_mean_median": round(med[True], 3),
@@ -246,6 +254,7 @@ def main():
     ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
     ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
     ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
+    ap.add_argument("--storage", default="native", choices=pkg.polar.STORAGES, help="how the batch stores its populations (half: binary16 deviations)")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
@@ -255,8 +264,11 @@ def main():
         a.repeats = 1 if plain else 7
     if a.lib:
         pkg.polar.load_polar_library(a.lib)
-    global LES, IBB, WIND
-    LES, IBB, WIND = a.les, a.ibb, a.wind
+    if a.storage == "half" and a.ibb:
+        ap.error("--storage half does not combine with --ibb")
+    half = a.storage == "half"
+    global LES, IBB, WIND, STORAGE
+    LES, IBB, WIND, STORAGE = a.les, a.ibb, a.wind, a.storage
     if a.mean:
         return mean_cost(a)
     if a.mex:
@@ -268,22 +280,24 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
-            bytes_step = b * sites * (72 + 12 / a.steps)
+            bytes_step = b * sites * ((37 if half else 72) + 12 / a.steps)
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.ibb or a.wind or a.repeats > 1:
+            if a.les is not None or a.ibb or a.wind or half or a.repeats > 1:
                 line["les"] = a.les
+                if half:
+                    line["storage"] = "half"
                 if a.ibb:
                     line["ibb"] = True
                 if a.wind:
                     line["wind"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None and not a.ibb and not a.wind:
+            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
