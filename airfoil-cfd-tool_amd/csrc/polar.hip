@@ -41,6 +41,11 @@
 // far field; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
 // read-outs read the fp32 macroscopic planes and run unchanged.  A native batch launches the kernels it always launched, with the
 // arguments they always had.
+//
+// State upload (wtp_write_f, wtp_write_stored) is the inverse of the read-backs: a member's [9][NY][NX] host planes go through the stage
+// into its current lattice by k_rows_to_cols, or by k_half_rows_to_cols with a Store on the way.  A write marks the macroscopic planes
+// stale until a step has emitted and zeroes the member's running sums; with wtp_set_step_count a sweep continues where another stopped.
+// A batch that never writes launches the kernels it always launched.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -173,6 +178,7 @@ struct wtp_batch {
     long m_stride = 0;
     int m_pitch = 0;                     // NY rounded up to WTP_MEAN_ROWS
     bool inited = false;
+    bool macro_stale = false;            // a member's populations were written (wtp_write_f / wtp_write_stored) and no step has emitted since
     long long steps_done = 0;
 };
 
@@ -430,6 +436,23 @@ __global__ void k_half_cols_to_rows(const half_t *__restrict__ src, float *__res
     for (int r = threadIdx.y; r < 32; r += blockDim.y) {
         const int j = bx + r, x = by + threadIdx.x;
         if (x < W && j < ny) dst[(long)j * W + x] = tile[threadIdx.x][r];
+    }
+}
+
+// k_rows_to_cols for population plane k of a half batch: Store on the way, dst[(i0+x)*pitch + j] = RN16(src[j*ld + x] - w).  The inverse
+// walk of k_half_cols_to_rows: a 32 x 32 tile through LDS, so that the reads of the rows and the writes of the columns are both coalesced.
+__global__ void k_half_rows_to_cols(const float *__restrict__ src, half_t *__restrict__ dst, int i0, int W, int ny, long pitch, long ld, float w)
+{
+    __shared__ float tile[32][33];
+    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;   // bx: x block, by: j block
+    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
+        const int j = by + r, x = bx + threadIdx.x;
+        if (x < W && j < ny) tile[r][threadIdx.x] = src[(long)j * ld + x];
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
+        const int x = bx + r, j = by + threadIdx.x;
+        if (x < W && j < ny) dst[(long)(i0 + x) * pitch + j] = (half_t)(tile[threadIdx.x][r] - w);
     }
 }
 
@@ -1000,7 +1023,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1180,6 +1203,7 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
     else WT_TRY(b->dtype == WT_F32 ? init_impl<float>(b, u0) : init_impl<double>(b, u0));
     b->cur = 0;
     b->inited = true;
+    b->macro_stale = false;
     b->steps_done = 0;
     b->h_step.clear();
     return clear_sums(b, 0, b->members);
@@ -1193,6 +1217,14 @@ static int check_ready(const wtp_batch *b)
     if (!b->inited) return fail(WT_ERR_STATE, "wtp_init_equilibrium has not been called");
     for (int m = 0; m < b->members; m++)
         if (!b->mask_set[(size_t)m]) return fail(WT_ERR_STATE, "member %d has no mask (wtp_set_masks)", m);
+    return WT_OK;
+}
+
+// The macroscopic planes belong to the populations: not after a write, until a step has emitted.
+static int check_macro(const wtp_batch *b)
+{
+    if (b->macro_stale)
+        return fail(WT_ERR_STATE, "the macroscopic planes are those of the state before wtp_write_f / wtp_write_stored: run wtp_step (nsteps >= 1) first");
     return WT_OK;
 }
 
@@ -1380,10 +1412,13 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
     HIP_TRY(hipSetDevice(b->device));
     if (b->dtype == WT_F32) {
         WT_TRY(upload_params<float>(b, tau, u0));
-        return b->storage == WTP_STORE_HALF ? step_half(b, nsteps, sample_every) : step_impl<float>(b, nsteps, sample_every);
+        WT_TRY(b->storage == WTP_STORE_HALF ? step_half(b, nsteps, sample_every) : step_impl<float>(b, nsteps, sample_every));
+    } else {
+        WT_TRY(upload_params<double>(b, tau, u0));
+        WT_TRY(step_impl<double>(b, nsteps, sample_every));
     }
-    WT_TRY(upload_params<double>(b, tau, u0));
-    return step_impl<double>(b, nsteps, sample_every);
+    if (nsteps > 0) b->macro_stale = false;      // the call's last step emitted
+    return WT_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1546,6 +1581,7 @@ extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, i
     WT_TRY(check_batch(b));
     if (!fx || !fy || !surf || !rev) return fail(WT_ERR_ARG, "null output");
     WT_TRY(check_ready(b));
+    WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? launch_forces<float>(b, b->cap) : launch_forces<double>(b, b->cap));     // the scratch row
     return read_rows(b, b->forces, b->cap, 1, {fx, fy, surf, rev});
@@ -1608,6 +1644,7 @@ extern "C" int wtp_moment(wtp_batch *b, double *mz)
     if (!mz) return fail(WT_ERR_ARG, "mz is null");
     WT_TRY(check_loads(b));
     WT_TRY(check_ready(b));
+    WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(b->dtype == WT_F32 ? launch_loads<float>(b, b->cap, false) : launch_loads<double>(b, b->cap, false));     // the scratch row
     return read_rows(b, b->moment, b->cap, 1, {mz});
@@ -1777,6 +1814,108 @@ extern "C" int wtp_read_f(wtp_batch *b, int member, void *f_out)
     return b->dtype == WT_F32 ? read_f_impl<float>(b, member, f_out) : read_f_impl<double>(b, member, f_out);
 }
 
+// ------------------------------------------------------------------------------------------
+// state upload and restart (include/wt_polar.h "State upload and restart")
+// ------------------------------------------------------------------------------------------
+// Nine [NY][NX] planes of the host, E each, to the member's current lattice, plane by plane through the stage: the inverse of
+// read_plane.  `launch(k, src)` enqueues the conversion of plane k from the stage, src, to column 0 of the member's plane.  The stream
+// runs dry before the first copy (the stage may still feed an earlier conversion; steps already enqueued end before the values land)
+// and after every plane (the next copy reuses the stage); steps enqueued afterwards follow in the stream.
+template <typename E, typename Launch>
+static int write_planes(wtp_batch *b, const E *in, Launch launch)
+{
+    const size_t n = (size_t)b->nx * b->ny;
+    WT_TRY(ensure_stage(b, n * sizeof(E)));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    for (int k = 0; k < 9; k++) {
+        HIP_TRY(hipMemcpyAsync(b->stage, in + k * n, n * sizeof(E), hipMemcpyHostToDevice, b->st));
+        launch(k, reinterpret_cast<const E *>(b->stage));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(b->st));
+    }
+    return WT_OK;
+}
+
+// The elements of the host are those of the lattice (T: float, double, or uint16_t for raw halves): stored as given.
+template <typename T>
+static int write_raw(wtp_batch *b, int member, const void *in)
+{
+    const Geom &g = b->g;
+    const dim3 blk(32, 8), grd((b->nx + 31) / 32, (g.ny + 31) / 32);
+    T *lat = fptr<T>(b, b->cur, member);
+    return write_planes<T>(b, reinterpret_cast<const T *>(in), [&](int k, const T *src) {
+        hipLaunchKernelGGL(k_rows_to_cols<T>, grd, blk, 0, b->st, src, lat + k * g.plane + g.pitch, 0, b->nx, g.ny, g.pitch, (long)b->nx);
+    });
+}
+
+// wtp_write_f of a half batch: Store of every fp32 value.
+static int write_f_half(wtp_batch *b, int member, const float *in)
+{
+    const Geom &g = b->g;
+    const dim3 blk(32, 8), grd((b->nx + 31) / 32, (g.ny + 31) / 32);
+    half_t *lat = fptr<half_t>(b, b->cur, member);
+    return write_planes<float>(b, in, [&](int k, const float *src) {
+        hipLaunchKernelGGL(k_half_rows_to_cols, grd, blk, 0, b->st, src, lat + k * g.plane + g.pitch, 0, b->nx, g.ny, g.pitch, (long)b->nx,
+                           half_w(k));
+    });
+}
+
+// A write fills columns 0 .. NX-1 and rows 0 .. NY-1 of one lattice only: the start call has to have defined the rest.
+static int check_writable(const wtp_batch *b, int member)
+{
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    if (!b->inited) return fail(WT_ERR_STATE, "wtp_init_equilibrium has not been called: pad columns and the other lattice hold nothing defined");
+    return WT_OK;
+}
+
+// What a write changes besides the populations: the macroscopic planes no longer belong to them, and the member's time statistics restart.
+static int after_write(wtp_batch *b, int member)
+{
+    b->macro_stale = true;
+    return clear_sums(b, member, 1);
+}
+
+extern "C" int wtp_write_f(wtp_batch *b, int member, const void *f_in)
+{
+    WT_TRY(check_batch(b));
+    if (!f_in) return fail(WT_ERR_ARG, "f_in is null");
+    WT_TRY(check_writable(b, member));
+    HIP_TRY(hipSetDevice(b->device));
+    if (b->storage == WTP_STORE_HALF) WT_TRY(write_f_half(b, member, reinterpret_cast<const float *>(f_in)));
+    else WT_TRY(b->dtype == WT_F32 ? write_raw<float>(b, member, f_in) : write_raw<double>(b, member, f_in));
+    return after_write(b, member);
+}
+
+extern "C" int wtp_write_stored(wtp_batch *b, int member, const uint16_t *h)
+{
+    WT_TRY(check_batch(b));
+    if (!h) return fail(WT_ERR_ARG, "h is null");
+    if (b->storage != WTP_STORE_HALF) return fail(WT_ERR_STATE, "the batch stores its populations natively (wtp_create_stored)");
+    WT_TRY(check_writable(b, member));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(write_raw<uint16_t>(b, member, h));
+    return after_write(b, member);
+}
+
+extern "C" int wtp_step_count(wtp_batch *b, int64_t *steps)
+{
+    WT_TRY(check_batch(b));
+    if (!steps) return fail(WT_ERR_ARG, "steps is null");
+    *steps = b->steps_done;
+    return WT_OK;
+}
+
+extern "C" int wtp_set_step_count(wtp_batch *b, int64_t steps)
+{
+    WT_TRY(check_batch(b));
+    if (steps < 0) return fail(WT_ERR_ARG, "steps < 0");
+    if (!b->h_step.empty() && steps < b->h_step.back())
+        return fail(WT_ERR_STATE, "step count %lld is below that of the last history row held (%lld): wtp_clear_history first",
+                    (long long)steps, (long long)b->h_step.back());
+    b->steps_done = steps;
+    return WT_OK;
+}
+
 template <typename T>
 static int read_macro_impl(wtp_batch *b, int member, void *rho, void *ux, void *uy)
 {
@@ -1792,6 +1931,7 @@ extern "C" int wtp_read_macro(wtp_batch *b, int member, void *rho, void *ux, voi
 {
     WT_TRY(check_batch(b));
     WT_TRY(check_member(b, member));
+    WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
     return b->dtype == WT_F32 ? read_macro_impl<float>(b, member, rho, ux, uy) : read_macro_impl<double>(b, member, rho, ux, uy);
 }

@@ -18,6 +18,8 @@ inclined free stream (``PolarEngine.enable_wind``, ``run_polar(frame="wind")``) 
 and the angle of attack turns its free stream, so the polar carries no raster jump from angle to angle.  With half-precision
 population storage (``PolarEngine(storage="half")``, ``run_polar(storage="half")``) a float32 batch keeps every population as the
 binary16 deviation from its lattice weight and computes in fp32: half the bytes per step and per batch, at a small bias of CL and CD.
+A sweep can be continued without a second warm-up: ``PolarEngine.state`` / ``restore`` (``write_f``, ``write_stored``,
+``set_step_count``) and ``run_polar(keep_state=True)`` followed by ``run_polar(start=result.state)``.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -51,6 +53,7 @@ EXPORTS = (
     "wtp_enable_ibb", "wtp_set_wall_q",
     "wtp_enable_wind",
     "wtp_create_stored", "wtp_read_stored",
+    "wtp_write_f", "wtp_write_stored", "wtp_step_count", "wtp_set_step_count",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
@@ -107,6 +110,10 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_enable_wind": ([B, dp], c_int),
         "wtp_create_stored": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(B)], c_int),
         "wtp_read_stored": ([B, c_int, c_void_p], c_int),
+        "wtp_write_f": ([B, c_int, c_void_p], c_int),
+        "wtp_write_stored": ([B, c_int, c_void_p], c_int),
+        "wtp_step_count": ([B, ip], c_int),
+        "wtp_set_step_count": ([B, c_int64], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)
@@ -131,6 +138,24 @@ def _check_storage(storage, dtype, walls: str = "staircase") -> None:
             raise ValueError('storage="half" stores float32 batches only')
         if walls == "interpolated":
             raise ValueError('storage="half" does not combine with walls="interpolated"')
+
+
+def _check_state(state, nx: int, ny: int, dtype, storage: str, members: int) -> None:
+    """ValueError where a PolarEngine.state() does not fit a batch of `members` nx x ny tunnels of `dtype` and `storage`."""
+    try:
+        got = (int(state["nx"]), int(state["ny"]), np.dtype(state["dtype"]), state["storage"], int(state["members"]))
+        int(state["steps"]), state["f"]
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError(f"not a PolarEngine.state(): {e!r}") from None
+    want = (int(nx), int(ny), _np_dtype(dtype), storage, int(members))
+    for name, g, w in zip(("nx", "ny", "dtype", "storage", "members"), got, want):
+        if g != w:
+            raise ValueError(f"the state's {name} is {g!s}, the batch's is {w!s}")
+    stored = np.uint16 if storage == "half" else want[2]
+    f = np.asarray(state["f"])
+    if f.shape != (want[4], 9, want[1], want[0]) or f.dtype != np.dtype(stored):
+        raise ValueError(f"the state's f must be [B][9][NY][NX] = {(want[4], 9, want[1], want[0])} of {np.dtype(stored).name}, "
+                         f"got {f.shape} of {f.dtype.name}")
 
 
 def _f64(a, n: int) -> np.ndarray:
@@ -357,6 +382,62 @@ class PolarEngine:
         _check(self._lib.wtp_read_stored(self._b, int(member), h.ctypes.data_as(c_void_p)))
         return h
 
+    def _planes(self, a, dtype, what: str) -> np.ndarray:
+        """`a` as a contiguous [9][NY][NX] array of `dtype`; ValueError where its shape or dtype is another (nothing is converted)."""
+        a = np.asarray(a)
+        if a.shape != (9, self.ny, self.nx) or a.dtype != np.dtype(dtype):
+            raise ValueError(f"{what} must be [9][NY][NX] = {(9, self.ny, self.nx)} of {np.dtype(dtype).name}, "
+                             f"got {a.shape} of {a.dtype.name}")
+        return np.ascontiguousarray(a)
+
+    def write_f(self, member: int, f) -> None:
+        """Replace one member's populations with f [9][NY][NX] of the batch's dtype: the inverse of read_f (wt_polar.h "State upload
+        and restart").  A native batch stores the bits given; a storage="half" batch stores (f - w).astype(float16).  Afterwards
+        read_macro, forces and moment raise WTError (WT_ERR_STATE) until a step has run, and the member's surface and mean sums are
+        empty; the history, the step count and the other members are untouched.  After init_equilibrium only.  ValueError for
+        another shape or dtype."""
+        a = self._planes(f, self.dtype, "f")
+        _check(self._lib.wtp_write_f(self._b, int(member), a.ctypes.data_as(c_void_p)))
+
+    def write_stored(self, member: int, h) -> None:
+        """The twin of read_stored in a storage="half" batch: h [9][NY][NX] uint16, raw binary16 bit patterns, stored as given.
+        read_f then write_f does not restore the stored bits (a stored -0 comes back as +0); read_stored then write_stored does.
+        WTError (WT_ERR_STATE) on a native batch; otherwise as write_f."""
+        a = self._planes(h, np.uint16, "h")
+        _check(self._lib.wtp_write_stored(self._b, int(member), a.ctypes.data_as(c_void_p)))
+
+    @property
+    def step_count(self) -> int:
+        """Steps since init_equilibrium: a step samples when this count, after it, is a multiple of sample_every."""
+        n = np.zeros(1, np.int64)
+        _check(self._lib.wtp_step_count(self._b, _ip(n)))
+        return int(n[0])
+
+    def set_step_count(self, n: int) -> None:
+        """Set the step count, so that the sampling cadence and the history's step column continue after a restart.  n >= 0, and not
+        below the step of the last history row held (WTError).  Nothing else changes."""
+        _check(self._lib.wtp_set_step_count(self._b, int(n)))
+
+    def state(self) -> Dict[str, object]:
+        """What a restart needs: nx, ny, dtype (its name), storage, members, steps (the step count) and f [B][9][NY][NX], the
+        populations of every member: read_f's values on a native batch, read_stored's raw uint16 halves on a storage="half" batch.
+        Not in it: the history, the running sums (surface, mean fields), the masks, the wall distances and the enable_* settings."""
+        read = self.read_stored if self.storage == "half" else self.read_f
+        return {"nx": self.nx, "ny": self.ny, "dtype": self.dtype.name, "storage": self.storage, "members": self.members,
+                "steps": self.step_count, "f": np.stack([read(m) for m in range(self.members)])}
+
+    def restore(self, state) -> None:
+        """Write every member's populations from a state() and set its step count.  ValueError where the state's nx, ny, dtype,
+        storage or members are not the engine's.  Call init_equilibrium first: it is what gives the pad columns and the lattice
+        that is not written defined contents, and it clears the history, so that the restored count cannot fall below a row held.
+        Masks, wall distances and enable_* settings are the caller's to set as they were; the running sums start empty and the
+        macroscopic planes are valid again after the first step."""
+        _check_state(state, self.nx, self.ny, self.dtype, self.storage, self.members)
+        write = self.write_stored if self.storage == "half" else self.write_f
+        for m in range(self.members):
+            write(m, state["f"][m])
+        self.set_step_count(state["steps"])
+
     def read_macro(self, member: int):
         rho, ux, uy = (np.empty((self.ny, self.nx), dtype=self.dtype) for _ in range(3))
         _check(self._lib.wtp_read_macro(self._b, int(member), rho.ctypes.data_as(c_void_p), ux.ctypes.data_as(c_void_p),
@@ -428,11 +509,14 @@ class PolarResult:
     frame: InitVar[str] = "body"
     # How the batch stored its populations: "native" (in its dtype) or "half" (binary16 deviations from the weights).  Init-only too.
     storage: InitVar[str] = "native"
+    # PolarEngine.state() after the last sample of a run_polar(keep_state=True), to continue from (run_polar(start=)); else None.  Init-only too.
+    state: InitVar[Optional[Dict[str, object]]] = None
 
-    def __post_init__(self, walls, frame, storage):
+    def __post_init__(self, walls, frame, storage, state):
         self.walls = walls
         self.frame = frame
         self.storage = storage
+        self.state = state
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -552,8 +636,8 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False, storage: str = "native", walls: str = "staircase", frame: str = "body",
-              les: Optional[float] = None) -> PolarResult:
+              total_forces: bool = False, mean_fields: bool = False, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
+              storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -586,7 +670,18 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     reference point and the surface pressure (x/c of the unrotated body) are unchanged.  Every |angle| must be at most 30
     degrees: the trailing edge sits 0.42 chords from the outlet and the half height is 0.46 chords, so up to there the wake
     leaves through the outlet.  The top and bottom rows stay equilibrium rows, now with inflow and outflow, and no blockage
-    correction is made: the level of CL and CD differs from the body frame's (README)."""
+    correction is made: the level of CL and CD differs from the body frame's (README).
+    `keep_state`: PolarResult.state carries PolarEngine.state() taken after the last sample: the populations of every angle and
+    the step count.  None otherwise.
+    `start`: such a state, to continue from.  The engine is set up and initialised as always (masks, wall rule, free stream and
+    collision are formed from the arguments of this call), then restored from `start` (PolarEngine.restore), then stepped.  The
+    warm-up is then what the caller says, and its default is 0: the sweep that gave the state has paid it.  The step count goes
+    on from the state's, so with the same `sample_every` the samples fall on the steps on which one longer run would have taken
+    them, with the same bits.  The first sample follows at least one step, so the macroscopic planes belong to the restored
+    populations again.  The running sums (surface pressure, mean fields) start empty: they cover this call's samples only, and
+    so do the statistics of the points.  Continuing with other angles, another body or other settings than the state was
+    taken with is the caller's decision: nothing checks it, and the flow then needs its own time to adjust.  A `start` whose
+    nx, ny, dtype, storage or number of angles is not this call's raises ValueError before an engine is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -608,8 +703,10 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
     nx, ny, u0 = int(nx), int(ny), float(u0)
     tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
+    if start is not None:
+        _check_state(start, nx, ny, dtype, storage, len(alphas))
     if warmup_steps is None:
-        warmup_steps = int(math.ceil(2 * nx / u0))
+        warmup_steps = 0 if start is not None else int(math.ceil(2 * nx / u0))
     warmup_steps = int(warmup_steps)
     user = geo.round_coords(coords) if coords is not None and len(coords) else []
     if wind:                                                   # one body, at 0 degrees, in every member
@@ -638,6 +735,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_mean_fields()
         if les is not None:
             eng.enable_les(les)
+        if start is not None:
+            eng.restore(start)
         if warmup_steps:
             eng.step(warmup_steps, tau, ux0)
         # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
@@ -646,6 +745,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), 0.0 if wind else a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
         means = [mean_flow(eng.mean_sums(m), u0) for m in range(len(alphas))] if mean_fields else [None] * len(alphas)
+        state = eng.state() if keep_state else None
     if wind:                                                   # lattice axes -> wind axes, every sample of every member
         h["fx"], h["fy"] = wind_axes(h["fx"], h["fy"], alphas)
         if total_forces:
@@ -657,7 +757,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     for p, mean in zip(points, means):
         p.mean = mean
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
-                       walls=walls, frame=frame, storage=storage)
+                       walls=walls, frame=frame, storage=storage, state=state)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

@@ -279,6 +279,49 @@ WTP_API int wtp_enable_wind(wtp_batch *b, const double *v0);
 WTP_API int wtp_create_stored(int nx, int ny, int dtype, int storage, int members, int history_cap, int device, wtp_batch **out);
 /* The raw halves of one member's current lattice, [9][NY][NX] binary16 bit patterns.  WT_ERR_STATE on a native batch. */
 WTP_API int wtp_read_stored(wtp_batch *b, int member, uint16_t *h);
+/*
+ * State upload and restart: the write twins of wtp_read_f and wtp_read_stored, and the step count, so that a sweep continues from
+ * a state taken earlier (or starts from any state the caller forms) without paying its warm-up again.
+ *
+ * wtp_write_f replaces the populations of one member's current lattice with f_in, [9][NY][NX] values of the batch's dtype (fp32
+ * for a half batch): the inverse layout of wtp_read_f.  Only columns 0 .. NX-1 and rows 0 .. NY-1 are written; the pad columns,
+ * the rows >= NY and the other lattice keep what they hold.  On a native batch the values are stored as given, bit for bit.  On a
+ * half batch each value goes through Store, h = RN16(f - w_k): one fp32 subtraction and one conversion.  The values are not
+ * inspected: NaN in means NaN out, as with wt_write_f.
+ * wtp_write_stored is the twin of wtp_read_stored: [9][NY][NX] raw binary16 bit patterns, stored as given.  WT_ERR_STATE on a
+ * native batch.  It exists because Load followed by Store is not the identity on bit patterns: the half -0 (0x8000, which Store
+ * writes for every population less than 2^-25 below its weight) loads as w_k and stores as +0 (0x0000), and a signalling NaN comes
+ * back quiet.  Every other pattern survives: the smallest subnormal half, 2^-24, is two fp32 ulps of the largest weight, so no
+ * half is lost in (float)h + w_k, and the loaded values of the two zeros are equal.  wtp_read_f followed by wtp_write_f therefore
+ * restores the values a half batch computes with but not its stored bits; a checkpoint that compares equal as bits is
+ * wtp_read_stored and wtp_write_stored.
+ * Both: a null pointer or a member outside the batch is WT_ERR_ARG; a batch that has never had wtp_init_equilibrium is
+ * WT_ERR_STATE, because the start call is what gives the pad columns and both lattices defined contents.  The checks happen
+ * before any device call and leave the batch as it was.
+ * What a write changes besides the populations, as wt_write_f and wtp_set_masks do:
+ *   The macroscopic planes are the pre-collision moments of the step that produced a state and cannot be derived from a written
+ *   one.  After a write to any member, wtp_read_macro, wtp_forces and wtp_moment return WT_ERR_STATE until a wtp_step with
+ *   nsteps >= 1 has run (its last step emits); wtp_init_equilibrium ends that too.  wtp_mex, wtp_read_f and wtp_read_stored read
+ *   populations and stay valid.  A sampled step emits before it reduces, so sampling needs nothing.  wtp_clamp_events is not
+ *   refused: until that step it counts on the planes of the state before the write.
+ *   The surface sums and the mean-field sums and counts of the written member are zeroed, as wtp_set_masks zeroes those of the
+ *   members it touches.
+ *   Kept: the history, the step count, the masks, the wall distances, every wtp_enable_* setting, and the other members'
+ *   populations and sums.
+ *   Steps already enqueued finish before the new values land, and steps enqueued afterwards see them.
+ *
+ * wtp_step_count returns the number of steps since wtp_init_equilibrium, which decides which steps sample (wtp_step) and is the
+ * `step` of a history row.  wtp_set_step_count sets it, so that the cadence and the history's step column continue after a restart:
+ * steps >= 0, else WT_ERR_ARG; not below the step of the last history row held, else WT_ERR_STATE (the rows stay in increasing
+ * order).  It changes nothing else: the count's parity only decides in which order a step walks its tiles, not a bit of the result.
+ * A null pointer is WT_ERR_ARG.
+ *
+ * A batch that never calls any of the four launches the kernels it always launched and returns the bits it always returned.
+ */
+WTP_API int wtp_write_f(wtp_batch *b, int member, const void *f_in);
+WTP_API int wtp_write_stored(wtp_batch *b, int member, const uint16_t *h);
+WTP_API int wtp_step_count(wtp_batch *b, int64_t *steps);
+WTP_API int wtp_set_step_count(wtp_batch *b, int64_t steps);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 
