@@ -8,6 +8,7 @@
 // (c*e)*e — each preserves every bit of the result.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace wt {
 
@@ -400,6 +401,33 @@ __device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bo
 // What a step kernel writes into a far-field cell (inlet column, top and bottom rows): the equilibrium of the axial free stream (U0, 0)
 // (the page's), or that of an inclined one (U0, V0) (include/wt_polar.h "Inclined free stream").
 enum : int { FAR_AXIAL = 0, FAR_INCLINED = 1 };
+
+// The stored element of a lattice and its Load / Store.  Native storage holds the arithmetic type itself; a half batch of libwtpolar holds
+// each population as the binary16 deviation from its lattice weight (the definition is polar.hip's "half-precision population storage").
+typedef _Float16 half_t;
+
+__host__ __device__ __forceinline__ constexpr float half_w(int k) { return k == 0 ? 4.0f / 9.0f : (k <= 4 ? 1.0f / 9.0f : 1.0f / 36.0f); }
+
+// Load and Store of a half with its weight w = half_w(k): f = (float)h + w and h = RN16(f - w).
+__device__ __forceinline__ float half_load(half_t h, float w) { return (float)h + w; }
+__device__ __forceinline__ half_t half_store(float f, float w) { return (half_t)(f - w); }
+
+// Load and Store of population k in a lattice whose elements are S, for arithmetic in T: the identity where S is T (native storage),
+// half_load and half_store where S is half_t and T is float.  Every step and read-out turns a stored population into a number, and back, here.
+template <typename T, typename S>
+__device__ __forceinline__ T lat_load(const S *__restrict__ p, int k)
+{
+    static_assert(std::is_same<S, T>::value || (std::is_same<S, half_t>::value && std::is_same<T, float>::value), "native storage, or halves of fp32");
+    if constexpr (std::is_same<S, T>::value) return *p;
+    else return half_load(*p, half_w(k));
+}
+template <typename S, typename T>
+__device__ __forceinline__ S lat_store(T f, int k)
+{
+    static_assert(std::is_same<S, T>::value || (std::is_same<S, half_t>::value && std::is_same<T, float>::value), "native storage, or halves of fp32");
+    if constexpr (std::is_same<S, T>::value) return f;
+    else return half_store(f, half_w(k));
+}
 
 // binary64 with the four-operation division by tau (see "Division by the relaxation time"): operation for operation collide<double> up to the
 // relaxation; the division is the fast one iff every lane of the wave holds finite populations below 2^100 (else, and with fd.on64 = 0, IEEE).

@@ -40,9 +40,12 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // distances `wq` (wall_incoming, d2q9.hpp): eight planes laid out like population planes 1..8, plane k - 1 holding q of direction k
 // at the link's fluid cell; `wq` points at column 0 of plane 0, as `s` does.  q is read only on lanes whose source cell is solid.
 // FAR selects what the far-field branch writes: FAR_AXIAL, feq(1, U0, 0), or FAR_INCLINED, feq(1, U0, V0) with the member's cross-flow `V0`.
+// S is the stored element of the lattices `s` and `d`: every population read goes through lat_load and every one written through
+// lat_store (d2q9.hpp), the identity for native storage (S = T) and Load / Store for a half batch (S = half_t, T = float).  The
+// macroscopic planes hold T.  Interpolated walls exist for native storage only.
 // --------------------------------------------------------------------------------------
-template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR = FAR_AXIAL>
-__device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restrict__ d, T *__restrict__ macro,
+template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR = FAR_AXIAL, typename S = T>
+__device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
                                              T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr, T V0 = T(0.0))
 {
@@ -51,12 +54,12 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
     T out[9], rho, ux, uy;
     if (m[c]) {                                                    // html:287-294 solid
 #pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = s[opp_of(k) * g.plane + c];
+        for (int k = 0; k < 9; k++) out[k] = lat_load<T>(s + opp_of(k) * g.plane + c, opp_of(k));
         rho = T(1.0); ux = T(0.0); uy = T(0.0);
     } else if (gi == g.nx_g - 1) {                                 // html:301-312 outlet
         T q[9];
 #pragma unroll
-        for (int k = 0; k < 9; k++) q[k] = s[k * g.plane + c - g.pitch];
+        for (int k = 0; k < 9; k++) q[k] = lat_load<T>(s + k * g.plane + c - g.pitch, k);
         rho = q[0] + q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7] + q[8];
         ux = (q[1] + q[5] + q[8] - q[3] - q[6] - q[7]) / rho;
         uy = (q[2] + q[5] + q[6] - q[4] - q[7] - q[8]) / rho;
@@ -74,9 +77,10 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
         for (int k = 0; k < 9; k++) {
             const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
             if constexpr (WALL == WALL_INTERP) wall |= k > 0 && m[src] ? 1u << k : 0u;
-            fin[k] = m[src] ? s[opp_of(k) * g.plane + c] : s[k * g.plane + src];
+            fin[k] = m[src] ? lat_load<T>(s + opp_of(k) * g.plane + c, opp_of(k)) : lat_load<T>(s + k * g.plane + src, k);
         }
         if constexpr (WALL == WALL_INTERP) {
+            static_assert(std::is_same<S, T>::value, "interpolated bounce-back reads its neighbours from a native lattice: not available with half storage");
             // The gather above is the half-way one, nine loads in flight together, and on a link it has fetched a = s[o](x), o = opp(k),
             // the link's direction: x + e_o = src is solid and x - e_o = `behind` is the cell the link comes from.  Waves that touch
             // no wall (nearly all) skip the correction on one ballot; with a branch per direction inside the gather instead, every
@@ -96,7 +100,7 @@ __device__ __forceinline__ void site_general(const T *__restrict__ s, T *__restr
         else collide(fin, tau, out, rho, ux, uy);
     }
 #pragma unroll
-    for (int k = 0; k < 9; k++) d[k * g.plane + c] = out[k];
+    for (int k = 0; k < 9; k++) d[k * g.plane + c] = lat_store<S>(out[k], k);
     if (emit) {
         const long mp = (long)g.nxl * g.pitch;
         macro[c] = rho; macro[mp + c] = ux; macro[2 * mp + c] = uy;

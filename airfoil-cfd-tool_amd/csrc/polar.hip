@@ -27,8 +27,8 @@
 //
 // Interpolated bounce-back (wtp_enable_ibb) is another wall rule: while it is on, wtp_step launches k_step_ibb_batch, the same
 // step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
-// collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction with the interpolated link term.  A
-// batch that has it off launches the kernels it always launched, with the arguments they always had.
+// collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction (mex_member) with the interpolated link
+// rule.  A batch that has it off launches the kernels it always launched, with the arguments they always had.
 //
 // The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_wind_batch, the same
 // step_tile with feq(1, U0, V0) in its far-field cells and one more value per member, with either collision and either wall rule,
@@ -37,8 +37,8 @@
 //
 // Half-precision population storage (wtp_create_stored with WTP_STORE_HALF) is another storage of an fp32 batch: its lattices hold
 // each population as the binary16 deviation from its lattice weight, in wt_create's layout with 2-byte elements.  wtp_step launches
-// k_step_half_batch, site_general's branches with a Load in front and a Store behind, fp32 between, with either collision and either
-// far field; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
+// k_step_half_batch, site_general with half_t as its stored element: a Load in front of its branches and a Store behind, fp32 between,
+// with either collision and either far field; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
 // read-outs read the fp32 macroscopic planes and run unchanged.  A native batch launches the kernels it always launched, with the
 // arguments they always had.
 //
@@ -46,6 +46,10 @@
 // into its current lattice by k_rows_to_cols, or by k_half_rows_to_cols with a Store on the way.  A write marks the macroscopic planes
 // stale until a step has emitted and zeroes the member's running sums; with wtp_set_step_count a sweep continues where another stopped.
 // A batch that never writes launches the kernels it always launched.
+//
+// Every variant above is a kernel of its own name and code object, so that a batch runs the one its switches select and no other.
+// What the variants share is source text: one site (site_general, kernels.hpp, for every storage), one momentum-exchange body
+// (mex_member, with a link rule per wall rule), one prologue of the tiled step kernels (MemberTile), one stepping loop on the host.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -185,8 +189,20 @@ struct wtp_batch {
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
-// One step of every member: blockIdx.y is the member, blockIdx.x * 4 + wave the tile inside it (k_step's grid).  rev walks
-// members and tiles backwards on every other step, as k_step walks its tiles.
+// A wave's place in a tiled step launch, the prologue of the four tiled step kernels: blockIdx.y is the member, blockIdx.x * 4 + wave
+// the tile inside it (k_step's grid).  rev walks members and tiles backwards on every other step, as k_step walks its tiles.  A wave
+// past the last tile is not live and returns.
+struct MemberTile {
+    long ntiles, t;
+    int rev;
+    __device__ __forceinline__ MemberTile(const Geom &g, int tiles_per_col, int rev_)
+        : ntiles((long)g.nxl * tiles_per_col), t((long)blockIdx.x * 4 + (threadIdx.x >> 6)), rev(rev_) {}
+    __device__ __forceinline__ bool live() const { return t < ntiles; }
+    __device__ __forceinline__ long member() const { return rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y; }
+    __device__ __forceinline__ long tile() const { return rev ? ntiles - 1 - t : t; }
+};
+
+// One step of every member.
 template <typename T, bool EMIT, int LOADMODE>
 __global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
                                                     const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
@@ -194,17 +210,16 @@ __global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T 
                                                     int rev)
 {
     const int lane = threadIdx.x & 63;
-    const long ntiles = (long)g.nxl * tiles_per_col;
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= ntiles) return;
-    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1];
     step_tile<T, EMIT, LOADMODE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask, tiles + m * ms.tiles,
-                                 tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane);
+                                 tiles_per_col, g, 0, tau, U0, w.tile(), lane);
 }
 
 // The same step with the Smagorinsky collision (collide_les, d2q9.hpp) in every member's interior fluid cells: k_step_batch's grid,
-// walk and arguments, and cles[m] = (T)(18 sqrt(2) Cs[m]^2) beside the member's tau and U0.  A member with cles = 0 computes
+// walk (MemberTile) and arguments, and cles[m] = (T)(18 sqrt(2) Cs[m]^2) beside the member's tau and U0.  A member with cles = 0 computes
 // k_step_batch's bits.  A kernel of its own name, so that a batch with the model off runs the code object it always ran.
 template <typename T, bool EMIT, int LOADMODE>
 __global__ __launch_bounds__(256) void k_step_les_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
@@ -213,14 +228,12 @@ __global__ __launch_bounds__(256) void k_step_les_batch(const T *__restrict__ fs
                                                         const T *__restrict__ cles, int rev)
 {
     const int lane = threadIdx.x & 63;
-    const long ntiles = (long)g.nxl * tiles_per_col;
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= ntiles) return;
-    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1], c = cles[m];
     step_tile<T, EMIT, LOADMODE, false, COLLIDE_LES>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                     tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t, lane,
-                                                     0, 0, 0, c);
+                                                     tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0, c);
 }
 
 // The same step with interpolated bounce-back (wall_incoming, d2q9.hpp) at every member's links, and with either collision:
@@ -234,16 +247,15 @@ __global__ __launch_bounds__(256) void k_step_ibb_batch(const T *__restrict__ fs
                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride, int rev)
 {
     const int lane = threadIdx.x & 63;
-    const long ntiles = (long)g.nxl * tiles_per_col;
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= ntiles) return;
-    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1];
     T c = T(0.0);
     if constexpr (COLL == COLLIDE_LES) c = cles[m];
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL_INTERP>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                           tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t,
-                                                           lane, 0, 0, 0, c, wq + m * qstride);
+                                                           tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0, c,
+                                                           wq + m * qstride);
 }
 
 // The same step with an inclined free stream (include/wt_polar.h "Inclined free stream"), with either collision and either wall rule:
@@ -267,18 +279,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wind_waves<
                                                          const T *__restrict__ vwind, int rev)
 {
     const int lane = threadIdx.x & 63;
-    const long ntiles = (long)g.nxl * tiles_per_col;
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= ntiles) return;
-    const long m = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1], V0 = vwind[m];
     T c = T(0.0);
     if constexpr (COLL == COLLIDE_LES) c = cles[m];
     const T *q = nullptr;
     if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, rev ? ntiles - 1 - t : t,
-                                                                  lane, 0, 0, 0, c, q, V0);
+                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
+                                                                  c, q, V0);
 }
 
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
@@ -310,59 +321,8 @@ __global__ void k_fill_wind(T *__restrict__ f0, T *__restrict__ f1, T *__restric
 //   the fp32 arithmetic produced.
 //   Start.  wtp_init_equilibrium stores Store(v_k) of the fp32 start values it forms without the mode, including the
 //   inclined-stream start; the macroscopic planes are unchanged.
-typedef _Float16 half_t;
-
-__host__ __device__ __forceinline__ constexpr float half_w(int k) { return k == 0 ? 4.0f / 9.0f : (k <= 4 ? 1.0f / 9.0f : 1.0f / 36.0f); }
-__device__ __forceinline__ float half_load(const half_t *__restrict__ p, int k) { return (float)*p + half_w(k); }
-__device__ __forceinline__ half_t half_store(float f, int k) { return (half_t)(f - half_w(k)); }
-
-// One site of a half batch: site_general's branches in site_general's order (solid, then outlet, then far field, then interior)
-// with Load and Store around them.  s, d, m point at column 0 of the member's lattices and mask, mm at its macroscopic planes.
-// KEEP IN STEP: the four branches are site_general's text (kernels.hpp) with half_load in place of each read of s and half_store in
-// place of each write of d; a change to a branch there is made here too.
-template <bool EMIT, int COLL, int FAR>
-__device__ __forceinline__ void site_half(const half_t *__restrict__ s, half_t *__restrict__ d, float *__restrict__ mm,
-                                          const uint8_t *__restrict__ m, const Geom &g, int i, int j, float tau, float U0, float c_les,
-                                          float V0)
-{
-    const long P = g.plane;
-    const long c = (long)i * g.pitch + j;
-    float out[9], rho, ux, uy;
-    if (m[c]) {                                                    // solid
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = half_load(s + opp_of(k) * P + c, opp_of(k));
-        rho = 1.0f; ux = 0.0f; uy = 0.0f;
-    } else if (i == g.nxl - 1) {                                   // outlet
-        float q[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) q[k] = half_load(s + k * P + c - g.pitch, k);
-        rho = q[0] + q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7] + q[8];
-        ux = (q[1] + q[5] + q[8] - q[3] - q[6] - q[7]) / rho;
-        uy = (q[2] + q[5] + q[6] - q[4] - q[7] - q[8]) / rho;
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = q[k];
-    } else if (i == 0 || j == g.ny - 1 || j == 0) {                // far field
-        rho = 1.0f; ux = U0;
-        if constexpr (FAR == FAR_INCLINED) uy = V0;
-        else uy = 0.0f;
-        feq_all(rho, ux, uy, out);
-    } else {                                                       // interior fluid
-        float fin[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
-            fin[k] = m[src] ? half_load(s + opp_of(k) * P + c, opp_of(k)) : half_load(s + k * P + src, k);
-        }
-        if constexpr (COLL == COLLIDE_LES) collide_les<float>(fin, tau, c_les, out, rho, ux, uy);
-        else collide(fin, tau, out, rho, ux, uy);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) d[k * P + c] = half_store(out[k], k);
-    if (EMIT) {
-        const long mp = (long)g.nxl * g.pitch;
-        mm[c] = rho; mm[mp + c] = ux; mm[2 * mp + c] = uy;
-    }
-}
+// half_t, half_w, Load and Store (half_load, half_store; lat_load, lat_store with half_t elements) are d2q9.hpp's: the step, the fill,
+// the transposes and the momentum exchange below all take them from there.
 
 // Blocks of one member's k_step_half_batch grid.
 static unsigned half_step_blocks(const Geom &g)
@@ -374,9 +334,10 @@ static unsigned half_step_blocks(const Geom &g)
 // One step of every member of a half batch: one site per lane and load, so that a wave loads 64 consecutive halves of a plane (128
 // bytes) at a time.  Grid (ceil(NX * pitch / 256 / 4), B): blockIdx.y is the member, blockIdx.x * 4 + wave a run of 256 rows of one
 // column, whose four chunks of 64 rows the wave walks one after the other, as k_step_batch walks a ragged tile; rev walks members and
-// runs backwards on every other step, as k_step_batch walks its tiles.  There are no tile classes: every site takes site_half.
+// runs backwards on every other step, as k_step_batch walks its tiles.  There are no tile classes: every site takes site_general
+// (kernels.hpp) with half_t as its stored element, which puts Load in front of its four branches and Store behind them.
 // Two rows per lane with packed halves (dword loads of two rows, packed conversion, a clean pair's two sites collided in one lane,
-// every other pair through site_half) was built, computed the same bits and measured slower in every walk tried, 26.9 us at best
+// every other pair through the general site) was built, computed the same bits and measured slower in every walk tried, 26.9 us at best
 // against 21.7 at 320x160 with 32 members (profiles/polar_half_cost.txt), and is not kept.
 // COLL is the collision of the interior branch (collide or collide_les with cles[m]), FAR the far field (feq(1, U0, 0), or
 // feq(1, U0, V0) with vwind[m]); cles is read only for COLLIDE_LES and vwind only for FAR_INCLINED.  fp32 arithmetic only.  ms.lat
@@ -406,7 +367,7 @@ __global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restric
 #pragma unroll 1
     for (int v = 0; v < 4; v++) {
         const int j = j0 + v * 64 + lane;
-        if (j < g.ny) site_half<EMIT, COLL, FAR>(s, d, mm, m, g, i, j, tau, U0, c_les, V0);
+        if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0);
     }
 }
 
@@ -418,7 +379,7 @@ __global__ void k_fill_half(half_t *__restrict__ f0, half_t *__restrict__ f1, fl
     const long mp = (long)g.nxl * g.pitch;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) { const half_t h = half_store(iv.v[k], k); f0[k * n + t] = h; f1[k * n + t] = h; }
+        for (int k = 0; k < 9; k++) { const half_t h = lat_store<half_t>(iv.v[k], k); f0[k * n + t] = h; f1[k * n + t] = h; }
         if (t < mp) { macro[t] = 1.0f; macro[mp + t] = iv.u0; macro[2 * mp + t] = v0; }
     }
 }
@@ -430,7 +391,7 @@ __global__ void k_half_cols_to_rows(const half_t *__restrict__ src, float *__res
     const int bx = blockIdx.x * 32, by = blockIdx.y * 32;   // bx: j block, by: x block
     for (int r = threadIdx.y; r < 32; r += blockDim.y) {
         const int x = by + r, j = bx + threadIdx.x;
-        if (x < W && j < ny) tile[r][threadIdx.x] = (float)src[(long)(i0 + x) * pitch + j] + w;
+        if (x < W && j < ny) tile[r][threadIdx.x] = half_load(src[(long)(i0 + x) * pitch + j], w);
     }
     __syncthreads();
     for (int r = threadIdx.y; r < 32; r += blockDim.y) {
@@ -452,7 +413,7 @@ __global__ void k_half_rows_to_cols(const float *__restrict__ src, half_t *__res
     __syncthreads();
     for (int r = threadIdx.y; r < 32; r += blockDim.y) {
         const int x = bx + r, j = by + threadIdx.x;
-        if (x < W && j < ny) dst[(long)(i0 + x) * pitch + j] = (half_t)(tile[threadIdx.x][r] - w);
+        if (x < W && j < ny) dst[(long)(i0 + x) * pitch + j] = half_store(tile[threadIdx.x][r], w);
     }
 }
 
@@ -583,6 +544,7 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
     if (threadIdx.x == 0) { mz[m] = s; tickets[m * kTicketStride] = 0; }
 }
 
+// The body of k_mex_batch, k_mex_ibb_batch and k_mex_half_batch.
 // Momentum exchange of every member in one launch: grid (ceil(W / kLoadsWaves), B), one wave per (member, column), W the widest
 // member's window.  Definition (include/wt_polar.h): directions e_k, k = 1..8, as d2q9.hpp / html:238-248; cell (i, j) covers
 // [i, i+1) x [j, j+1).  After step n the current lattice holds, in every interior fluid cell x (not solid, 1 <= i <= NX-2,
@@ -599,9 +561,124 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
 // 64 rows, one row per lane: the mask bytes of columns i-1, i, i+1 at rows j-1, j, j+1, then a population only on the lanes that
 // own a link in its direction.  The column's terms are added by wave_sum; the member's last block (member_done) adds the
 // columns' partials in column order, each of the four sums on a wave of its own.
-// KEEP IN STEP: k_mex_ibb_batch below is this kernel with another link term, body included, and k_mex_half_batch this kernel with
-// the loaded value of a half batch.  The link bits, the walk, the ticket and the final sum through LDS are the same text in all
-// three: a change to any of them here is made there too.
+// E is the lattice's stored element.  `link(fc, mk, g, m, coloff, j, k, t, q)` is the link rule: for the link of direction k that the cell
+// at row j of the column owns (fc and mk the column in population plane 0 and in the mask, coloff its offset in a padded plane), t is
+// the magnitude of the momentum the link hands over, so that F_link = t e_k, and q the distance from the cell's centre to the link's
+// point, r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky), both doubles.  The definition above is the half-way rule, t = 2 f*_k(x) and q = 0.5.
+template <typename E, typename Link>
+__device__ __forceinline__ void mex_member(const E *__restrict__ f, const uint8_t *__restrict__ mask, const Geom &g, const MemberStrides &ms,
+                                           const double *__restrict__ ref, const int32_t *__restrict__ win, MexPartial *__restrict__ col,
+                                           unsigned int *__restrict__ tickets, double *__restrict__ fx, double *__restrict__ fy,
+                                           double *__restrict__ mz, long long *__restrict__ links, const Link &link)
+{
+    const long m = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int nx = g.nxl, ny = g.ny;
+    const int width = win[2 * m + 1];
+    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
+    if (c < width) {                                                // (wave-uniform)
+        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
+        const long coloff = g.pitch + (long)i * g.pitch;            // column i of a padded plane
+        const uint8_t *mk = mask + m * ms.mask + coloff;            // ... of the mask
+        const E *fc = f + m * ms.lat + coloff;                      // ... of population plane 0
+        const double xr = ref[2 * m], yr = ref[2 * m + 1];
+        double sx = 0.0, sy = 0.0, sm = 0.0;
+        long long n = 0;
+        for (int j0 = 0; j0 < ny; j0 += 64) {
+            const int j = j0 + lane;
+            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
+            if (j >= 1 && j <= ny - 2 && !mk[j]) {
+                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
+                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
+                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
+            }
+            if (__ballot(s != 0) == 0ULL) continue;
+#pragma unroll
+            for (int k = 1; k <= 8; k++) {
+                if (!(s >> k & 1u)) continue;
+                double t, q;                                        // the link's magnitude and its distance to the wall
+                link(fc, mk, g, m, coloff, j, k, t, q);
+                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
+                const double rx = ((double)i + 0.5) + q * (double)ex_of(k), ry = ((double)j + 0.5) + q * (double)ey_of(k);
+                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
+                sx += flx;
+                sy += fly;
+                sm += a - b;
+                n += 1;
+            }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
+        if (lane == 0) {
+            MexPartial p;
+            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
+            col[m * nx + c] = p;
+        }
+    }
+    constexpr int NT = kLoadsWaves * 64;
+    __shared__ double sh[3][NT];
+    __shared__ long long shn[NT];
+    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
+    const volatile MexPartial *vc = col + m * nx;
+    const int w = (int)(threadIdx.x >> 6);
+    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
+    long long sn = 0;                                               // lane 0 of wave 3: links
+    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
+        const int p = c0 + (int)threadIdx.x;
+        const bool in = p < width;
+        sh[0][threadIdx.x] = in ? vc[p].fx : 0.0;
+        sh[1][threadIdx.x] = in ? vc[p].fy : 0.0;
+        sh[2][threadIdx.x] = in ? vc[p].mz : 0.0;
+        shn[threadIdx.x] = in ? vc[p].links : 0;
+        __syncthreads();
+        if (lane == 0 && w < 4) {
+            const int cnt = width - c0 < NT ? width - c0 : NT;
+            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
+            else for (int k = 0; k < cnt; k++) sn += shn[k];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
+        else if (w == 1) fy[m] = s;
+        else if (w == 2) mz[m] = s;
+        else if (w == 3) links[m] = sn;
+    }
+}
+
+// The half-way link: t = 2 f*_k(x), f*_k(x) the stored population through Load (lat_load: the identity for a native lattice,
+// (float)h + w_k for a half batch) converted exactly to double, and q = 0.5.
+template <typename T>
+struct LinkHalfway {
+    template <typename E>
+    __device__ __forceinline__ void operator()(const E *__restrict__ fc, const uint8_t *__restrict__, const Geom &g, long, long, int j, int k,
+                                               double &t, double &q) const
+    {
+        t = 2.0 * (double)lat_load<T>(fc + k * g.plane + j, k);
+        q = 0.5;
+    }
+};
+
+// The interpolated link (include/wt_polar.h "Interpolated bounce-back"): t = (double)a + (double)b, a = f*_k(x) and b the value the next
+// step will reflect (wall_incoming of the current lattice, in T), and q the link's wall distance converted exactly, so that the link's
+// point is the wall point.  wq holds the members' wall distances (eight planes each, laid out like population planes 1..8, qstride
+// elements apart), read, like the populations, only on the lanes that own a link.  At q = 0.5 both are the half-way link's.
+template <typename T>
+struct LinkInterp {
+    const T *__restrict__ wq;
+    long qstride;
+    __device__ __forceinline__ void operator()(const T *__restrict__ fc, const uint8_t *__restrict__ mk, const Geom &g, long m, long coloff, int j,
+                                               int k, double &t, double &q) const
+    {
+        const long back = j - ey_of(k) - (long)ex_of(k) * g.pitch;      // x - e_k, from column i
+        const T qk = wq[m * qstride + coloff + (k - 1) * g.plane + j], fa = fc[k * g.plane + j];
+        const T fb = wall_incoming<T>(qk, fa, fc + k * g.plane + back, mk[back] != 0, fc + opp_of(k) * g.plane + j);
+        t = (double)fa + (double)fb;
+        q = (double)qk;
+    }
+};
+
+// The three kernels of the momentum exchange: one body (mex_member), each a kernel of its own name and code object, so that a batch runs
+// the one its storage and wall rule select (launch_mex) and no other.  ms.lat counts the lattice's elements: T, or halves.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
@@ -609,86 +686,9 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restr
                                                    double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
                                                    long long *__restrict__ links)
 {
-    const long m = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int nx = g.nxl, ny = g.ny;
-    const int width = win[2 * m + 1];
-    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
-    if (c < width) {                                                // (wave-uniform)
-        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
-        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
-        const T *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;               // column i of population plane 0
-        const double xr = ref[2 * m], yr = ref[2 * m + 1];
-        double sx = 0.0, sy = 0.0, sm = 0.0;
-        long long n = 0;
-        for (int j0 = 0; j0 < ny; j0 += 64) {
-            const int j = j0 + lane;
-            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
-            if (j >= 1 && j <= ny - 2 && !mk[j]) {
-                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
-                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
-                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
-            }
-            if (__ballot(s != 0) == 0ULL) continue;
-#pragma unroll
-            for (int k = 1; k <= 8; k++) {
-                if (!(s >> k & 1u)) continue;
-                const double t = 2.0 * (double)fc[k * g.plane + j];
-                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
-                const double rx = ((double)i + 0.5) + 0.5 * (double)ex_of(k), ry = ((double)j + 0.5) + 0.5 * (double)ey_of(k);
-                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
-                sx += flx;
-                sy += fly;
-                sm += a - b;
-                n += 1;
-            }
-        }
-        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
-        if (lane == 0) {
-            MexPartial p;
-            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
-            col[m * nx + c] = p;
-        }
-    }
-    constexpr int NT = kLoadsWaves * 64;
-    __shared__ double sh[3][NT];
-    __shared__ long long shn[NT];
-    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
-    const volatile MexPartial *vc = col + m * nx;
-    const int w = (int)(threadIdx.x >> 6);
-    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
-    long long sn = 0;                                               // lane 0 of wave 3: links
-    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
-        const int q = c0 + (int)threadIdx.x;
-        const bool in = q < width;
-        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
-        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
-        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
-        shn[threadIdx.x] = in ? vc[q].links : 0;
-        __syncthreads();
-        if (lane == 0 && w < 4) {
-            const int cnt = width - c0 < NT ? width - c0 : NT;
-            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
-            else for (int k = 0; k < cnt; k++) sn += shn[k];
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
-        else if (w == 1) fy[m] = s;
-        else if (w == 2) mz[m] = s;
-        else if (w == 3) links[m] = sn;
-    }
+    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkHalfway<T>{});
 }
 
-// The momentum exchange of members that step with interpolated bounce-back (include/wt_polar.h "Interpolated bounce-back"):
-// k_mex_batch's grid, walk, arguments and final sum, with the link's term ((double)a + (double)b) e_k, a = f*_k(x) and b the value the
-// next step will reflect (wall_incoming of the current lattice, in T), and the link's point the wall point
-// r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky), q converted exactly.  wq holds the members' wall distances (eight planes each, laid out
-// like population planes 1..8, qstride elements apart), read, like the populations, only on the lanes that own a link.  At q = 0.5
-// both are k_mex_batch's.  A kernel of its own, body included, so that k_mex_batch compiles to the code it always compiled to.
-// KEEP IN STEP: everything but the three lines that form q, fa and fb and the two that use them (t, rx / ry) is k_mex_batch's text,
-// the ticket (member_done) and the final sum through LDS after it included: a change to either kernel's copy is made in the other.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
@@ -696,163 +696,16 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__r
                                                    double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
                                                    long long *__restrict__ links, const T *__restrict__ wq, long qstride)
 {
-    const long m = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int nx = g.nxl, ny = g.ny;
-    const int width = win[2 * m + 1];
-    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
-    if (c < width) {                                                // (wave-uniform)
-        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
-        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
-        const T *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;               // column i of population plane 0
-        const T *qc = wq + m * qstride + g.pitch + (long)i * g.pitch;             // column i of the plane of direction 1
-        const double xr = ref[2 * m], yr = ref[2 * m + 1];
-        double sx = 0.0, sy = 0.0, sm = 0.0;
-        long long n = 0;
-        for (int j0 = 0; j0 < ny; j0 += 64) {
-            const int j = j0 + lane;
-            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
-            if (j >= 1 && j <= ny - 2 && !mk[j]) {
-                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
-                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
-                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
-            }
-            if (__ballot(s != 0) == 0ULL) continue;
-#pragma unroll
-            for (int k = 1; k <= 8; k++) {
-                if (!(s >> k & 1u)) continue;
-                const long back = j - ey_of(k) - (long)ex_of(k) * g.pitch;      // x - e_k, from column i
-                const T q = qc[(k - 1) * g.plane + j], fa = fc[k * g.plane + j];
-                const T fb = wall_incoming<T>(q, fa, fc + k * g.plane + back, mk[back] != 0, fc + opp_of(k) * g.plane + j);
-                const double t = (double)fa + (double)fb, hq = (double)q;
-                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
-                const double rx = ((double)i + 0.5) + hq * (double)ex_of(k), ry = ((double)j + 0.5) + hq * (double)ey_of(k);
-                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
-                sx += flx;
-                sy += fly;
-                sm += a - b;
-                n += 1;
-            }
-        }
-        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
-        if (lane == 0) {
-            MexPartial p;
-            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
-            col[m * nx + c] = p;
-        }
-    }
-    constexpr int NT = kLoadsWaves * 64;
-    __shared__ double sh[3][NT];
-    __shared__ long long shn[NT];
-    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
-    const volatile MexPartial *vc = col + m * nx;
-    const int w = (int)(threadIdx.x >> 6);
-    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
-    long long sn = 0;                                               // lane 0 of wave 3: links
-    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
-        const int q = c0 + (int)threadIdx.x;
-        const bool in = q < width;
-        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
-        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
-        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
-        shn[threadIdx.x] = in ? vc[q].links : 0;
-        __syncthreads();
-        if (lane == 0 && w < 4) {
-            const int cnt = width - c0 < NT ? width - c0 : NT;
-            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
-            else for (int k = 0; k < cnt; k++) sn += shn[k];
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
-        else if (w == 1) fy[m] = s;
-        else if (w == 2) mz[m] = s;
-        else if (w == 3) links[m] = sn;
-    }
+    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkInterp<T>{wq, qstride});
 }
 
-// The momentum exchange of members of a half batch: k_mex_batch's grid, walk, arguments and final sum, with the loaded value
-// (float)h + w_k (half_load) as f*_k(x), converted exactly to double.  ms.lat counts halves.  A kernel of its own, body included, so
-// that k_mex_batch compiles to the code it always compiled to.
-// KEEP IN STEP: everything but the line that forms t is k_mex_batch's text, the ticket (member_done) and the final sum through LDS
-// after it included: a change to either kernel's copy is made in the other.
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_half_batch(const half_t *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
                                                    MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
                                                    double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
                                                    long long *__restrict__ links)
 {
-    const long m = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int nx = g.nxl, ny = g.ny;
-    const int width = win[2 * m + 1];
-    const int c = (int)blockIdx.x * kLoadsWaves + (int)(threadIdx.x >> 6);
-    if (c < width) {                                                // (wave-uniform)
-        const int i = win[2 * m] + c;                               // 1 <= i <= NX-2 (mex_window)
-        const uint8_t *mk = mask + m * ms.mask + g.pitch + (long)i * g.pitch;      // column i of the padded mask
-        const half_t *fc = f + m * ms.lat + g.pitch + (long)i * g.pitch;          // column i of population plane 0
-        const double xr = ref[2 * m], yr = ref[2 * m + 1];
-        double sx = 0.0, sy = 0.0, sm = 0.0;
-        long long n = 0;
-        for (int j0 = 0; j0 < ny; j0 += 64) {
-            const int j = j0 + lane;
-            unsigned s = 0;                                         // bit k: this lane's cell owns a link in direction k
-            if (j >= 1 && j <= ny - 2 && !mk[j]) {
-                const uint8_t *l = mk - g.pitch + j, *r = mk + g.pitch + j;
-                s = (r[0] ? 1u << 1 : 0u) | (mk[j + 1] ? 1u << 2 : 0u) | (l[0] ? 1u << 3 : 0u) | (mk[j - 1] ? 1u << 4 : 0u) |
-                    (r[1] ? 1u << 5 : 0u) | (l[1] ? 1u << 6 : 0u) | (l[-1] ? 1u << 7 : 0u) | (r[-1] ? 1u << 8 : 0u);
-            }
-            if (__ballot(s != 0) == 0ULL) continue;
-#pragma unroll
-            for (int k = 1; k <= 8; k++) {
-                if (!(s >> k & 1u)) continue;
-                const double t = 2.0 * (double)half_load(fc + k * g.plane + j, k);
-                const double flx = t * (double)ex_of(k), fly = t * (double)ey_of(k);
-                const double rx = ((double)i + 0.5) + 0.5 * (double)ex_of(k), ry = ((double)j + 0.5) + 0.5 * (double)ey_of(k);
-                const double a = (rx - xr) * fly, b = (ry - yr) * flx;
-                sx += flx;
-                sy += fly;
-                sm += a - b;
-                n += 1;
-            }
-        }
-        sx = wave_sum(sx); sy = wave_sum(sy); sm = wave_sum(sm); n = wave_sum(n);
-        if (lane == 0) {
-            MexPartial p;
-            p.fx = sx; p.fy = sy; p.mz = sm; p.links = n;
-            col[m * nx + c] = p;
-        }
-    }
-    constexpr int NT = kLoadsWaves * 64;
-    __shared__ double sh[3][NT];
-    __shared__ long long shn[NT];
-    if (!member_done<true, kTicketStride>(tickets, m, gridDim.x)) return;
-    const volatile MexPartial *vc = col + m * nx;
-    const int w = (int)(threadIdx.x >> 6);
-    double s = 0.0;                                                 // lane 0 of wave 0, 1, 2: Fx, Fy, Mz
-    long long sn = 0;                                               // lane 0 of wave 3: links
-    for (int c0 = 0; c0 < width; c0 += NT) {                        // NT partials at a time through LDS, added in column order
-        const int q = c0 + (int)threadIdx.x;
-        const bool in = q < width;
-        sh[0][threadIdx.x] = in ? vc[q].fx : 0.0;
-        sh[1][threadIdx.x] = in ? vc[q].fy : 0.0;
-        sh[2][threadIdx.x] = in ? vc[q].mz : 0.0;
-        shn[threadIdx.x] = in ? vc[q].links : 0;
-        __syncthreads();
-        if (lane == 0 && w < 4) {
-            const int cnt = width - c0 < NT ? width - c0 : NT;
-            if (w < 3) for (int k = 0; k < cnt; k++) s += sh[w][k];
-            else for (int k = 0; k < cnt; k++) sn += shn[k];
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        if (w == 0) { fx[m] = s; tickets[m * kTicketStride] = 0; }
-        else if (w == 1) fy[m] = s;
-        else if (w == 2) mz[m] = s;
-        else if (w == 3) links[m] = sn;
-    }
+    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkHalfway<float>{});
 }
 
 // Every element of p[0, n) set to v: the wall distances' default.
@@ -1161,19 +1014,24 @@ static Init9<T> wind_init(double u0, double v0)
     return iv;
 }
 
+// The fp start values of member m, and its cross-flow v0: wind_init with an inclined free stream, else wt_init_equilibrium's values and 0.
+template <typename T>
+static Init9<T> start_values(const wtp_batch *b, int m, double u0, double *v0)
+{
+    *v0 = b->wind ? b->wind_host[(size_t)m] : 0.0;
+    return b->wind ? wind_init<T>(u0, *v0) : equilibrium_init<T>(u0);
+}
+
 template <typename T>
 static int init_impl(wtp_batch *b, const double *u0)
 {
     for (int m = 0; m < b->members; m++) {
-        if (b->wind) {
-            const double v0 = b->wind_host[(size_t)m];
-            hipLaunchKernelGGL(k_fill_wind<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m), b->g,
-                               wind_init<T>(u0[m], v0), (T)v0);
-        } else {
-            const Init9<T> iv = equilibrium_init<T>(u0[m]);      // wt_init_equilibrium's values
-            hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m),
-                               b->g, iv);
-        }
+        double v0;
+        const Init9<T> iv = start_values<T>(b, m, u0[m], &v0);
+        if (b->wind)
+            hipLaunchKernelGGL(k_fill_wind<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m), b->g, iv, (T)v0);
+        else
+            hipLaunchKernelGGL(k_fill_equilibrium<T>, dim3(2048), dim3(256), 0, b->st, fptr<T>(b, 0, m), fptr<T>(b, 1, m), macro_of<T>(b, m), b->g, iv);
         HIP_TRY(hipGetLastError());
     }
     return WT_OK;
@@ -1183,8 +1041,8 @@ static int init_impl(wtp_batch *b, const double *u0)
 static int init_half(wtp_batch *b, const double *u0)
 {
     for (int m = 0; m < b->members; m++) {
-        const double v0 = b->wind ? b->wind_host[(size_t)m] : 0.0;
-        const Init9<float> iv = b->wind ? wind_init<float>(u0[m], v0) : equilibrium_init<float>(u0[m]);
+        double v0;
+        const Init9<float> iv = start_values<float>(b, m, u0[m], &v0);
         hipLaunchKernelGGL(k_fill_half, dim3(2048), dim3(256), 0, b->st, fptr<half_t>(b, 0, m), fptr<half_t>(b, 1, m), macro_of<float>(b, m),
                            b->g, iv, (float)v0);
         HIP_TRY(hipGetLastError());
@@ -1325,42 +1183,49 @@ static auto half_kernel(bool emit)
     return emit ? k_step_half_batch<true, COLL, FAR> : k_step_half_batch<false, COLL, FAR>;
 }
 
-// step_impl<float> for a half batch: the same loop, samples included, around k_step_half_batch.
-static int step_half(wtp_batch *b, int nsteps, int sample_every)
+// The stepping loop of wtp_step: which steps sample and which emit, the flip of the lattices, the step count and the history rows.
+// `launch(emit, rev)` enqueues one step of every member from the current lattice into the other; T is the type of the read-outs.
+template <typename T, typename Launch>
+static int step_loop(wtp_batch *b, int nsteps, int sample_every, Launch launch)
 {
-    const dim3 grid(half_step_blocks(b->g), (unsigned)b->members), block(256);
     for (int s = 0; s < nsteps; s++) {
         const long long n = b->steps_done + 1;
         const bool sample = sample_every > 0 && n % sample_every == 0;
         const bool emit = sample || s + 1 == nsteps;
-        const auto k_step = b->wind ? (b->les ? half_kernel<COLLIDE_LES, FAR_INCLINED>(emit) : half_kernel<COLLIDE_BGK, FAR_INCLINED>(emit))
-                                    : (b->les ? half_kernel<COLLIDE_LES, FAR_AXIAL>(emit) : half_kernel<COLLIDE_BGK, FAR_AXIAL>(emit));
-        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
-                           macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
-                           (const float *)b->wind_v, (int)(b->steps_done & 1));
+        launch(emit, (int)(b->steps_done & 1));
         HIP_TRY(hipGetLastError());
         b->cur = 1 - b->cur;
         b->steps_done = n;
         if (sample) {
-            WT_TRY(sample_into<float>(b, (int)b->h_step.size()));
+            WT_TRY(sample_into<T>(b, (int)b->h_step.size()));
             b->h_step.push_back(n);
         }
     }
     return WT_OK;
 }
 
+// The steps of a half batch: k_step_half_batch, with the fp32 read-outs.
+static int step_half(wtp_batch *b, int nsteps, int sample_every)
+{
+    const dim3 grid(half_step_blocks(b->g), (unsigned)b->members), block(256);
+    return step_loop<float>(b, nsteps, sample_every, [&](bool emit, int rev) {
+        const auto k_step = b->wind ? (b->les ? half_kernel<COLLIDE_LES, FAR_INCLINED>(emit) : half_kernel<COLLIDE_BGK, FAR_INCLINED>(emit))
+                                    : (b->les ? half_kernel<COLLIDE_LES, FAR_AXIAL>(emit) : half_kernel<COLLIDE_BGK, FAR_AXIAL>(emit));
+        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
+                           macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
+                           (const float *)b->wind_v, rev);
+    });
+}
+
+// The steps of a native batch: the tiled kernel that the free stream, the wall rule and the collision select.
 template <typename T>
 static int step_impl(wtp_batch *b, int nsteps, int sample_every)
 {
     const long ntiles = (long)b->g.nxl * b->tiles_per_col;
     const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)b->members), block(256);
-    for (int s = 0; s < nsteps; s++) {
-        const long long n = b->steps_done + 1;
-        const bool sample = sample_every > 0 && n % sample_every == 0;
-        const bool emit = sample || s + 1 == nsteps;
+    return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
-        const int rev = (int)(b->steps_done & 1);
         if (b->wind) {
             const auto k_step = b->ibb ? (b->les ? wind_kernel<T, COLLIDE_LES, WALL_INTERP>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_INTERP>(emit))
                                        : (b->les ? wind_kernel<T, COLLIDE_LES, WALL_HALFWAY>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_HALFWAY>(emit));
@@ -1381,15 +1246,7 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
             hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
                                b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
         }
-        HIP_TRY(hipGetLastError());
-        b->cur = 1 - b->cur;
-        b->steps_done = n;
-        if (sample) {
-            WT_TRY(sample_into<T>(b, (int)b->h_step.size()));
-            b->h_step.push_back(n);
-        }
-    }
-    return WT_OK;
+    });
 }
 
 extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const double *u0, int sample_every)
@@ -1424,15 +1281,16 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
 // ------------------------------------------------------------------------------------------
 // Smagorinsky subgrid viscosity
 // ------------------------------------------------------------------------------------------
-// c = 18 sqrt(2) Cs^2 of every member: the product formed left to right in double, then rounded to T once.
-template <typename T>
-static int upload_les(wtp_batch *b, const double *cs)
+// One value per member, value_of(m) rounded to T once, into *dev (allocated on the first call) once the steps already enqueued, which
+// read the previous values, have run.
+template <typename T, typename Value>
+static int upload_per_member(wtp_batch *b, void **dev, Value value_of)
 {
     std::vector<T> v((size_t)b->members);
-    for (size_t m = 0; m < v.size(); m++) v[m] = (T)(18.0 * std::sqrt(2.0) * cs[m] * cs[m]);
-    if (!b->les_c) HIP_TRY(hipMalloc(&b->les_c, v.size() * sizeof(T)));
-    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
-    HIP_TRY(hipMemcpy(b->les_c, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    for (size_t m = 0; m < v.size(); m++) v[m] = (T)value_of(m);
+    if (!*dev) HIP_TRY(hipMalloc(dev, v.size() * sizeof(T)));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    HIP_TRY(hipMemcpy(*dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return WT_OK;
 }
 
@@ -1443,7 +1301,8 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
     for (int m = 0; m < b->members; m++)
         if (!std::isfinite(cs[m]) || cs[m] < 0.0 || cs[m] > 0.5) return fail(WT_ERR_ARG, "cs[%d] must be finite and in [0, 0.5]", m);
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? upload_les<float>(b, cs) : upload_les<double>(b, cs));
+    const auto c = [&](size_t m) { return 18.0 * std::sqrt(2.0) * cs[m] * cs[m]; };      // c = 18 sqrt(2) Cs^2: formed left to right in double
+    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->les_c, c) : upload_per_member<double>(b, &b->les_c, c));
     b->les = true;
     return WT_OK;
 }
@@ -1451,18 +1310,6 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
 // ------------------------------------------------------------------------------------------
 // inclined free stream
 // ------------------------------------------------------------------------------------------
-// V0 of every member, rounded to T once.
-template <typename T>
-static int upload_wind(wtp_batch *b, const double *v0)
-{
-    std::vector<T> v((size_t)b->members);
-    for (size_t m = 0; m < v.size(); m++) v[m] = (T)v0[m];
-    if (!b->wind_v) HIP_TRY(hipMalloc(&b->wind_v, v.size() * sizeof(T)));
-    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
-    HIP_TRY(hipMemcpy(b->wind_v, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return WT_OK;
-}
-
 extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
 {
     WT_TRY(check_batch(b));
@@ -1470,7 +1317,8 @@ extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
     for (int m = 0; m < b->members; m++)
         if (!std::isfinite(v0[m]) || std::fabs(v0[m]) > 0.35) return fail(WT_ERR_ARG, "v0[%d] must be finite and in [-0.35, 0.35]", m);
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? upload_wind<float>(b, v0) : upload_wind<double>(b, v0));
+    const auto v = [&](size_t m) { return v0[m]; };
+    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->wind_v, v) : upload_per_member<double>(b, &b->wind_v, v));
     b->wind_host.assign(v0, v0 + b->members);
     b->wind = true;
     return WT_OK;
@@ -1743,19 +1591,29 @@ extern "C" int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_ev
     return WT_OK;
 }
 
-// One [NX][pitch] plane of the device (y fastest) to [NY][NX] rows on the host, through the stage.
-template <typename T>
-static int read_plane(wtp_batch *b, const T *src_cols, long pitch, T *host_dst)
+// One plane of the device to [NY][NX] rows of E on the host, through the stage.  `launch(grd, blk, dst)` enqueues the conversion of the
+// plane into the stage, dst, as k_cols_to_rows walks it.
+template <typename E, typename Launch>
+static int read_plane_by(wtp_batch *b, E *host_dst, Launch launch)
 {
     const Geom &g = b->g;
-    const size_t bytes = (size_t)b->nx * g.ny * sizeof(T);
+    const size_t bytes = (size_t)b->nx * g.ny * sizeof(E);
     WT_TRY(ensure_stage(b, bytes));
     dim3 blk(32, 8), grd((g.ny + 31) / 32, (b->nx + 31) / 32);
-    hipLaunchKernelGGL(k_cols_to_rows<T>, grd, blk, 0, b->st, src_cols, reinterpret_cast<T *>(b->stage), 0, b->nx, g.ny, pitch);
+    launch(grd, blk, reinterpret_cast<E *>(b->stage));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_dst, b->stage, bytes, hipMemcpyDeviceToHost, b->st));
     HIP_TRY(hipStreamSynchronize(b->st));
     return WT_OK;
+}
+
+// One [NX][pitch] plane of the device (y fastest), as it is stored.
+template <typename T>
+static int read_plane(wtp_batch *b, const T *src_cols, long pitch, T *host_dst)
+{
+    return read_plane_by<T>(b, host_dst, [&](dim3 grd, dim3 blk, T *dst) {
+        hipLaunchKernelGGL(k_cols_to_rows<T>, grd, blk, 0, b->st, src_cols, dst, 0, b->nx, b->g.ny, pitch);
+    });
 }
 
 static int check_member(const wtp_batch *b, int member)
@@ -1779,15 +1637,11 @@ static int read_f_half(wtp_batch *b, int member, float *out)
 {
     const Geom &g = b->g;
     const size_t n = (size_t)b->nx * g.ny;
-    WT_TRY(ensure_stage(b, n * sizeof(float)));
-    dim3 blk(32, 8), grd((g.ny + 31) / 32, (b->nx + 31) / 32);
-    for (int k = 0; k < 9; k++) {
-        hipLaunchKernelGGL(k_half_cols_to_rows, grd, blk, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, member) + k * g.plane + g.pitch,
-                           reinterpret_cast<float *>(b->stage), 0, b->nx, g.ny, g.pitch, half_w(k));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out + k * n, b->stage, n * sizeof(float), hipMemcpyDeviceToHost, b->st));
-        HIP_TRY(hipStreamSynchronize(b->st));
-    }
+    const half_t *lat = fptr<half_t>(b, b->cur, member);
+    for (int k = 0; k < 9; k++)
+        WT_TRY(read_plane_by<float>(b, out + k * n, [&](dim3 grd, dim3 blk, float *dst) {
+            hipLaunchKernelGGL(k_half_cols_to_rows, grd, blk, 0, b->st, lat + k * g.plane + g.pitch, dst, 0, b->nx, g.ny, g.pitch, half_w(k));
+        }));
     return WT_OK;
 }
 

@@ -1,4 +1,4 @@
-"""GPU: the final sums of the sample reductions of batched sweeps (k_loads_batch, k_mex_batch, k_mex_ibb_batch) when a member holds more
+"""GPU: the final sums of the sample reductions of batched sweeps (k_loads_batch, k_mex_batch, k_mex_ibb_batch, k_mex_half_batch) when a member holds more
 than NT = 1024 column partials, so that the loop through LDS takes a second, partial trip: the carry of the running sums across
 trips, the count of the last trip, the re-use of the LDS array.  1100 x 24, the members of tests/_wide_cases.py: a plate whose
 window is 1062 columns wide, a block whose window is 22 columns wide in a grid sized by the plate, a member without a body.
@@ -6,6 +6,10 @@ window is 1062 columns wide, a block whose window is 22 columns wide in a grid s
 The references are those of the narrow tests, evaluated on the batch's own state (read_f / read_macro after every sampled call), and
 so are the tolerances, which are derived, not measured: Loads.mz_bound, Mex.fx_bound / fy_bound / mz_bound, MexIbb's with interpolated
 walls.  The surface sums add the same doubles in the same order on both sides: same bits.
+
+The three momentum-exchange kernels share one source text of that loop and are three code objects: each is taken past 1024 partials,
+the half batch's as tests/test_gpu_polar_half.py compares its samples (_mex_reference on the batch's own read_f, which is Load of the
+stored halves).
 """
 import functools
 
@@ -31,7 +35,7 @@ def _q(dtype):
     return q
 
 
-def _sequence(dtype, walls, swap, read=True):
+def _sequence(dtype, walls, swap, read=True, storage="native"):
     """CALLS sampled calls of EVERY steps from equilibrium; then, with `swap`, member 0's plate is replaced by a short block
     (set_masks keeps the flow); then one more sampled call.  After every call: the history so far is left to the end, the on-demand
     moment and momentum exchange and, with `read`, read_f and read_macro of every member."""
@@ -41,7 +45,7 @@ def _sequence(dtype, walls, swap, read=True):
     tau, u0 = [m[0] for m in wc.MEMBERS], [m[1] for m in wc.MEMBERS]
     xr, yr = wc.refs()
     out = {"f": [], "macro": [], "moment": [], "mex": [], "masks": [masks] * wc.CALLS}
-    with pkg.PolarEngine(wc.NX, wc.NY, B, dtype=dtype, history_cap=wc.CALLS + 1) as b:
+    with pkg.PolarEngine(wc.NX, wc.NY, B, dtype=dtype, history_cap=wc.CALLS + 1, storage=storage) as b:
         b.set_masks(masks)
         b.init_equilibrium(u0)
         if walls == "interpolated":
@@ -78,10 +82,7 @@ def _ratio(err, bound):
     return err / bound if bound > 0 else (0.0 if err == 0 else float("inf"))
 
 
-@pytest.mark.parametrize("walls", ["halfway", "interpolated"])
-@pytest.mark.parametrize("dtype", ["float32", "float64"])
-def test_sums_past_1024_partials_match_the_references(dtype, walls):
-    run = _swapped(dtype, walls)
+def _check_sums(run, dtype, walls):
     h = run["h"]
     B, rows = len(wc.MEMBERS), wc.CALLS + 1
     xr, yr = wc.refs()
@@ -127,6 +128,22 @@ def test_sums_past_1024_partials_match_the_references(dtype, walls):
     assert (run["surface"][0]["n_upper"][wc.NT:1080] == wc.CALLS).all()
 
 
+@pytest.mark.parametrize("walls", ["halfway", "interpolated"])
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_sums_past_1024_partials_match_the_references(dtype, walls):
+    _check_sums(_swapped(dtype, walls), dtype, walls)
+
+
+def test_half_storage_sums_past_1024_partials_match_the_references():
+    """k_mex_half_batch's own second trip: the same lattice, masks, swap and checks on a half batch, whose read_f is Load of the stored
+    halves, so that _mex_reference stands on the state the kernel summed."""
+    run = _sequence("float32", "halfway", True, storage="half")
+    assert run["f"][0][0].dtype == np.float32
+    _check_sums(run, "float32", "halfway")
+    native = _swapped("float32", "halfway")
+    assert not bits_equal(run["h"]["fx_mex"], native["h"]["fx_mex"])               # (the half model's state, not the fp32 one's)
+
+
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_the_short_member_is_untouched_and_runs_repeat(dtype):
     run = _swapped(dtype, "halfway")
@@ -142,3 +159,4 @@ def test_the_short_member_is_untouched_and_runs_repeat(dtype):
     for a, c in zip(again["mex"][-1], run["mex"][-1]):
         assert a.tobytes() == c.tobytes()
     assert int(plain["h"]["links"][-1, 0]) == 6410 and int(run["h"]["links"][-1, 0]) == 152
+
