@@ -147,7 +147,9 @@ class Canvas:
         self._cov = None
 
     def fill_polygon(self, cx, cy, colour) -> None:
-        """Even-odd scanline fill at pixel centres (the canvas default for a simple closed path)."""
+        """Even-odd scanline fill at pixel centres (the canvas default for a simple closed path).  Between two crossings a < b of a row the
+        pixels whose centre lies in the half-open interval [a, b) are filled, as rasterisers do and as the rows are chosen (an edge owns
+        the rows ya <= centre < yb); k_canvas_compose (csrc/canvas.hpp) counts the crossings at or left of the centre: the same rule."""
         cx, cy = np.asarray(cx, dtype=np.float64), np.asarray(cy, dtype=np.float64)
         x2, y2 = np.roll(cx, -1), np.roll(cy, -1)
         ya, yb = max(int(np.floor(cy.min())), 0), min(int(np.ceil(cy.max())), self.h - 1)
@@ -158,7 +160,7 @@ class Canvas:
                 continue
             xs = np.sort(cx[m] + (yc - cy[m]) / (y2[m] - cy[m]) * (x2[m] - cx[m]))
             for a, b in zip(xs[0::2], xs[1::2]):
-                i0, i1 = max(int(np.ceil(a - 0.5)), 0), min(int(np.floor(b - 0.5)), self.w - 1)
+                i0, i1 = max(int(np.ceil(a - 0.5)), 0), min(int(np.ceil(b - 0.5)) - 1, self.w - 1)      # a <= i + 0.5 < b
                 if i1 >= i0:
                     self.rgb[y, i0:i1 + 1] = colour
 
@@ -205,10 +207,15 @@ class TrailLayer:
         if len(seg) == 0:
             return
         # segments are a few pixels long: sample them densely and splat with a small round brush
-        rec = stroke_records(canvas, seg, t, y_half)
+        self.splat(stroke_records(canvas, seg, t, y_half))
+
+    def splat(self, rec: np.ndarray) -> None:
+        """Strokes the records [n][8] of stroke_records in their order, each over what the earlier ones left (what wt_canvas_stroke does
+        with the same array on the device)."""
+        rec = np.asarray(rec, dtype=np.float64).reshape(-1, 8)
         x0, y0, x1, y1, n, col = rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4].astype(int), rec[:, 5:8]
         r = 1.1 * self.s / 2.0 + 0.5
-        for i in range(len(seg)):
+        for i in range(len(rec)):
             ts = np.linspace(0.0, 1.0, int(n[i]))
             xs, ys = x0[i] + ts * (x1[i] - x0[i]), y0[i] + ts * (y1[i] - y0[i])
             xa, xb = int(np.floor(xs.min() - r)), int(np.ceil(xs.max() + r))
@@ -217,7 +224,10 @@ class TrailLayer:
             if xb < xa or yb < ya:
                 continue
             yy, xx = np.mgrid[ya:yb + 1, xa:xb + 1]
-            d = np.min(np.hypot(xx[..., None] + 0.5 - xs, yy[..., None] + 0.5 - ys), axis=-1)
+            # the nearest sample point, 64 points at a time: a long stroke's box x points would not fit in memory, and a minimum is exact
+            d = np.full(xx.shape, np.inf)
+            for k in range(0, len(ts), 64):
+                np.minimum(d, np.min(np.hypot(xx[..., None] + 0.5 - xs[k:k + 64], yy[..., None] + 0.5 - ys[k:k + 64]), axis=-1), out=d)
             a = np.clip(r - d, 0.0, 1.0) * 0.75
             self.rgb[ya:yb + 1, xa:xb + 1] = self.rgb[ya:yb + 1, xa:xb + 1] * (1 - a[..., None]) + col[i] * a[..., None]
             self.a[ya:yb + 1, xa:xb + 1] = self.a[ya:yb + 1, xa:xb + 1] * (1 - a) + a

@@ -124,7 +124,10 @@ __global__ __launch_bounds__(256) void k_canvas_compose(const T *__restrict__ ma
         const double4 v = a.layer[(long)y * d.w + x];
         c[0] = c[0] * (1.0 - v.w) + v.x; c[1] = c[1] * (1.0 - v.w) + v.y; c[2] = c[2] * (1.0 - v.w) + v.z;
     }
-    // ---- drawFoil, html:815-828: even-odd fill at the pixel centre, then the outline (one path: the segments' coverages max-combine)
+    // ---- drawFoil, html:815-828: even-odd fill at the pixel centre, then the outline (one path: the segments' coverages max-combine).
+    // Fill rule: an edge owns the rows ay <= centre < by, and a crossing counts when it lies at or left of the centre, so between two crossings
+    // a < b the centres in the half-open [a, b) are filled (compose.Canvas.fill_polygon: i0 = ceil(a - 0.5), i1 = ceil(b - 0.5) - 1).
+    // Fewer than 3 points draw no foil, neither fill nor outline.
     const double pxc = (double)x + 0.5, pyc = (double)y + 0.5;
     if (a.npoly >= 3 && pxc >= a.pbx0 - a.foil_r - 1.0 && pxc <= a.pbx1 + a.foil_r + 1.0 && pyc >= a.pby0 - a.foil_r - 1.0 && pyc <= a.pby1 + a.foil_r + 1.0) {
         bool in = false;

@@ -325,8 +325,13 @@ WT_API int wt_advect_tracers(wt_handle *h, int n, const double *x, const double 
  * wt_canvas_compose: one frame — background, the field image of wt_render_rgba resampled into the plot rectangle (drawImage, html:923),
  *   the particle layer when use_trails != 0, the foil polygon poly_xy[npoly][2] (canvas pixels) filled (#0d1018) and outlined (html:815-828),
  *   the colour bar bar_rgb[308*scale][3] (html:830-848) and the labels: text_alpha[360*scale][680*scale] = alpha of the white text at every
- *   pixel (0 = none), or NULL to keep the map of the previous call (it changes with the angle and the field only).  mode .. vort_scale as
- *   in wt_render_rgba.  rgba_out: [360*scale][680*scale][4]. */
+ *   pixel (0 = none), or NULL for the previous map: the one the last call with a map left on this canvas, or no text at all when the
+ *   canvas has had none since it was (re-)allocated at this scale (wt_get_option "canvas_text_set").  mode .. vort_scale as in
+ *   wt_render_rgba.  rgba_out: [360*scale][680*scale][4].
+ *   The foil: npoly < 3 draws none, neither fill nor outline (npoly <= 4096).  The fill is even-odd at pixel centres under the half-open
+ *   rule of rasterisers: an edge owns the rows ya <= centre < yb, and between two crossings a < b of a row the pixels with a <= centre < b
+ *   are filled — a centre exactly on a left crossing is inside, one exactly on a right crossing is outside (compose.Canvas.fill_polygon
+ *   fills by the same rule). */
 WT_API int wt_canvas_stroke(wt_handle *h, int scale, int fade, int n, const double *seg);
 WT_API int wt_canvas_compose(wt_handle *h, int scale, int mode, double u0, double max_s, double cp_min, double cp_max, double vort_scale,
                              const double *poly_xy, int npoly, const uint8_t *bar_rgb, const float *text_alpha, int use_trails,
