@@ -333,8 +333,11 @@ __device__ __forceinline__ void collide(const T (&fin)[9], T tau, T (&fo)[9], T 
     uy = v;
 }
 
-// The collision a step kernel runs in an interior fluid cell: plain BGK (collide) or BGK with a Smagorinsky eddy viscosity (collide_les).
-enum : int { COLLIDE_BGK = 0, COLLIDE_LES = 1 };
+// The collision a step kernel runs in an interior fluid cell: plain BGK (collide), BGK with a Smagorinsky eddy viscosity (collide_les),
+// or the two-relaxation-time collision without and with that eddy viscosity (collide_trt).
+enum : int { COLLIDE_BGK = 0, COLLIDE_LES = 1, COLLIDE_TRT = 2, COLLIDE_TRT_LES = 3 };
+__host__ __device__ constexpr bool coll_is_trt(int coll) { return coll == COLLIDE_TRT || coll == COLLIDE_TRT_LES; }
+__host__ __device__ constexpr bool coll_has_les(int coll) { return coll == COLLIDE_LES || coll == COLLIDE_TRT_LES; }
 
 // BGK with a Smagorinsky subgrid viscosity (Hou et al. 1996; include/wt_polar.h "Smagorinsky subgrid viscosity"): operation for operation
 // collide<T> up to the equilibrium; then the relaxation time of THIS site grows with the norm of its non-equilibrium stress:
@@ -368,6 +371,57 @@ __device__ __forceinline__ void collide_les(const T (&fin)[9], T tau, T c, T (&f
     const T te = T(0.5) * (tau + wt_sqrt<T>(tau * tau + (c * q) / r));
 #pragma unroll
     for (int k = 0; k < 9; k++) fo[k] = fin[k] - n[k] / te;
+    rho = r;
+    ux = u;
+    uy = v;
+}
+
+// The two-relaxation-time collision (Ginzburg, Verhaeghe and d'Humieres 2008; include/wt_polar.h "Two-relaxation-time collision"):
+// operation for operation collide<T> up to the equilibrium; then every pair k, o = opp(k) of non-equilibrium parts is split into its
+// symmetric half-sum, relaxed with tp, and its antisymmetric half-difference, relaxed with tm, where (tp - 0.5)(tm - 0.5) = lam, the
+// member's magic number:
+//   n[k] = fin[k] - eq[k];  tp = tau, or te of collide_les from these n[k] (LES);  tm = 0.5 + lam / (tp - 0.5)
+//   fo[0] = fin[0] - n[0] / tp
+//   s = 0.5 (n[k] + n[o]);  a = 0.5 (n[k] - n[o]);  ds = s / tp;  da = a / tm;  fo[k] = (fin[k] - ds) - da;  fo[o] = (fin[o] - ds) + da
+// for (k, o) = (1, 3), (2, 4), (5, 7), (6, 8), in the arithmetic contract of this file (left to right as written, one rounding per
+// operation, IEEE division and square root).  Nine divisions of populations per site, as collide<T>, and one for tm.  With c = 0,
+// te == tau exactly, so LES at c = 0 gives the bits of the plain form.  tau <= 0.5 is the caller's to refuse (wtp_step does).
+template <typename T, bool LES>
+__device__ __forceinline__ void collide_trt(const T (&fin)[9], T tau, T lam, T c, T (&fo)[9], T &rho, T &ux, T &uy)
+{
+    T r, u, v;
+    moments(fin, r, u, v);
+    const T uMax = T(0.35), rhoMin = T(0.5), rhoMax = T(2.0);   // html:344
+    r = (r < rhoMin) ? rhoMin : r;
+    r = (rhoMax < r) ? rhoMax : r;
+    const T spd2 = u * u + v * v;
+    if (spd2 > uMax * uMax) {
+        const T k = uMax / wt_sqrt<T>(spd2);
+        u *= k;
+        v *= k;
+    }
+    T n[9];
+    feq_all(r, u, v, n);
+#pragma unroll
+    for (int k = 0; k < 9; k++) n[k] = fin[k] - n[k];
+    T tp = tau;
+    if constexpr (LES) {
+        const T pxx = n[1] + n[3] + n[5] + n[6] + n[7] + n[8];
+        const T pyy = n[2] + n[4] + n[5] + n[6] + n[7] + n[8];
+        const T pxy = n[5] - n[6] + n[7] - n[8];
+        const T q = wt_sqrt<T>((pxx * pxx + T(2.0) * (pxy * pxy)) + pyy * pyy);
+        tp = T(0.5) * (tau + wt_sqrt<T>(tau * tau + (c * q) / r));
+    }
+    const T tm = T(0.5) + lam / (tp - T(0.5));
+    fo[0] = fin[0] - n[0] / tp;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const int k = p < 2 ? p + 1 : p + 3, o = opp_of(k);      // (1, 3), (2, 4), (5, 7), (6, 8)
+        const T s = T(0.5) * (n[k] + n[o]), a = T(0.5) * (n[k] - n[o]);
+        const T ds = s / tp, da = a / tm;
+        fo[k] = (fin[k] - ds) - da;
+        fo[o] = (fin[o] - ds) + da;
+    }
     rho = r;
     ux = u;
     uy = v;

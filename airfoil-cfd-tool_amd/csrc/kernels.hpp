@@ -35,7 +35,8 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // lane.  Correct for any site; used by the tiles that touch the body surface and by ragged
 // tiles.  (A 4-sites-per-lane vector form of this path was measured SLOWER on the 4096^2
 // body case, 213 vs 207 us per step: its 111 VGPRs cost the whole kernel two waves per SIMD.)
-// COLL selects the collision of the interior branch: COLLIDE_BGK, or COLLIDE_LES with the member's constant `cles` (collide_les).
+// COLL selects the collision of the interior branch: COLLIDE_BGK, COLLIDE_LES with the member's constant `cles` (collide_les), or
+// COLLIDE_TRT / COLLIDE_TRT_LES with the member's magic number `lam` (collide_trt).
 // WALL selects what the interior branch does with a population whose source cell is solid: WALL_HALFWAY, or WALL_INTERP with the wall
 // distances `wq` (wall_incoming, d2q9.hpp): eight planes laid out like population planes 1..8, plane k - 1 holding q of direction k
 // at the link's fluid cell; `wq` points at column 0 of plane 0, as `s` does.  q is read only on lanes whose source cell is solid.
@@ -47,7 +48,8 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR = FAR_AXIAL, typename S = T>
 __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
-                                             T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr, T V0 = T(0.0))
+                                             T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr, T V0 = T(0.0),
+                                             T lam = T(0.0))
 {
     const long c = (long)i * g.pitch + j;
     const int gi = i + g.gi0;
@@ -96,7 +98,8 @@ __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restr
                 }
             }
         }
-        if constexpr (COLL == COLLIDE_LES) collide_les<T>(fin, tau, cles, out, rho, ux, uy);
+        if constexpr (coll_is_trt(COLL)) collide_trt<T, COLL == COLLIDE_TRT_LES>(fin, tau, lam, cles, out, rho, ux, uy);
+        else if constexpr (COLL == COLLIDE_LES) collide_les<T>(fin, tau, cles, out, rho, ux, uy);
         else collide(fin, tau, out, rho, ux, uy);
     }
 #pragma unroll

@@ -47,6 +47,13 @@
 // stale until a step has emitted and zeroes the member's running sums; with wtp_set_step_count a sweep continues where another stopped.
 // A batch that never writes launches the kernels it always launched.
 //
+// The two-relaxation-time collision (wtp_enable_trt) is a third collision: while it is on, wtp_step launches k_step_trt_batch (in a half
+// batch k_step_trt_half_batch), the same step_tile (site_general) with collide_trt in its interior cells and one more value per member,
+// the magic number, without or with the Smagorinsky eddy viscosity, with either wall rule and either storage.  Its kernels always take
+// the inclined far field, with an array of zeros as the cross-flow while wtp_enable_wind is off.  While it is on, wtp_step refuses a
+// tau that is not above 0.5 in the batch's dtype.  A batch that has it off launches the kernels it always launched, with the arguments
+// they always had.
+//
 // Every variant above is a kernel of its own name and code object, so that a batch runs the one its switches select and no other.
 // What the variants share is source text: one site (site_general, kernels.hpp, for every storage), one momentum-exchange body
 // (mex_member, with a link rule per wall rule), one prologue of the tiled step kernels (MemberTile), one stepping loop on the host.
@@ -149,6 +156,10 @@ struct wtp_batch {
     bool wind = false;
     void *wind_v = nullptr;              // [B] of T: the cross-flow V0 of every member
     std::vector<double> wind_host;       // ... as the caller gave them (doubles), for wtp_init_equilibrium
+    // two-relaxation-time collision (wtp_enable_trt); the pointers are null until then
+    bool trt = false;
+    void *trt_lam = nullptr;             // [B] of T: the magic number of every member
+    void *zero_v = nullptr;              // [B] of T, all zero: the cross-flow its kernels read while the free stream is axial
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -292,6 +303,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wind_waves<
                                                                   c, q, V0);
 }
 
+// The same step with the two-relaxation-time collision (collide_trt, d2q9.hpp; include/wt_polar.h "Two-relaxation-time collision") in
+// every member's interior fluid cells, without (COLLIDE_TRT) or with (COLLIDE_TRT_LES) the Smagorinsky eddy viscosity, and with either
+// wall rule: k_step_wind_batch's grid, walk and arguments, and lam[m], the member's magic number, behind vwind.  The far field is always
+// the inclined one: a batch without wtp_enable_wind hands an array of zeros as vwind, and V0 = 0 gives the axial far field's bits (see
+// k_step_wind_batch), so that the collision costs eight instantiations per dtype and not sixteen.  cles is read only for
+// COLLIDE_TRT_LES and wq only for WALL_INTERP.  A kernel of its own name, so that a batch with the model off runs the code object it
+// always ran.
+// Waves per SIMD, from the compiler's resource report as for wind_waves (profiles/polar_trt_isa.txt): asked for wind_waves' occupancy
+// the emitting and the Smagorinsky kernels allocate 84 to 92 VGPRs in fp32 (5 waves) and 108 to 122 in fp64 (4 waves) without scratch,
+// but the plain non-emitting fp32 kernels, asked for 6 waves, get 80 VGPRs and 12 to 16 bytes of scratch per lane: the split keeps
+// n[k], the half-sums and the half-differences alive together.  So every fp32 kernel asks for 5 waves.
+template <typename T>
+constexpr int trt_waves() { return sizeof(T) == 8 ? 4 : 5; }
+
+template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(trt_waves<T>()))) void k_step_trt_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
+                                                         const T *__restrict__ vwind, const T *__restrict__ lam, int rev)
+{
+    static_assert(coll_is_trt(COLL), "COLLIDE_TRT or COLLIDE_TRT_LES");
+    const int lane = threadIdx.x & 63;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
+    const T tau = params[2 * m], U0 = params[2 * m + 1], V0 = vwind[m], magic = lam[m];
+    T c = T(0.0);
+    if constexpr (COLL == COLLIDE_TRT_LES) c = cles[m];
+    const T *q = nullptr;
+    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
+    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
+                                                                  c, q, V0, magic);
+}
+
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
 // the nine values of wind_init and (1, u0, v0) in the macroscopic planes.
 template <typename T>
@@ -368,6 +415,39 @@ __global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restric
     for (int v = 0; v < 4; v++) {
         const int j = j0 + v * 64 + lane;
         if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0);
+    }
+}
+
+// One step of every member of a half batch with the two-relaxation-time collision: k_step_half_batch's grid, walk and arguments, and
+// lam[m], the member's magic number, behind vwind.  COLL is COLLIDE_TRT or COLLIDE_TRT_LES (cles is read only for the latter); the far
+// field is always the inclined one, with an array of zeros as vwind in a batch without wtp_enable_wind (see k_step_trt_batch).  Load
+// comes in front of the site's branches and Store behind them, as for the other collisions.
+template <bool EMIT, int COLL>
+__global__ __launch_bounds__(256) void k_step_trt_half_batch(const half_t *__restrict__ fs, half_t *__restrict__ fd, float *__restrict__ macro,
+                                                             const uint8_t *__restrict__ mask, Geom g, MemberStrides ms,
+                                                             const float *__restrict__ params, const float *__restrict__ cles,
+                                                             const float *__restrict__ vwind, const float *__restrict__ lam, int rev)
+{
+    static_assert(coll_is_trt(COLL), "COLLIDE_TRT or COLLIDE_TRT_LES");
+    const int runs = (int)(g.pitch / 256);                          // runs of 256 rows in a column
+    const long nruns = (long)g.nxl * runs;
+    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nruns) return;
+    const long t = rev ? nruns - 1 - q : q;
+    const int i = (int)(t / runs), j0 = (int)(t % runs) * 256;
+    const long mb = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
+    const float tau = params[2 * mb], U0 = params[2 * mb + 1], V0 = vwind[mb], magic = lam[mb];
+    float c_les = 0.0f;
+    if constexpr (COLL == COLLIDE_TRT_LES) c_les = cles[mb];
+    const half_t *s = fs + mb * ms.lat + g.pitch;
+    half_t *d = fd + mb * ms.lat + g.pitch;
+    const uint8_t *m = mask + mb * ms.mask + g.pitch;
+    float *mm = macro + mb * ms.macro;
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (int v = 0; v < 4; v++) {
+        const int j = j0 + v * 64 + lane;
+        if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR_INCLINED>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0, magic);
     }
 }
 
@@ -787,7 +867,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -876,7 +956,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1183,6 +1263,22 @@ static auto half_kernel(bool emit)
     return emit ? k_step_half_batch<true, COLL, FAR> : k_step_half_batch<false, COLL, FAR>;
 }
 
+// k_step_trt_batch of one collision and one wall rule, and k_step_trt_half_batch of one collision, emitting or not.
+template <typename T, int COLL, int WALL>
+static auto trt_kernel(bool emit)
+{
+    return emit ? k_step_trt_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_trt_batch<T, false, WT_LOADMODE, COLL, WALL>;
+}
+
+template <int COLL>
+static auto trt_half_kernel(bool emit)
+{
+    return emit ? k_step_trt_half_batch<true, COLL> : k_step_trt_half_batch<false, COLL>;
+}
+
+// The cross-flow array of the two-relaxation-time kernels: the members' V0, or zeros while the free stream is axial.
+static const void *trt_cross_flow(const wtp_batch *b) { return b->wind ? b->wind_v : b->zero_v; }
+
 // The stepping loop of wtp_step: which steps sample and which emit, the flip of the lattices, the step count and the history rows.
 // `launch(emit, rev)` enqueues one step of every member from the current lattice into the other; T is the type of the read-outs.
 template <typename T, typename Launch>
@@ -1209,6 +1305,13 @@ static int step_half(wtp_batch *b, int nsteps, int sample_every)
 {
     const dim3 grid(half_step_blocks(b->g), (unsigned)b->members), block(256);
     return step_loop<float>(b, nsteps, sample_every, [&](bool emit, int rev) {
+        if (b->trt) {
+            const auto k_trt = b->les ? trt_half_kernel<COLLIDE_TRT_LES>(emit) : trt_half_kernel<COLLIDE_TRT>(emit);
+            hipLaunchKernelGGL(k_trt, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
+                               macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
+                               (const float *)trt_cross_flow(b), (const float *)b->trt_lam, rev);
+            return;
+        }
         const auto k_step = b->wind ? (b->les ? half_kernel<COLLIDE_LES, FAR_INCLINED>(emit) : half_kernel<COLLIDE_BGK, FAR_INCLINED>(emit))
                                     : (b->les ? half_kernel<COLLIDE_LES, FAR_AXIAL>(emit) : half_kernel<COLLIDE_BGK, FAR_AXIAL>(emit));
         hipLaunchKernelGGL(k_step, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
@@ -1226,7 +1329,13 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
     return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
-        if (b->wind) {
+        if (b->trt) {
+            const auto k_step = b->ibb ? (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_INTERP>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_INTERP>(emit))
+                                       : (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_HALFWAY>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_HALFWAY>(emit));
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
+                               (const T *)trt_cross_flow(b), (const T *)b->trt_lam, rev);
+        } else if (b->wind) {
             const auto k_step = b->ibb ? (b->les ? wind_kernel<T, COLLIDE_LES, WALL_INTERP>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_INTERP>(emit))
                                        : (b->les ? wind_kernel<T, COLLIDE_LES, WALL_HALFWAY>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_HALFWAY>(emit));
             hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
@@ -1259,6 +1368,10 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
         if (!(tau[m] > 0.0) || !std::isfinite(tau[m])) return fail(WT_ERR_ARG, "tau[%d] must be positive and finite", m);
         if (!std::isfinite(u0[m])) return fail(WT_ERR_ARG, "u0[%d] must be finite", m);
     }
+    if (b->trt)                                  // tm = 0.5 + lam / (tp - 0.5) needs tp > 0.5 in the batch's dtype
+        for (int m = 0; m < b->members; m++)
+            if (!(b->dtype == WT_F32 ? (float)tau[m] > 0.5f : tau[m] > 0.5))
+                return fail(WT_ERR_ARG, "tau[%d] must be above 0.5 in the batch's dtype while the two-relaxation-time collision is on", m);
     WT_TRY(check_ready(b));
     if (sample_every > 0) {
         const long long samples = (b->steps_done + nsteps) / sample_every - b->steps_done / sample_every;
@@ -1304,6 +1417,26 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
     const auto c = [&](size_t m) { return 18.0 * std::sqrt(2.0) * cs[m] * cs[m]; };      // c = 18 sqrt(2) Cs^2: formed left to right in double
     WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->les_c, c) : upload_per_member<double>(b, &b->les_c, c));
     b->les = true;
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// two-relaxation-time collision
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_trt(wtp_batch *b, const double *magic)
+{
+    WT_TRY(check_batch(b));
+    if (!magic) { b->trt = false; return WT_OK; }        // (steps already enqueued were launched with the model on: stream order)
+    for (int m = 0; m < b->members; m++)
+        if (!std::isfinite(magic[m]) || !(magic[m] > 0.0) || magic[m] > 1.0) return fail(WT_ERR_ARG, "magic[%d] must be finite and in (0, 1]", m);
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->zero_v) {
+        HIP_TRY(hipMalloc(&b->zero_v, (size_t)b->members * b->esz));
+        HIP_TRY(hipMemsetAsync(b->zero_v, 0, (size_t)b->members * b->esz, b->st));      // (+0 in either dtype)
+    }
+    const auto lam = [&](size_t m) { return magic[m]; };
+    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->trt_lam, lam) : upload_per_member<double>(b, &b->trt_lam, lam));
+    b->trt = true;
     return WT_OK;
 }
 

@@ -154,7 +154,8 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // by reading what the previous step wrote last — still resident in the 256 MB Infinity Cache.
 // WIN: the tile belongs to a grid whose tiles start every `stride` rows (tile height stays 64*N) and
 // only rows in [st_lo, st_hi) are stored — the window-aligned zone passes of step_fused.hpp.
-// COLL: the collision of interior fluid cells, COLLIDE_BGK or COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp).
+// COLL: the collision of interior fluid cells, COLLIDE_BGK, COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp), or COLLIDE_TRT /
+// COLLIDE_TRT_LES with the magic number `lam` (collide_trt); the two-relaxation-time kernels always come with FAR_INCLINED.
 // WALL: the wall rule of interior fluid cells, WALL_HALFWAY or WALL_INTERP with the wall distances `wq`, eight planes laid out like
 // population planes 1..8, pad column included (wall_incoming, d2q9.hpp).  Only TILE_GENERAL tiles can own a link: no other path reads them.
 // FAR: what a far-field cell holds, FAR_AXIAL (feq(1, U0, 0)) or FAR_INCLINED with the cross-flow `V0` (feq(1, U0, V0)); the three places
@@ -164,12 +165,13 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
                                           int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr,
-                                          T V0 = T(0.0))
+                                          T V0 = T(0.0), T lam = T(0.0))
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
     constexpr bool NT = (LOADMODE & 1) != 0;
     constexpr bool UNALIGNED = (LOADMODE & 2) != 0;
+    static_assert(!coll_is_trt(COLL) || FAR == FAR_INCLINED, "the two-relaxation-time kernels take the inclined far field");
     const int i = i_begin + (int)(tile_local / tiles_per_col);
     const int jt = (int)(tile_local % tiles_per_col);
     const int row0 = WIN ? jt * stride : jt * TJ;
@@ -186,7 +188,7 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             const int j = row0 + v * 64 + lane;
             if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) {
                 if constexpr (FAR == FAR_INCLINED)
-                    site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0);
+                    site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0, lam);
                 else if constexpr (WALL == WALL_INTERP) site_general<T, COLL, WALL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch);
                 else site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
             }
@@ -228,7 +230,8 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             T a[9], o[9], rho, ux, uy;
 #pragma unroll
             for (int k = 0; k < 9; k++) a[k] = fin[k].v[v];
-            if constexpr (COLL == COLLIDE_LES) collide_les<T>(a, tau, cles, o, rho, ux, uy);
+            if constexpr (coll_is_trt(COLL)) collide_trt<T, COLL == COLLIDE_TRT_LES>(a, tau, lam, cles, o, rho, ux, uy);
+            else if constexpr (COLL == COLLIDE_LES) collide_les<T>(a, tau, cles, o, rho, ux, uy);
             else collide<T>(a, tau, o, rho, ux, uy);
             const int j = j0 + v;
             const bool far = (j == 0) || (j == g.ny - 1);   // top / bottom rows

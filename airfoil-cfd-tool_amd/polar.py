@@ -20,6 +20,8 @@ population storage (``PolarEngine(storage="half")``, ``run_polar(storage="half")
 binary16 deviation from its lattice weight and computes in fp32: half the bytes per step and per batch, at a small bias of CL and CD.
 A sweep can be continued without a second warm-up: ``PolarEngine.state`` / ``restore`` (``write_f``, ``write_stored``,
 ``set_step_count``) and ``run_polar(keep_state=True)`` followed by ``run_polar(start=result.state)``.
+With the two-relaxation-time collision (``PolarEngine.enable_trt``, ``run_polar(collision="trt")``) the effective position of a
+half-way wall is set by a magic number and not by tau, so a body keeps its thickness when the Reynolds number of a sweep changes.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -54,11 +56,14 @@ EXPORTS = (
     "wtp_enable_wind",
     "wtp_create_stored", "wtp_read_stored",
     "wtp_write_f", "wtp_write_stored", "wtp_step_count", "wtp_set_step_count",
+    "wtp_enable_trt",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
 WALLS = ("staircase", "interpolated")                              # run_polar's wall rules
 STORAGES = ("native", "half")                                      # how a batch stores its populations: in its dtype, or as binary16 deviations from the weights
+COLLISIONS = ("bgk", "trt")                                        # run_polar's collisions: single relaxation time, or two with a magic number
+MAGIC_DEFAULT = 3 / 16                                             # the magic number at which a half-way wall of a Poiseuille flow sits half-way at every tau
 FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
 WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
@@ -66,8 +71,10 @@ MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_su
 _lib = None
 
 
-def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
-    """Load libwtpolar.so, importing torch first when it is importable (one HIP runtime per process, as _capi.load_library)."""
+def load_polar_library(path: str = POLAR_LIB_PATH, optional: Sequence[str] = ()) -> ctypes.CDLL:
+    """Load libwtpolar.so, importing torch first when it is importable (one HIP runtime per process, as _capi.load_library).
+    `optional`: entry points that an older build given as `path` may lack (tools/polar_bench.py --lib, to time a parent commit's
+    library); every other one of EXPORTS is required, and so are these in the package's own library."""
     global _lib
     if _lib is not None:
         return _lib
@@ -114,8 +121,11 @@ def load_polar_library(path: str = POLAR_LIB_PATH) -> ctypes.CDLL:
         "wtp_write_stored": ([B, c_int, c_void_p], c_int),
         "wtp_step_count": ([B, ip], c_int),
         "wtp_set_step_count": ([B, c_int64], c_int),
+        "wtp_enable_trt": ([B, dp], c_int),
     }
     for name, (argtypes, restype) in sig.items():
+        if name in optional and path != POLAR_LIB_PATH and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
@@ -189,6 +199,7 @@ class PolarEngine:
         self.les_enabled = False
         self.interpolated_walls = False
         self._wind = False
+        self._trt = False
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         if storage == "half":
             _check(self._lib.wtp_create_stored(self.nx, self.ny, code, WTP_STORE_HALF, self.members, self.history_cap, int(device),
@@ -364,6 +375,25 @@ class PolarEngine:
     def wind_enabled(self) -> bool:
         return self._wind
 
+    def enable_trt(self, magic) -> None:
+        """Collide with two relaxation times from the next step on (wt_polar.h "Two-relaxation-time collision"): magic is the
+        magic number (tau+ - 1/2)(tau- - 1/2), one value or [B], each finite with 0 < magic <= 1; 3/16 puts a half-way wall
+        half-way at every tau, 1/4 is the most stable.  None switches the model off again: the following steps are those of a batch
+        that never enabled it.  While it is on, step raises WTError (WT_ERR_ARG) for a tau that is not above 0.5 in the batch's
+        dtype.  The flow state, the history, every running sum and every other enable_* setting are kept; combines with enable_les,
+        enable_interpolated_walls, enable_wind and storage="half", independent of the read-outs."""
+        if magic is None:
+            _check(self._lib.wtp_enable_trt(self._b, None))
+            self._trt = False
+            return
+        v = _f64(magic, self.members)
+        _check(self._lib.wtp_enable_trt(self._b, _dp(v)))
+        self._trt = True
+
+    @property
+    def trt_enabled(self) -> bool:
+        return self._trt
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -511,12 +541,17 @@ class PolarResult:
     storage: InitVar[str] = "native"
     # PolarEngine.state() after the last sample of a run_polar(keep_state=True), to continue from (run_polar(start=)); else None.  Init-only too.
     state: InitVar[Optional[Dict[str, object]]] = None
+    # The collision of the sweep, "bgk" or "trt", and the magic number of a "trt" sweep (None for "bgk").  Init-only too.
+    collision: InitVar[str] = "bgk"
+    magic: InitVar[Optional[float]] = None
 
-    def __post_init__(self, walls, frame, storage, state):
+    def __post_init__(self, walls, frame, storage, state, collision, magic):
         self.walls = walls
         self.frame = frame
         self.storage = storage
         self.state = state
+        self.collision = collision
+        self.magic = magic
 
 
 def raw_coefficients(fx, fy, surf, rev, u0: float, nx: int):
@@ -637,6 +672,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
               total_forces: bool = False, mean_fields: bool = False, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
+              collision: str = "bgk", magic: float = MAGIC_DEFAULT,
               storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
@@ -681,7 +717,14 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     populations again.  The running sums (surface pressure, mean fields) start empty: they cover this call's samples only, and
     so do the statistics of the points.  Continuing with other angles, another body or other settings than the state was
     taken with is the caller's decision: nothing checks it, and the flow then needs its own time to adjust.  A `start` whose
-    nx, ny, dtype, storage or number of angles is not this call's raises ValueError before an engine is created."""
+    nx, ny, dtype, storage or number of angles is not this call's raises ValueError before an engine is created.
+    `collision`: "bgk", the default, is the single-relaxation-time collision, with the code path and the bits it always had.  "trt"
+    is the two-relaxation-time collision with the magic number `magic` (default 3/16; finite, in (0, 1]) in every member, from the
+    first warm-up step on (PolarEngine.enable_trt): the effective position of a staircase wall then no longer moves with tau, that
+    is with `re`.  It needs a tau above 0.5 in `dtype` and combines with `les`, `walls`, `frame`, `storage` and `start`.  What it
+    does to CL and CD was measured, not assumed: README, profiles/polar_trt_sweep.txt.  PolarResult.collision and .magic say what ran
+    (magic is None for "bgk").  An unknown collision, a magic outside (0, 1] or "trt" with such a tau raises ValueError before an
+    engine is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -698,11 +741,20 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     if frame not in FRAMES:
         raise ValueError(f"frame must be one of {FRAMES}, got {frame!r}")
     _check_storage(storage, dtype, walls)
+    if not isinstance(collision, str) or collision not in COLLISIONS:
+        raise ValueError(f"collision must be one of {COLLISIONS}, got {collision!r}")
+    trt = collision == "trt"
+    if trt:
+        magic = float(magic)
+        if not math.isfinite(magic) or not 0.0 < magic <= 1.0:
+            raise ValueError(f"magic must be a finite magic number in (0, 1], got {magic!r}")
     wind = frame == "wind"
     if wind and any(not abs(a) <= WIND_ALPHA_MAX for a in alphas):
         raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
     nx, ny, u0 = int(nx), int(ny), float(u0)
     tau = float(tau) if tau is not None else (tau_from_reynolds(re, u0, nx) if re is not None else TAU_DEFAULT)
+    if trt and not _np_dtype(dtype).type(tau) > 0.5:
+        raise ValueError(f'collision="trt" needs tau above 0.5 in {_np_dtype(dtype).name}, got {tau!r}')
     if start is not None:
         _check_state(start, nx, ny, dtype, storage, len(alphas))
     if warmup_steps is None:
@@ -735,6 +787,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_mean_fields()
         if les is not None:
             eng.enable_les(les)
+        if trt:
+            eng.enable_trt(magic)
         if start is not None:
             eng.restore(start)
         if warmup_steps:
@@ -757,7 +811,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     for p, mean in zip(points, means):
         p.mean = mean
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
-                       walls=walls, frame=frame, storage=storage, state=state)
+                       walls=walls, frame=frame, storage=storage, state=state, collision=collision, magic=magic if trt else None)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

@@ -322,6 +322,47 @@ WTP_API int wtp_write_f(wtp_batch *b, int member, const void *f_in);
 WTP_API int wtp_write_stored(wtp_batch *b, int member, const uint16_t *h);
 WTP_API int wtp_step_count(wtp_batch *b, int64_t *steps);
 WTP_API int wtp_set_step_count(wtp_batch *b, int64_t steps);
+/*
+ * Two-relaxation-time collision (TRT; Ginzburg, Verhaeghe and d'Humieres 2008): with the single relaxation time of BGK a half-way
+ * bounce-back wall sits where tau puts it, its offset growing with (tau - 1/2)^2, so a body's effective thickness changes with the
+ * Reynolds number of a sweep.  TRT splits every pair of populations k, opp(k) into a symmetric part, relaxed with tau+ = tau (which
+ * sets the viscosity), and an antisymmetric part, relaxed with tau-, chosen so that the "magic" number
+ * Lambda = (tau+ - 1/2)(tau- - 1/2) is the same at every tau.  With Lambda = 3/16 the half-way wall of a Poiseuille flow sits exactly
+ * half-way for every tau; with Lambda = 1/4 the scheme is at its most stable.  It is another collision, per member and opt-in.
+ * Definition, for an interior fluid cell only.  Untouched are: solid cells, the inlet column, the top and bottom rows and the outlet
+ * column; the gather and either wall rule; the moments and the stability net; the stored (rho, ux, uy), which stay the clamped
+ * pre-collision moments.  Let fin[0..8], rho, ux, uy and eq[k] = feq_k(rho, ux, uy) be exactly as in the BGK step; T is the batch's
+ * dtype and lam the member's magic number rounded once to T.  Every operation rounds once in T, evaluation is left to right as
+ * written with no contraction, division and square root are IEEE:
+ *     n[k] = fin[k] - eq[k]                                   k = 0..8
+ *     tp   = tau                                              (model without Smagorinsky)
+ *     tp   = te of the Smagorinsky section, from these n[k]   (with wtp_enable_les on: pxx, pyy, pxy, q, te as written there)
+ *     tm   = 0.5 + lam / (tp - 0.5)
+ *     fo[0] = fin[0] - n[0] / tp
+ *     for (k, o) in (1,3), (2,4), (5,7), (6,8):               o = opp(k)
+ *         s  = 0.5 * (n[k] + n[o]);   a  = 0.5 * (n[k] - n[o])
+ *         ds = s / tp;                da = a / tm
+ *         fo[k] = (fin[k] - ds) - da
+ *         fo[o] = (fin[o] - ds) + da
+ * Consequences.  Mass and momentum are conserved as in BGK: the symmetric parts carry the mass, the antisymmetric ones the momentum,
+ * and both sums of n vanish up to rounding.  The viscosity is nu = (tau - 1/2)/3 as before.  With cs = 0 in every member te == tau
+ * exactly, so TRT with the Smagorinsky model on at cs = 0 has the bits of TRT alone.  With lam = (tau - 1/2)^2, tm equals tp as a
+ * number and the result equals BGK's as a number, not bit for bit, because the split rounds differently: at tau = 0.75 and
+ * lam = 1/16, where tm == tp exactly in both dtypes, the largest difference after one step from a rough state was 0.125 eps(T) on the
+ * CPU reference; the bound is eps(T), at most four roundings differing by half an ulp of a value below 1/2 each.  A TRT member has
+ * no libwindtunnel twin.
+ *
+ * wtp_enable_trt switches the model on.  magic: [B], each finite with 0 < magic <= 1, else WT_ERR_ARG before any device call (and the
+ * batch is left as it was).  magic == NULL switches it off again: the following steps launch the kernels, and compute the bits, of a
+ * batch that never enabled it.  Either takes effect from the next wtp_step.  The flow state, the step count, the history, every
+ * running sum and every other wtp_enable_* setting are kept.  While the model is on, wtp_step fails with WT_ERR_ARG before anything
+ * is enqueued if any (T)tau[m] is not greater than 0.5 (tm would not be defined); the step count and the history are unchanged by
+ * such a call.  With the model off wtp_step accepts what it always accepted.  It combines with wtp_enable_les, wtp_enable_ibb and
+ * wtp_enable_wind, with WTP_STORE_HALF (Load in front, Store behind, as for the other collisions) and with wtp_write_f and
+ * wtp_write_stored, and is independent of the read-outs: the momentum exchange reads post-collision populations, whichever collision
+ * wrote them.  A batch that never calls it launches the kernels it always launched.
+ */
+WTP_API int wtp_enable_trt(wtp_batch *b, const double *magic);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -51,6 +51,13 @@ on lattices of binary16 deviations from the weights.  The line has the shape of 
 nine 2-byte stores and the mask byte) in place of 72; no sequential leg.  Not with --ibb.  With --loads / --mex / --mean the batch is
 a half batch in both variants of those protocols (and --mex then times k_mex_half_batch).
 
+    python tools/polar_bench.py --trt MAGIC [--les CS] [--ibb] [--wind] [--storage half] [--repeats 5] [the options of the first form]
+
+The batched step with the two-relaxation-time collision (wtp_enable_trt, magic number MAGIC in every member): k_step_trt_batch (in a
+half batch k_step_trt_half_batch) in place of the kernel the other switches select.  The line has the shape of --les's; no sequential
+leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.  Without --trt, --lib may name a
+build from before the collision existed, so that a parent commit's library is timed by the same script.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -90,9 +97,10 @@ def _cross_flow(b):
     return U0 * np.sin(np.radians(_alphas(b)))
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native"):
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native", trt=None):
     """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
-    ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across."""
+    ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across;
+    trt: the magic number of the two-relaxation-time collision in every member (None: one relaxation time)."""
     out = []
     with pkg.PolarEngine(nx, ny, b, storage=storage) as eng:
         eng.set_masks(masks)
@@ -103,6 +111,8 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False,
             eng.enable_les(les)
         if ibb:
             _interpolated_walls(eng, nx, ny, b)
+        if trt is not None:
+            eng.enable_trt(trt)
         eng.step(warmup, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -117,6 +127,7 @@ LES = None      # --les: the Smagorinsky constant the sampled protocols run with
 IBB = False     # --ibb: the sampled protocols run with interpolated bounce-back
 WIND = False    # --wind: the sampled protocols run with an inclined free stream
 STORAGE = "native"      # --storage: the sampled protocols run on a batch of this storage
+TRT = None      # --trt: the magic number the sampled protocols run the two-relaxation-time collision with (None: off)
 
 
 def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
@@ -137,6 +148,8 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.enable_les(LES)
         if IBB:
             _interpolated_walls(eng, nx, ny, b)
+        if TRT is not None:
+            eng.enable_trt(TRT)
         eng.step(warmup - warmup % every, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -255,6 +268,7 @@ def main():
     ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
     ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
     ap.add_argument("--storage", default="native", choices=pkg.polar.STORAGES, help="how the batch stores its populations (half: binary16 deviations)")
+    ap.add_argument("--trt", type=float, default=None, metavar="MAGIC", help="step with the two-relaxation-time collision, magic number MAGIC in every member")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
@@ -263,12 +277,12 @@ def main():
     if a.repeats is None:
         a.repeats = 1 if plain else 7
     if a.lib:
-        pkg.polar.load_polar_library(a.lib)
+        pkg.polar.load_polar_library(a.lib, optional=() if a.trt is not None else ("wtp_enable_trt",))
     if a.storage == "half" and a.ibb:
         ap.error("--storage half does not combine with --ibb")
     half = a.storage == "half"
-    global LES, IBB, WIND, STORAGE
-    LES, IBB, WIND, STORAGE = a.les, a.ibb, a.wind, a.storage
+    global LES, IBB, WIND, STORAGE, TRT
+    LES, IBB, WIND, STORAGE, TRT = a.les, a.ibb, a.wind, a.storage, a.trt
     if a.mean:
         return mean_cost(a)
     if a.mex:
@@ -280,7 +294,7 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage, trt=a.trt)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
@@ -288,8 +302,12 @@ def main():
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.ibb or a.wind or half or a.repeats > 1:
+            if a.les is not None or a.ibb or a.wind or half or a.trt is not None or a.repeats > 1:
                 line["les"] = a.les
+                if a.trt is not None:
+                    line["trt"] = a.trt
+                if a.lib:
+                    line["lib"] = a.lib
                 if half:
                     line["storage"] = "half"
                 if a.ibb:
@@ -297,7 +315,7 @@ def main():
                 if a.wind:
                     line["wind"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half:
+            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half and a.trt is None:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
