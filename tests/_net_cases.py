@@ -4,8 +4,10 @@ tests/test_gpu_polar_net.py compares the kernels with.  Test infrastructure only
 A case is a lattice (chosen by step_tile's tile classes, as in tests/test_gpu_polar_les.py), a configuration is a pair of wall rule
 and collision: "les" (half-way walls, k_step_les_batch), "ibb-bgk" and "ibb-les" (interpolated walls, k_step_ibb_batch with either
 collision).  Every batch has the same three kinds of member: one driven onto the net with a weak model (cs > 0), one driven onto it
-with cs = 0, one healthy.  The library has no way to write a state, so the net is reached by stepping from equilibrium: tau - 0.5
-of 4e-4 and an inflow of 0.31 against the velocity bound of 0.35, started impulsively on a body of blocks, slots and single cells.
+with cs = 0, one healthy.  These cases reach the net by stepping from equilibrium, as a sweep does: tau - 0.5 of 4e-4 and an inflow
+of 0.31 against the velocity bound of 0.35, started impulsively on a body of blocks, slots and single cells.  (They were written when
+the library had no way to write a state; since wtp_write_f, tests/_net_rough_cases.py puts every step kernel on the net in its first
+step from a written start, on these masks and wall distances.)
 
 The reference of a member is lbm_numpy.run (cs = 0, half-way walls), _les_reference or _ibb_reference, stepped one step at a time so
 that the events of every step are seen: an event is an interior fluid cell whose stored moments sit at a bound (rho == 0.5, rho == 2.0
