@@ -117,7 +117,6 @@ template <int DIR, int DEPTH, bool EMIT, int FD, typename T, int S>
 struct ChainUnit {
     typedef MV<T, S> V3;
     typedef ChainPops<DIR> P;
-    static constexpr unsigned HREC = M3_HL * sizeof(T);
     static constexpr int FULL = (1 << DEPTH) - 1;
     static constexpr bool OVLF = (FD & MARCH_FD_OVL) != 0;
 
@@ -141,7 +140,7 @@ struct ChainUnit {
                                          ChainLds<T, S, DEPTH> &lds_)
         : p(p_), m(m_), rh(rh_), feq0(feq0_), lds(lds_) {}
 
-    __device__ __forceinline__ unsigned hcol(int c) const { return (unsigned)(c > 0 ? c : 0) * HREC; }
+    __device__ __forceinline__ unsigned hcol(int c) const { return halo_line_off<T>(c); }
     __device__ __forceinline__ int clampx(int x) const { return x < x_lo ? x_lo : (x > x_hi ? x_hi : x); }
 
     // One iteration with the level-1 front at column x: stage 1 (bit 0 of MASK) = STEP_FS on the streamed inputs of column x; stage k
@@ -361,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
     feq_all<T>(T(1), p.U0, T(0), feq0);
 
     // classes of columns ia-PAD .. ib+PAD-1 (lane l <-> columns ia-PAD+l and ia-PAD+64+l): two ballots each (ClassMask), up to 128 columns
-    constexpr int PAD = DEPTH == 4 ? 3 : 2;
+    constexpr int PAD = march_pad(DEPTH);
     ClassMask nonfast_m, solid_m;
     {
         const int n = ib - ia + 2 * PAD;
@@ -374,11 +373,12 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
     }
     const ClassMask no_m{0ULL, 0ULL};
     const bool lean = (nonfast_m.lo | nonfast_m.hi) == 0ULL && ia + g.gi0 >= PAD + 1 && ib + g.gi0 <= g.nx_g - PAD - 1 && !(uflags & MU_OUTLET_AFTER) && !(p.rev & 2);
+    // fp32 at four steps per pass: the packed two-site collision (step_march.hpp)
+    constexpr int FDP = (DEPTH == 4 && sizeof(T) == 4) ? (FD | MARCH_FD_PACKED | (EMIT ? 0 : MARCH_FD_VELSHARED)) : FD;
     if constexpr (DEPTH >= 3) {
         // chain blocks (step_chain.hpp): the four waves of this workgroup share the edge columns of their units through LDS.  The flag is
         // per block (set by chain_blocks on the host for all four units or none), so the barriers inside are workgroup-uniform.
         if (uflags & MU_CHAIN) {
-            constexpr int FDP = (DEPTH == 4 && sizeof(T) == 4) ? (FD | MARCH_FD_PACKED | (EMIT ? 0 : MARCH_FD_VELSHARED)) : FD;
             ChainLds<T, S, DEPTH> &chain_lds = lds_pool.chain;
             const bool end_shared = (uflags & MU_END_SHARED) != 0;
             if (lane < 2 * (DEPTH - 1)) chain_lds.flag[lane / (DEPTH - 1)][lane % (DEPTH - 1)][u & 3] = 0;     // my own hand-over flags ...
@@ -395,17 +395,8 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
             return;
         }
     }
-    if (DEPTH == 4) {
-        constexpr int FDP = sizeof(T) == 4 ? (FD | MARCH_FD_PACKED | (EMIT ? 0 : MARCH_FD_VELSHARED)) : FD;     // fp32: the packed two-site collision (step_march.hpp)
-        if (lean) march_unit4<false, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, no_m, no_m, feq0);
-        else march_unit4<true, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
-    } else if (DEPTH == 3) {
-        if (lean) march_unit3<false, EMIT, FD, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, no_m, no_m, feq0);
-        else march_unit3<true, EMIT, FD, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
-    } else {
-        if (lean) march_unit3_d2<false, EMIT, FD, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, no_m, no_m, feq0);
-        else march_unit3_d2<true, EMIT, FD, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
-    }
+    if (lean) march_unit<DEPTH, false, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, no_m, no_m, feq0);
+    else march_unit<DEPTH, true, EMIT, FDP, T, S>(p, m, rh, hoff, ia, ib, uflags, j0, lane, far_win, nonfast_m, solid_m, feq0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -417,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void k_march3(MarchParams<T> p)
 // windows of one column range are neighbours), like the units of the solo plan.
 static inline void chain_blocks(MarchPlan &pl, const uint8_t *wcls, const Geom &g, int depth, bool enable)
 {
-    const int ld = g.nxl + 2, pad = depth == 4 ? 3 : 2;
+    const int ld = g.nxl + 2, pad = march_pad(depth);
     std::vector<std::vector<MarchUnit>> per((size_t)pl.nwin);
     for (const MarchUnit &u : pl.units) per[(size_t)u.w].push_back(u);
     struct Block { MarchUnit u[4]; };
@@ -462,7 +453,7 @@ static inline void chain_blocks(MarchPlan &pl, const uint8_t *wcls, const Geom &
 // footprint (`pad` columns beyond either end) inside the local lattice, clear of the tunnel's ends and FAST throughout.
 static inline bool chain_group_ok(const MarchUnit *u, const uint8_t *wcls, const Geom &g, int depth)
 {
-    const int ld = g.nxl + 2, pad = depth == 4 ? 3 : 2;
+    const int ld = g.nxl + 2, pad = march_pad(depth);
     static const int want[4] = {MU_CHAIN | MU_DIR_NEG, MU_CHAIN | MU_END_SHARED, MU_CHAIN | MU_DIR_NEG | MU_END_SHARED, MU_CHAIN};
     for (int k = 0; k < 4; k++) {
         if (u[k].flags != want[k] || u[k].w != u[0].w || u[k].ib - u[k].ia < depth + 1) return false;
@@ -532,7 +523,7 @@ static inline MarchPlan build_chain_plan_timed(const uint8_t *wcls, const Geom &
                                                int max_len, int depth, const ChainCost &cc, const float *colw = nullptr)
 {
     MarchPlan pl;
-    const int nwin = march_nwin(g.ny, win), ld = g.nxl + 2, pad = depth == 4 ? 3 : 2;
+    const int nwin = march_nwin(g.ny, win), ld = g.nxl + 2, pad = march_pad(depth);
     pl.nwin = nwin;
     const int ncol = r.i_end - r.i_begin;
     if (ncol <= 0) return pl;

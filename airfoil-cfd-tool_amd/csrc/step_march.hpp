@@ -34,6 +34,9 @@ static constexpr int MARCH_MAX_CHUNK = 60;       // two-step tables: the unit le
 static constexpr int MARCH3_MAX_CHUNK = 124;     // three / four steps per pass: two ballots (ClassMask), columns ia-PAD .. ib+PAD-1 <= 128
 // most columns a unit of a `depth`-step plan may hold (the planners' max_len; a four-step unit's class masks reach three columns beyond it)
 static inline int march_max_len(int depth) { return depth == 4 ? MARCH3_MAX_CHUNK - 3 : (depth == 3 ? MARCH3_MAX_CHUNK : MARCH_MAX_CHUNK); }
+// columns beyond either end of a unit of a `depth`-step pass whose classes it reads — its class masks cover ia-PAD .. ib+PAD-1 —, and that a chain
+// block's footprint takes in: a four-step unit computes level 1 of three columns on either side, the others of (at most) two
+__host__ __device__ constexpr int march_pad(int depth) { return depth == 4 ? 3 : 2; }
 
 // classes of up to 128 consecutive columns of a window, one bit each (lane l of the first ballot <-> the first column + l, of the second + 64 + l)
 struct ClassMask { unsigned long long lo, hi; };
@@ -844,7 +847,7 @@ __device__ __forceinline__ MV<T, S> own_read(const char *buf, int k, int lane)
 
 // Step 1 of column x -> G (all nine directions).  `in` holds the streamed inputs of column x (modified in place).
 // OWN_LDS: the column's own populations (general columns only) are in the LDS buffer `own_buf`, requested by own_prefetch — one iteration ago in the
-// units' loops, just now for a unit's first columns; false (the two-step passes, march_unit3_d2): they are loaded here.
+// units' loops, just now for a unit's first columns; false (the two-step passes, march_unit at DEPTH 2, and the chain units): they are loaded here.
 // `pre` (optional): the column's solid flags and bounce codes {solid4, code4}, fetched ahead by the caller (SiteBytes below)
 template <bool BODY, int FD, typename T, int S, bool OWN_LDS = false>
 __device__ __forceinline__ void march_step1(const MarchParams<T> &p, const MarchAddr<T, S> &a, int x, int j0, bool far_win, bool nonfast, bool allsolid,

@@ -10,7 +10,7 @@
 // per site instead of 18 T.  Every further level costs 21 register-resident vectors; with 8-byte vectors T = 3 takes
 // 196-225 VGPRs and T = 4 216-256 (two waves per SIMD either way; 16-byte vectors do not fit beyond T = 2).
 //
-// Pipeline of one wave (window w, columns [ia, ib)), iteration x (DEPTH = 3; DEPTH = 4: one more level, march_unit4):
+// Pipeline of one wave (window w, columns [ia, ib)), iteration x (march_unit at DEPTH = 3; DEPTH = 4: one more level and stage, DEPTH = 2: one less):
 //     level 1 of column x      <- STEP_FS on the nine streamed vectors of column x        (march_align_in + march_step1)
 //     level 2 of column x - 1  <- STEP_FS on level 1 of columns x-2, x-1, x               (march_stage)
 //     level 3 of column x - 2  <- STEP_FS on level 2 of columns x-3, x-2, x-1 -> stored   (march_stage)
@@ -19,6 +19,7 @@
 // previous pass wrote (four rows on either side of every seam) or, when that is stale, from the lattice.
 // Every site goes through the arithmetic of k_step DEPTH times: results are bit-identical to DEPTH single steps.
 #pragma once
+#include <type_traits>
 #include "step_march.hpp"
 
 namespace wt {
@@ -39,6 +40,9 @@ static constexpr int M3_SHALF = 40;
 static constexpr int M3_HL = 32;            // elements of one halo line
 static constexpr int HL_COLS = 60;          // lines (columns) per workgroup of the halo kernels
 static constexpr int H3_COLS = HL_COLS, H4_COLS = HL_COLS;
+// byte offset of column c's line within a seam's lines; a column left of the lattice (a pipeline that starts left of the inlet, a chain unit's
+// prefetch beyond its seam) reads line 0: its words are never used
+template <typename T> __device__ __forceinline__ unsigned halo_line_off(int c) { return (unsigned)(c > 0 ? c : 0) * (unsigned)(M3_HL * sizeof(T)); }
 
 // ------------------------------------------------------------------------------------------------
 // once per pass: the halo lines
@@ -463,20 +467,11 @@ __device__ __forceinline__ void wait_for_column(const MV<T, S> (&c)[9], T h1)
     for (int k = 0; k < 9; k++) __builtin_memcpy(&r[k], &c[k], 8);
     asm volatile("" ::"v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), "v"(r[8]), "v"(h1));
 }
-template <typename T, int S>
-__device__ __forceinline__ void wait_for_column(const MV<T, S> (&c)[9], T h1, T h2)
+template <typename T>
+__device__ __forceinline__ void wait_for_line(T h)      // a halo line more (a unit's prologue requests one per level)
 {
-    wait_for_column(c, h1);
 #ifndef WT_M3_NOWAIT
-    asm volatile("" ::"v"(h2));
-#endif
-}
-template <typename T, int S>
-__device__ __forceinline__ void wait_for_column(const MV<T, S> (&c)[9], T h1, T h2, T h3)
-{
-    wait_for_column(c, h1);
-#ifndef WT_M3_NOWAIT
-    asm volatile("" ::"v"(h2), "v"(h3));
+    asm volatile("" ::"v"(h));
 #endif
 }
 __device__ __forceinline__ void wait_for_bytes(const SiteBytes &b)
@@ -515,379 +510,231 @@ __device__ __forceinline__ void seam3_flush(const March3Addr<T, S> &m, int col, 
     store_data_fence2(d0, d1);
 }
 
-template <bool BODY, bool EMIT, int FD, typename T, int S>
-__device__ __forceinline__ void march_unit3(const MarchParams<T> &p, March3Addr<T, S> &m, __amdgpu_buffer_rsrc_t rh, unsigned hoff,
-                                            int ia, int ib, int uflags, int j0, int lane, bool far_win, ClassMask nonfast_m,
-                                            ClassMask solid_m, const T (&feq0)[9])
+// f(integral_constant<int, k>) for k = K0 .. K1 - 1: a loop over levels, whose number is a template argument of the stages
+template <int K0, int K1, typename F>
+__device__ __forceinline__ void for_levels(F &&f)
+{
+    if constexpr (K0 < K1) { f(std::integral_constant<int, K0>{}); for_levels<K0 + 1, K1>(f); }
+}
+
+// One SOLO unit of a DEPTH-step pass (DEPTH = 2, 3, 4): iteration x computes level 1 of column x from the streamed inputs, level k of column
+// x - (k-1) from the level below in registers, and stores level DEPTH of column x - (DEPTH-1).  BODY: the general loop (class tests, inlet, outlet,
+// body); false: the lean loop of a unit whose whole footprint is plain interior fluid.
+template <int DEPTH, bool BODY, bool EMIT, int FD, typename T, int S>
+__device__ __forceinline__ void march_unit(const MarchParams<T> &p, March3Addr<T, S> &m, __amdgpu_buffer_rsrc_t rh, unsigned hoff,
+                                           int ia, int ib, int uflags, int j0, int lane, bool far_win, ClassMask nonfast_m,
+                                           ClassMask solid_m, const T (&feq0)[9])
 {
     constexpr bool OVLF = (FD & MARCH_FD_OVL) != 0;      // overlapping windows: no halo lines, no seam rows (step_chain.hpp k_march3)
+    constexpr int NL = DEPTH - 1;                        // levels held in registers from one iteration to the next (21 vectors each)
+    constexpr int PAD = march_pad(DEPTH);                // the class masks start at column ia - PAD (k_march3)
+    constexpr int PRO = DEPTH == 2 ? 1 : 2;              // columns whose level 1 the prologue computes, ia-NL .. ia-NL+PRO-1: it holds one level, so two at the most
+    constexpr int LEAD = NL - PRO;                       // ... and the loop starts LEAD columns left of ia (0, 0, 1): a four-step pass needs level 1 of a third
+    constexpr bool LEFT = LEAD > 0;                      // the loop's columns may lie left of the masks and of the inlet column: the three guards below
+    constexpr bool PREFETCH = DEPTH >= 3;                // a general column's own populations go through LDS and its site bytes are fetched one iteration
+                                                         // ahead; the two-step passes load both in march_step1
     typedef MV<T, S> V3;
-    constexpr unsigned HREC = M3_HL * sizeof(T);     // bytes of one halo line
     const Geom &g = p.g;
     const MarchAddr<T, S> &a = m.a;
-#define NONFAST(x) (BODY && cm_bit(nonfast_m, (x) - ia + 2))
-#define ALLSOLID(x) (BODY && cm_bit(solid_m, (x) - ia + 2))
+    // (LEFT: the last stage of the first iteration works on column ia-PAD-1, outside the masks: no class -> plain / inlet branch, no mask access)
+    auto nonfast = [&](int x) { return BODY && (!LEFT || x >= ia - PAD) && cm_bit(nonfast_m, x - ia + PAD); };
+    auto allsolid = [&](int x) { return BODY && (!LEFT || x >= ia - PAD) && cm_bit(solid_m, x - ia + PAD); };
+    // the halo line of column c; (LEFT) of a column left of the lattice: any line, its stage takes the inlet branch
+    auto hcol = [&](int c) { return LEFT ? halo_line_off<T>(c) : (unsigned)c * (unsigned)(M3_HL * sizeof(T)); };
+    // (LEFT) the loads of a first loop column left of the inlet go to the inlet column (values unused)
+    auto lcol = [&](int x) { return (LEFT && BODY && x + g.gi0 < 0) ? -g.gi0 : x; };
     // a general column's own populations come out of this wave's LDS buffer (x & 1) (step_march.hpp own_prefetch): requested one iteration ahead in
-    // the loop, on the spot (OWN_NOW) for the unit's first columns
-#define OWN_BUF(x) (a.own_lds + ((x) & 1) * OWN_LDS_BYTES)
-#define OWN_NOW(x) do { if (BODY && NONFAST(x)) own_prefetch<T, S, OVLF>(a, (x), OWN_BUF(x)); } while (0)
-#define STEP1(x, in, G) march_step1<BODY, FD, T, S, BODY>(p, a, (x), j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G, nullptr, OWN_BUF(x))
-#define STEP1P(x, in, G, sb) march_step1<BODY, FD, T, S, BODY>(p, a, (x), j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G, BODY ? (sb).v : nullptr, OWN_BUF(x))
+    // the loop, on the spot (own_now) for the unit's first columns
+    auto own_buf = [&](int x) { return a.own_lds + (x & 1) * OWN_LDS_BYTES; };
+    auto own_now = [&](int x) { if (PREFETCH && BODY && nonfast(x)) own_prefetch<T, S, OVLF>(a, x, own_buf(x)); };
+    auto step1 = [&](int x, V3 (&in_)[9], V3 (&G_)[9], const uint32_t *pre) {
+        if constexpr (PREFETCH) march_step1<BODY, FD, T, S, BODY>(p, a, x, j0, far_win, nonfast(x), allsolid(x), feq0, in_, G_, pre, own_buf(x));
+        else march_step1<BODY, FD, T, S>(p, a, x, j0, far_win, nonfast(x), allsolid(x), feq0, in_, G_);
+    };
+    V3 mac[3];
+    // level K of column c from level K-1 of columns c-1 (`mb`: its populations 1, 5, 8), c and c+1; level DEPTH is what is stored, with its macros
+    auto stage = [&](auto level, int c, const V3 (&mb)[3], const V3 (&Gc)[9], const V3 (&Gn)[9], T hvc, V3 (&out)[9], const uint32_t *pre) {
+        constexpr int K = decltype(level)::value;
+        march_stage<BODY, K == DEPTH && EMIT, FD, 4 * (K - 2)>(p, c, j0, lane, far_win, nonfast(c), allsolid(c), feq0, mb, Gc, Gn, hvc, out, mac, pre);
+    };
     const bool outlet = BODY && (uflags & MU_OUTLET_AFTER) != 0;
-    const int xend = outlet ? ib : ib + 1;       // last column whose level 1 is computed (the outlet column itself for the last unit)
-    V3 s1m[3], s1c[9];           // level 1: populations 1,5,8 of column x-2; all nine of column x-1
-    V3 s2m[3], s2c[9];           // level 2: populations 1,5,8 of column x-3; all nine of column x-2
-    V3 in[9], G1[9], G2[9], mac[3];
-    // ---- prologue: level 1 of columns ia-2 and ia-1 (columns left of the inlet do not exist: the inlet column's far-field
+    const int xend = outlet ? ib : ib + DEPTH - 2;       // last column whose level 1 is computed (the outlet column itself for the last unit)
+    const int xs = ia - LEAD;                            // first loop column
+    V3 sm[NL][3], sc[NL][9];     // level k (index k-1): populations 1,5,8 of column x-k-1; all nine of column x-k
+    V3 in[9], G[DEPTH + 1][9];   // streamed inputs of column x; G[k] = level k computed in this iteration, of column x-k+1
+    T hv[DEPTH];                 // halo lines of the columns this iteration's stages work on: hv[k] = column x-k
+    SiteBytes sb[DEPTH];         // their site bytes (PREFETCH, general loop only; see SiteBytes)
+    // ---- prologue: level 1 of the PRO columns before the loop's first (columns left of the inlet do not exist: the inlet column's far-field
     //      value stands in — never used, the inlet column is a constant at every level)
 #pragma unroll
-    for (int k = 0; k < 9; k++) { s1c[k] = mv_splat<T, S>(feq0[k]); s2c[k] = s1c[k]; }
-    s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-    s2m[0] = s1c[1]; s2m[1] = s1c[5]; s2m[2] = s1c[8];
+    for (int k = 0; k < NL; k++) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) sc[k][q] = mv_splat<T, S>(feq0[q]);
+        sm[k][0] = sc[k][1]; sm[k][1] = sc[k][5]; sm[k][2] = sc[k][8];
+    }
     // halo lines of the columns the first iteration's stages work on (afterwards: one line per iteration, fetched one iteration ahead like the
     // populations, and handed from stage to stage)
-    T hv2 = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(ia - 2 > 0 ? ia - 2 : 0) * HREC);          // column x-2
-    T hv1 = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(ia - 1 > 0 ? ia - 1 : 0) * HREC);          // column x-1
-    T hv0 = halo_load_x<OVLF, T>(rh, hoff, (unsigned)ia * HREC);                                 // column x
-    if (!BODY || ia - 2 + g.gi0 >= 0) {
-        OWN_NOW(ia - 2);
-        march_load_aligned(a, ia - 2, in);
-        march_align_in<OVLF>(in, lane, hv2);
-        STEP1(ia - 2, in, s1c);
+#pragma unroll
+    for (int k = NL; k > 0; k--) hv[k] = halo_load_x<OVLF, T>(rh, hoff, halo_line_off<T>(xs - k));
+    hv[0] = halo_load_x<OVLF, T>(rh, hoff, hcol(xs));
+#pragma unroll
+    for (int q = 0; q < PRO; q++) {
+        const int c = xs - PRO + q;
+        if (q > 0) { sm[0][0] = sc[0][1]; sm[0][1] = sc[0][5]; sm[0][2] = sc[0][8]; }
+        if (!BODY || c + g.gi0 >= 0) {
+            own_now(c);
+            march_load_aligned(a, c, in);
+            march_align_in<OVLF>(in, lane, hv[PRO - q]);
+            step1(c, in, sc[0], nullptr);
+        }
     }
-    s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-    if (!BODY || ia - 1 + g.gi0 >= 0) {
-        OWN_NOW(ia - 1);
-        march_load_aligned(a, ia - 1, in);
-        march_align_in<OVLF>(in, lane, hv1);
-        STEP1(ia - 1, in, s1c);
+    own_now(xs);                                         // (a column left of the inlet carries no class)
+    march_load_aligned(a, lcol(xs), in);
+#pragma unroll
+    for (int k = 0; k < DEPTH; k++) sb[k] = SiteBytes{{0, 0}};
+    if (PREFETCH && BODY) {
+#pragma unroll
+        for (int k = 0; k < DEPTH; k++) sb[k] = site_bytes_load<T, S, OVLF>(p, xs - k, j0);
+#pragma unroll
+        for (int k = 0; k < DEPTH; k++) wait_for_bytes(sb[k]);
     }
-    OWN_NOW(ia);
-    march_load_aligned(a, ia, in);
-    // site bytes of columns x, x-1, x-2 (general loop only; see SiteBytes)
-    SiteBytes sb0{{0, 0}}, sb1{{0, 0}}, sb2{{0, 0}};
-    if (BODY) { sb0 = site_bytes_load<T, S, OVLF>(p, ia, j0); sb1 = site_bytes_load<T, S, OVLF>(p, ia - 1, j0); sb2 = site_bytes_load<T, S, OVLF>(p, ia - 2, j0); wait_for_bytes(sb0); wait_for_bytes(sb1); wait_for_bytes(sb2); }
-    wait_for_column(in, hv0, hv1, hv2);      // no load pending at the loop header: see wait_for_column
+    wait_for_column(in, hv[0]);                          // no load pending at the loop header: see wait_for_column
+#pragma unroll
+    for (int k = 1; k < DEPTH; k++) wait_for_line(hv[k]);
     int seam_col = -1;           // column whose seam rows are staged in LDS (-1: none yet; the flush then lands on the pad record)
+    // A finished column c out: its nine (twelve) stores — dropped through an out-of-range offset unless the unit owns the column — stage its seam rows in
+    // LDS; `sp` = those of the column before, taken out (seam3_fetch) BEFORE that, go to the seam buffer behind the stores.
+    auto put_col = [&](const Seam3 &sp, bool owned, int c, const V3 (&o)[9]) {
+        march3_store<EMIT, OVLF>(m, owned ? a.voff_st : p.lat_bytes, owned ? c : 0, o, mac);
+        seam3_flush<OVLF>(m, seam_col, sp);
+        seam_col = owned ? c : seam_col;
+    };
 #ifdef WT_M3_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev_ = __builtin_amdgcn_s_memtime();
 #endif
-    // The loop body has no branch on the pipeline fill: during the first two iterations (x - 2 < ia) level 3 is computed on
+    // The loop body has no branch on the pipeline fill: during the first iterations (x - NL < ia) the last level is computed on
     // don't-care values and its stores are dropped by an out-of-range offset — a scalar `if` around the stage and its
     // stores makes hipcc's waitcnt pass drain vmcnt(0) at the merge points of every iteration.
 #pragma unroll 1
-    for (int x = ia; x <= xend; x++) {
+    for (int x = xs; x <= xend; x++) {
         V3 nxt[9];
         // a general column next: its own populations on their way into LDS (own_prefetch), AHEAD of this iteration's prefetch — loads return in
         // order, so the wait for the prefetched column at the end of the iteration covers them (behind stage 1 instead: the plain slabs ran 4 % slower)
-        if (BODY && x + 1 <= xend && NONFAST(x + 1)) own_prefetch<T, S, OVLF>(a, x + 1, OWN_BUF(x + 1));
+        if (PREFETCH && BODY && x + 1 <= xend && nonfast(x + 1)) own_prefetch<T, S, OVLF>(a, x + 1, own_buf(x + 1));
         march_load_aligned(a, (x + 1 <= xend) ? x + 1 : x, nxt);              // prefetch (last one: harmless re-load)
-        const bool has2 = x - 2 >= ia;                                         // column x-2 is an output column
-        const int c1 = x - 1, c2 = x - 2;
-        const T hvn = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(x + 1) * HREC);        // column x+1's halo line: the next iteration's first stage
+        const int co = x - NL;                                                 // the column this iteration stores ...
+        const bool has = co >= ia;                                             // ... if it is an output column
+        const T hvn = halo_load_x<OVLF, T>(rh, hoff, hcol(x + 1));             // column x+1's halo line: the next iteration's first stage
         SiteBytes sbn{{0, 0}};
-        if (BODY) sbn = site_bytes_load<T, S, OVLF>(p, x + 1, j0);
-        const Seam3 sp = seam3_fetch<OVLF>(m);                                       // staged by the previous iteration's store
+        if (PREFETCH && BODY) sbn = site_bytes_load<T, S, OVLF>(p, x + 1, j0);
+        const Seam3 sp = seam3_fetch<OVLF>(m);                                 // staged by the previous iteration's store
         M3_STAMP(0);                                                           // issue of the prefetch
-        march_align_in<OVLF>(in, lane, hv0);
-        STEP1P(x, in, G1, sb0);                                                // level 1 of column x
+        march_align_in<OVLF>(in, lane, hv[0]);
+        step1(x, in, G[1], (PREFETCH && BODY) ? sb[0].v : nullptr);            // level 1 of column x
         M3_STAMP(1);
-        // level 2 of column x-1 (a column left of the inlet takes the inlet branch: constants, no memory access)
-        march_stage<BODY, false, FD, 0>(p, c1, j0, lane, far_win, NONFAST(c1), ALLSOLID(c1), feq0, s1m, s1c, G1, hv1, G2, mac, BODY ? sb1.v : nullptr);
+        // level k of column x-k+1 (a column left of the inlet takes the inlet branch: constants, no memory access)
+        for_levels<2, DEPTH + 1>([&](auto level) {
+            constexpr int k = decltype(level)::value;
+            stage(level, x - k + 1, sm[k - 2], sc[k - 2], G[k - 1], hv[k - 1], G[k], (PREFETCH && BODY) ? sb[k - 1].v : nullptr);
 #ifdef WT_M3_STAMPS
-        pin_after(G2);
+            if constexpr (k == 2 && k < DEPTH) { pin_after(G[k]); M3_STAMP(2); }
 #endif
-        M3_STAMP(2);
-        V3 out[9];
-        march_stage<BODY, EMIT, FD, 4>(p, c2, j0, lane, far_win, NONFAST(c2), ALLSOLID(c2), feq0, s2m, s2c, G2, hv2, out, mac, BODY ? sb2.v : nullptr);
-        pin_after(out);
+        });
+        pin_after(G[DEPTH]);
         M3_STAMP(3);
         wait_for_column(nxt, hvn);
-        if (BODY) { wait_for_bytes(sbn); sb2 = sb1; sb1 = sb0; sb0 = sbn; }
+        if (PREFETCH && BODY) wait_for_bytes(sbn);
 #ifdef WT_M3_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         M3_STAMP(4);                                                           // the wait for the prefetched column
-        hv2 = hv1; hv1 = hv0; hv0 = hvn;
-        march3_store<EMIT, OVLF>(m, has2 ? a.voff_st : p.lat_bytes, has2 ? c2 : 0, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        M3_STAMP(5);                                                           // issue of the stores
-        seam_col = has2 ? c2 : seam_col;
-        if (BODY && outlet && x == xend) break;                                // the tail below needs the unshifted state
-        s2m[0] = s2c[1]; s2m[1] = s2c[5]; s2m[2] = s2c[8];
-        s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
 #pragma unroll
-        for (int k = 0; k < 9; k++) { s2c[k] = G2[k]; s1c[k] = G1[k]; in[k] = nxt[k]; }
+        for (int k = NL; k > 0; k--) { hv[k] = hv[k - 1]; sb[k] = sb[k - 1]; }
+        hv[0] = hvn; sb[0] = sbn;
+        put_col(sp, has, co, G[DEPTH]);
+        M3_STAMP(5);                                                           // issue of the stores
+        if (BODY && outlet && x == xend) break;                                // the tail below needs the unshifted state
+#pragma unroll
+        for (int k = NL - 1; k >= 0; k--) { sm[k][0] = sc[k][1]; sm[k][1] = sc[k][5]; sm[k][2] = sc[k][8]; }
+#pragma unroll
+        for (int q = 0; q < 9; q++) {
+#pragma unroll
+            for (int k = NL - 1; k >= 0; k--) sc[k][q] = G[k + 1][q];
+            in[q] = nxt[q];
+        }
     }
 #ifdef WT_M3_STAMPS
     if (!BODY && lane == 0) {
         for (int i = 0; i < 6; i++) atomicAdd(&g_m3_stamps[i], st_[i]);
-        atomicAdd(&g_m3_stamps[6], (unsigned long long)(xend - ia + 1));
+        atomicAdd(&g_m3_stamps[6], (unsigned long long)(xend - xs + 1));
         atomicAdd(&g_m3_stamps[7], 1ULL);
     }
 #endif
     if (BODY && outlet) {
-        // Here x = ib = NX-1 (local): s1c = level 1 of NX-2, G1 = level 1 of NX-1, s2c = level 2 of NX-3, G2 = level 2 of NX-2;
-        // level 3 of NX-3 is stored.  The outlet column copies the previous level of column NX-2 (html:301-312):
-        //   level 2 of NX-1 = level 1 of NX-2;  level 3 of NX-1 = level 2 of NX-2;  solid sites: own previous level reversed.
-        const int co = ib;                                   // outlet column
-        uint32_t solid4 = 0;
-        if (NONFAST(co)) solid4 = load_site_bytes<S>(p.mask + (long)(co + 1) * g.pitch + site_row<S, OVLF>(j0, g.ny));
-        const bool any_solid = __ballot(solid4 != 0) != 0ULL;
-        V3 L2o[9], out[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) L2o[k] = s1c[k];
-        if (any_solid) { auto own1 = [&](int k) { return G1[k]; }; march_solid<T, S, false>(L2o, mac, solid4, own1); }
-        // level 3 of column NX-2
-        V3 t2m[3];
-        t2m[0] = s2c[1]; t2m[1] = s2c[5]; t2m[2] = s2c[8];
-        const T hv2t = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(co - 1) * HREC);
-        Seam3 sp = seam3_fetch<OVLF>(m);
-        march_stage<BODY, EMIT, FD, 4>(p, co - 1, j0, lane, far_win, NONFAST(co - 1), ALLSOLID(co - 1), feq0, t2m, G2, L2o, hv2t, out, mac);
-        march3_store<EMIT, OVLF>(m, a.voff_st, co - 1, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = co - 1;
-        // level 3 of the outlet column
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = G2[k];
-        if (EMIT) march_outlet_macro(G2, mac);
-        if (any_solid) { auto own2 = [&](int k) { return L2o[k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own2); }
-        sp = seam3_fetch<OVLF>(m);
-        march3_store<EMIT, OVLF>(m, a.voff_st, co, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = co;
-    }
-    seam3_flush<OVLF>(m, seam_col, seam3_fetch<OVLF>(m));
-#undef NONFAST
-#undef ALLSOLID
-#undef STEP1
-#undef STEP1P
-#undef OWN_BUF
-#undef OWN_NOW
-}
-
-// FOUR steps per pass: one more level (s3m / s3c) and one more stage than march_unit3; the pipeline starts one column earlier
-// (level 2 of column ia-2 is needed) and delivers level 4 of column x-3.  Columns ia-3 .. ib+2 take part: class masks are indexed
-// by x - ia + 3.
-template <bool BODY, bool EMIT, int FD, typename T, int S>
-__device__ __forceinline__ void march_unit4(const MarchParams<T> &p, March3Addr<T, S> &m, __amdgpu_buffer_rsrc_t rh,
-                                            unsigned hoff, int ia, int ib, int uflags, int j0, int lane, bool far_win,
-                                            ClassMask nonfast_m, ClassMask solid_m, const T (&feq0)[9])
-{
-    constexpr bool OVLF = (FD & MARCH_FD_OVL) != 0;      // overlapping windows: no halo lines, no seam rows (step_chain.hpp k_march3)
-    typedef MV<T, S> V3;
-    constexpr unsigned HREC = M3_HL * sizeof(T);
-    const Geom &g = p.g;
-    const MarchAddr<T, S> &a = m.a;
-    // (the level-4 stage of the first iteration works on column ia-4, outside the masks: no class -> plain / inlet branch, no mask access)
-#define NONFAST(x) (BODY && (x) >= ia - 3 && cm_bit(nonfast_m, (x) - ia + 3))
-#define ALLSOLID(x) (BODY && (x) >= ia - 3 && cm_bit(solid_m, (x) - ia + 3))
-#define OWN_BUF(x) (a.own_lds + ((x) & 1) * OWN_LDS_BYTES)
-#define OWN_NOW(x) do { if (BODY && NONFAST(x)) own_prefetch<T, S, OVLF>(a, (x), OWN_BUF(x)); } while (0)      // (see march_unit3)
-#define STEP1(x, in, G) march_step1<BODY, FD, T, S, BODY>(p, a, (x), j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G, nullptr, OWN_BUF(x))
-#define HCOL(c) ((unsigned)((c) > 0 ? (c) : 0) * HREC)
-    const bool outlet = BODY && (uflags & MU_OUTLET_AFTER) != 0;
-    const int xend = outlet ? ib : ib + 2;       // last column whose level 1 is computed
-    V3 s1m[3], s1c[9];           // level 1: populations 1,5,8 of column x-2; all nine of column x-1
-    V3 s2m[3], s2c[9];           // level 2: ... of column x-3; x-2
-    V3 s3m[3], s3c[9];           // level 3: ... of column x-4; x-3
-    V3 in[9], G1[9], G2[9], G3[9], mac[3];
-#pragma unroll
-    for (int k = 0; k < 9; k++) { s1c[k] = mv_splat<T, S>(feq0[k]); s2c[k] = s1c[k]; s3c[k] = s1c[k]; }
-    s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-    s2m[0] = s1c[1]; s2m[1] = s1c[5]; s2m[2] = s1c[8];
-    s3m[0] = s1c[1]; s3m[1] = s1c[5]; s3m[2] = s1c[8];
-    // ---- prologue: level 1 of columns ia-3 and ia-2 (columns left of the inlet do not exist: the far-field value stands in)
-    const int xs = ia - 1;       // first loop column; when it lies left of the inlet its loads go to the inlet column (values unused)
-#define LCOL(x) ((BODY && (x) + g.gi0 < 0) ? -g.gi0 : (x))
-    // halo lines of columns x-3, x-2, x-1, x (afterwards: one line per iteration, fetched one iteration ahead, handed from stage to stage)
-    T hv3 = halo_load_x<OVLF, T>(rh, hoff, HCOL(xs - 3)), hv2 = halo_load_x<OVLF, T>(rh, hoff, HCOL(xs - 2)), hv1 = halo_load_x<OVLF, T>(rh, hoff, HCOL(xs - 1)),
-      hv0 = halo_load_x<OVLF, T>(rh, hoff, HCOL(xs));
-    if (!BODY || ia - 3 + g.gi0 >= 0) {
-        OWN_NOW(ia - 3);
-        march_load_aligned(a, ia - 3, in);
-        march_align_in<OVLF>(in, lane, hv2);          // ia - 3 = xs - 2
-        STEP1(ia - 3, in, s1c);
-    }
-    s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-    if (!BODY || ia - 2 + g.gi0 >= 0) {
-        OWN_NOW(ia - 2);
-        march_load_aligned(a, ia - 2, in);
-        march_align_in<OVLF>(in, lane, hv1);          // ia - 2 = xs - 1
-        STEP1(ia - 2, in, s1c);
-    }
-    OWN_NOW(xs);                                // (a column left of the inlet carries no class)
-    march_load_aligned(a, LCOL(xs), in);
-    // site bytes of columns x, x-1, x-2, x-3 (general loop only; see SiteBytes)
-    SiteBytes sb0{{0, 0}}, sb1{{0, 0}}, sb2{{0, 0}}, sb3{{0, 0}};
-    if (BODY) {
-        sb0 = site_bytes_load<T, S, OVLF>(p, xs, j0); sb1 = site_bytes_load<T, S, OVLF>(p, xs - 1, j0); sb2 = site_bytes_load<T, S, OVLF>(p, xs - 2, j0); sb3 = site_bytes_load<T, S, OVLF>(p, xs - 3, j0);
-        wait_for_bytes(sb0); wait_for_bytes(sb1); wait_for_bytes(sb2); wait_for_bytes(sb3);
-    }
-    wait_for_column(in, hv0, hv1, hv2);
-    wait_for_column(in, hv3);
-    int seam_col = -1;
-#pragma unroll 1
-    for (int x = xs; x <= xend; x++) {
-        V3 nxt[9];
-        if (BODY && x + 1 <= xend && NONFAST(x + 1)) own_prefetch<T, S, OVLF>(a, x + 1, OWN_BUF(x + 1));      // (see march_unit3)
-        march_load_aligned(a, (x + 1 <= xend) ? x + 1 : x, nxt);
-        const bool has3 = x - 3 >= ia;                                         // column x-3 is an output column
-        const int c1 = x - 1, c2 = x - 2, c3 = x - 3;
-        const T hvn = halo_load_x<OVLF, T>(rh, hoff, HCOL(x + 1));                      // column x+1's halo line: the next iteration's first stage
-        SiteBytes sbn{{0, 0}};
-        if (BODY) sbn = site_bytes_load<T, S, OVLF>(p, x + 1, j0);
-        const Seam3 sp = seam3_fetch<OVLF>(m);
-        march_align_in<OVLF>(in, lane, hv0);
-        march_step1<BODY, FD, T, S, BODY>(p, a, x, j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G1, BODY ? sb0.v : nullptr, OWN_BUF(x));      // level 1 of column x
-
-        march_stage<BODY, false, FD, 0>(p, c1, j0, lane, far_win, NONFAST(c1), ALLSOLID(c1), feq0, s1m, s1c, G1, hv1, G2, mac, BODY ? sb1.v : nullptr);     // level 2 of x-1
-        march_stage<BODY, false, FD, 4>(p, c2, j0, lane, far_win, NONFAST(c2), ALLSOLID(c2), feq0, s2m, s2c, G2, hv2, G3, mac, BODY ? sb2.v : nullptr);     // level 3 of x-2
-        V3 out[9];
-        march_stage<BODY, EMIT, FD, 8>(p, c3, j0, lane, far_win, NONFAST(c3), ALLSOLID(c3), feq0, s3m, s3c, G3, hv3, out, mac, BODY ? sb3.v : nullptr);     // level 4 of x-3
-        pin_after(out);
-        wait_for_column(nxt, hvn);
-        if (BODY) { wait_for_bytes(sbn); sb3 = sb2; sb2 = sb1; sb1 = sb0; sb0 = sbn; }
-        hv3 = hv2; hv2 = hv1; hv1 = hv0; hv0 = hvn;
-        march3_store<EMIT, OVLF>(m, has3 ? a.voff_st : p.lat_bytes, has3 ? c3 : 0, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = has3 ? c3 : seam_col;
-        if (BODY && outlet && x == xend) break;                                // the tail below needs the unshifted state
-        s3m[0] = s3c[1]; s3m[1] = s3c[5]; s3m[2] = s3c[8];
-        s2m[0] = s2c[1]; s2m[1] = s2c[5]; s2m[2] = s2c[8];
-        s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-#pragma unroll
-        for (int k = 0; k < 9; k++) { s3c[k] = G3[k]; s2c[k] = G2[k]; s1c[k] = G1[k]; in[k] = nxt[k]; }
-    }
-    if (BODY && outlet) {
-        // x = ib = NX-1 = co (local).  Held: level 1 of co-1 (s1c) and co (G1); level 2 of co-2 (s2c) and co-1 (G2); level 3 of co-3
-        // (s3c) and co-2 (G3); level 4 of co-3 is stored.  Outlet rule (html:301-312): level k+1 of co = level k of co-1; its solid
-        // sites: own level k reversed.
+        // Here x = ib = co, the outlet column NX-1 (local).  Held: level k of column co-k (sc[k-1]) and of column co-k+1 (G[k]); level DEPTH of column
+        // co-NL is stored.  The outlet column copies the previous level of column co-1 (html:301-312): level k+1 of co = level k of co-1, its solid
+        // sites their own level k reversed; the columns in between, co-d, climb their remaining levels d+2 .. DEPTH through march_stage.
         const int co = ib;
         uint32_t solid4 = 0;
-        if (NONFAST(co)) solid4 = load_site_bytes<S>(p.mask + (long)(co + 1) * g.pitch + site_row<S, OVLF>(j0, g.ny));
+        if (nonfast(co)) solid4 = load_site_bytes<S>(p.mask + (long)(co + 1) * g.pitch + site_row<S, OVLF>(j0, g.ny));
         const bool any_solid = __ballot(solid4 != 0) != 0ULL;
-        V3 O2[9], O3[9], L3a[9], out[9], tm[3];
-        // level 2 of co
+        // (three blocks on the shared arrays: written as ONE schedule over levels — L[d][k] = level k of column co-d — the fp32 four-step kernels
+        //  came out with 72-136 bytes of scratch per lane, profiles/march_unit_fold_isa.txt)
+        V3 out[9], mb[3];
+        if constexpr (DEPTH == 2) {
+            // level 2 of the outlet column = level 1 of co-1
 #pragma unroll
-        for (int k = 0; k < 9; k++) O2[k] = s1c[k];
-        if (any_solid) { auto own = [&](int k) { return G1[k]; }; march_solid<T, S, false>(O2, mac, solid4, own); }
-        // level 3 of co-1
-        tm[0] = s2c[1]; tm[1] = s2c[5]; tm[2] = s2c[8];
-        march_stage<BODY, false, FD, 4>(p, co - 1, j0, lane, far_win, NONFAST(co - 1), ALLSOLID(co - 1), feq0, tm, G2, O2, halo_load_x<OVLF, T>(rh, hoff, HCOL(co - 1)), L3a, mac);
-        // level 3 of co
+            for (int k = 0; k < 9; k++) out[k] = sc[0][k];
+            if (EMIT) march_outlet_macro(sc[0], mac);
+            if (any_solid) { auto own = [&](int k) { return G[1][k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own); }
+        } else if constexpr (DEPTH == 3) {
+            V3 O2[9];                    // level 2 of the outlet column
 #pragma unroll
-        for (int k = 0; k < 9; k++) O3[k] = G2[k];
-        if (any_solid) { auto own = [&](int k) { return O2[k]; }; march_solid<T, S, false>(O3, mac, solid4, own); }
-        // level 4 of co-2
-        tm[0] = s3c[1]; tm[1] = s3c[5]; tm[2] = s3c[8];
-        Seam3 sp = seam3_fetch<OVLF>(m);
-        // (a last unit of a single marched column does not own column co-2, and its level 3 of co-3 is not valid: drop the stores)
-        const bool own2 = co - 2 >= ia;
-        march_stage<BODY, EMIT, FD, 8>(p, co - 2, j0, lane, far_win, NONFAST(co - 2), ALLSOLID(co - 2), feq0, tm, G3, L3a, halo_load_x<OVLF, T>(rh, hoff, HCOL(co - 2)), out, mac);
-        march3_store<EMIT, OVLF>(m, own2 ? a.voff_st : p.lat_bytes, own2 ? co - 2 : 0, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = own2 ? co - 2 : seam_col;
-        // level 4 of co-1
-        tm[0] = G3[1]; tm[1] = G3[5]; tm[2] = G3[8];
-        sp = seam3_fetch<OVLF>(m);
-        march_stage<BODY, EMIT, FD, 8>(p, co - 1, j0, lane, far_win, NONFAST(co - 1), ALLSOLID(co - 1), feq0, tm, L3a, O3, halo_load_x<OVLF, T>(rh, hoff, HCOL(co - 1)), out, mac);
-        march3_store<EMIT, OVLF>(m, a.voff_st, co - 1, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = co - 1;
-        // level 4 of co
+            for (int k = 0; k < 9; k++) O2[k] = sc[0][k];
+            if (any_solid) { auto own = [&](int k) { return G[1][k]; }; march_solid<T, S, false>(O2, mac, solid4, own); }
+            // level 3 of column co-1
+            mb[0] = sc[1][1]; mb[1] = sc[1][5]; mb[2] = sc[1][8];
+            const T hvt = halo_load_x<OVLF, T>(rh, hoff, hcol(co - 1));
+            const Seam3 sp = seam3_fetch<OVLF>(m);
+            march_stage<BODY, EMIT, FD, 4>(p, co - 1, j0, lane, far_win, nonfast(co - 1), allsolid(co - 1), feq0, mb, G[2], O2, hvt, out, mac);
+            put_col(sp, true, co - 1, out);
+            // level 3 of the outlet column
 #pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = L3a[k];
-        if (EMIT) march_outlet_macro(L3a, mac);
-        if (any_solid) { auto own = [&](int k) { return O3[k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own); }
-        sp = seam3_fetch<OVLF>(m);
-        march3_store<EMIT, OVLF>(m, a.voff_st, co, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = co;
+            for (int k = 0; k < 9; k++) out[k] = G[2][k];
+            if (EMIT) march_outlet_macro(G[2], mac);
+            if (any_solid) { auto own = [&](int k) { return O2[k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own); }
+        } else {
+            V3 O2[9], O3[9], A3[9];      // levels 2 and 3 of the outlet column, level 3 of column co-1
+#pragma unroll
+            for (int k = 0; k < 9; k++) O2[k] = sc[0][k];
+            if (any_solid) { auto own = [&](int k) { return G[1][k]; }; march_solid<T, S, false>(O2, mac, solid4, own); }
+            mb[0] = sc[1][1]; mb[1] = sc[1][5]; mb[2] = sc[1][8];
+            march_stage<BODY, false, FD, 4>(p, co - 1, j0, lane, far_win, nonfast(co - 1), allsolid(co - 1), feq0, mb, G[2], O2, halo_load_x<OVLF, T>(rh, hoff, hcol(co - 1)), A3, mac);
+#pragma unroll
+            for (int k = 0; k < 9; k++) O3[k] = G[2][k];
+            if (any_solid) { auto own = [&](int k) { return O2[k]; }; march_solid<T, S, false>(O3, mac, solid4, own); }
+            // level 4 of column co-2
+            mb[0] = sc[2][1]; mb[1] = sc[2][5]; mb[2] = sc[2][8];
+            Seam3 sp = seam3_fetch<OVLF>(m);
+            // (a last unit of a single marched column does not own column co-2, and its level 3 of co-3 is not valid: drop the stores.  The planner
+            //  keeps the last unit of a four-step pass at two columns or more)
+            const bool own2 = co - 2 >= ia;
+            march_stage<BODY, EMIT, FD, 8>(p, co - 2, j0, lane, far_win, nonfast(co - 2), allsolid(co - 2), feq0, mb, G[3], A3, halo_load_x<OVLF, T>(rh, hoff, hcol(co - 2)), out, mac);
+            put_col(sp, own2, co - 2, out);
+            // level 4 of column co-1
+            mb[0] = G[3][1]; mb[1] = G[3][5]; mb[2] = G[3][8];
+            sp = seam3_fetch<OVLF>(m);
+            march_stage<BODY, EMIT, FD, 8>(p, co - 1, j0, lane, far_win, nonfast(co - 1), allsolid(co - 1), feq0, mb, A3, O3, halo_load_x<OVLF, T>(rh, hoff, hcol(co - 1)), out, mac);
+            put_col(sp, true, co - 1, out);
+            // level 4 of the outlet column
+#pragma unroll
+            for (int k = 0; k < 9; k++) out[k] = A3[k];
+            if (EMIT) march_outlet_macro(A3, mac);
+            if (any_solid) { auto own = [&](int k) { return O3[k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own); }
+        }
+        put_col(seam3_fetch<OVLF>(m), true, co, out);        // the outlet column at level DEPTH
     }
     seam3_flush<OVLF>(m, seam_col, seam3_fetch<OVLF>(m));
-#undef NONFAST
-#undef ALLSOLID
-#undef STEP1
-#undef OWN_BUF
-#undef OWN_NOW
-#undef HCOL
-#undef LCOL
-}
-
-// The same machinery stopped after level 2: TWO steps per pass on the tables of the plan (units, classes, halo lines, seam buffer S3) — the
-// two steps a step count leaves over after its three- / four-step passes, and every pass of a two-step plan (fuse_depth = 2).
-template <bool BODY, bool EMIT, int FD, typename T, int S>
-__device__ __forceinline__ void march_unit3_d2(const MarchParams<T> &p, March3Addr<T, S> &m, __amdgpu_buffer_rsrc_t rh, unsigned hoff, int ia, int ib,
-                                               int uflags, int j0, int lane, bool far_win, ClassMask nonfast_m, ClassMask solid_m,
-                                               const T (&feq0)[9])
-{
-    constexpr bool OVLF = (FD & MARCH_FD_OVL) != 0;      // overlapping windows: no halo lines, no seam rows (step_chain.hpp k_march3)
-    typedef MV<T, S> V3;
-    constexpr unsigned HREC = M3_HL * sizeof(T);
-    const Geom &g = p.g;
-    const MarchAddr<T, S> &a = m.a;
-#define NONFAST(x) (BODY && cm_bit(nonfast_m, (x) - ia + 2))
-#define ALLSOLID(x) (BODY && cm_bit(solid_m, (x) - ia + 2))
-#define STEP1(x, in, G) march_step1<BODY, FD, T, S>(p, a, (x), j0, far_win, NONFAST(x), ALLSOLID(x), feq0, in, G)
-    const bool outlet = BODY && (uflags & MU_OUTLET_AFTER) != 0;
-    const int xend = ib;         // last column whose level 1 is computed
-    V3 s1m[3], s1c[9];           // level 1: populations 1,5,8 of column x-2; all nine of column x-1
-    V3 in[9], G1[9], mac[3];
-#pragma unroll
-    for (int k = 0; k < 9; k++) s1c[k] = mv_splat<T, S>(feq0[k]);
-    s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-    T hv1 = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(ia - 1 > 0 ? ia - 1 : 0) * HREC), hv0 = halo_load_x<OVLF, T>(rh, hoff, (unsigned)ia * HREC);
-    if (!BODY || ia - 1 + g.gi0 >= 0) {
-        march_load_aligned(a, ia - 1, in);
-        march_align_in<OVLF>(in, lane, hv1);
-        STEP1(ia - 1, in, s1c);
-    }
-    march_load_aligned(a, ia, in);
-    wait_for_column(in, hv0, hv1);
-    int seam_col = -1;
-#pragma unroll 1
-    for (int x = ia; x <= xend; x++) {
-        V3 nxt[9];
-        march_load_aligned(a, (x + 1 <= xend) ? x + 1 : x, nxt);
-        const bool has1 = x - 1 >= ia;                                         // column x-1 is an output column
-        const int c1 = x - 1;
-        const T hvn = halo_load_x<OVLF, T>(rh, hoff, (unsigned)(x + 1) * HREC);
-        const Seam3 sp = seam3_fetch<OVLF>(m);
-        march_align_in<OVLF>(in, lane, hv0);
-        STEP1(x, in, G1);
-        V3 out[9];
-        march_stage<BODY, EMIT, FD, 0>(p, c1, j0, lane, far_win, NONFAST(c1), ALLSOLID(c1), feq0, s1m, s1c, G1, hv1, out, mac);
-        pin_after(out);
-        wait_for_column(nxt, hvn);
-        hv1 = hv0; hv0 = hvn;
-        march3_store<EMIT, OVLF>(m, has1 ? a.voff_st : p.lat_bytes, has1 ? c1 : 0, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = has1 ? c1 : seam_col;
-        if (BODY && outlet && x == xend) break;
-        s1m[0] = s1c[1]; s1m[1] = s1c[5]; s1m[2] = s1c[8];
-#pragma unroll
-        for (int k = 0; k < 9; k++) { s1c[k] = G1[k]; in[k] = nxt[k]; }
-    }
-    if (BODY && outlet) {
-        // x = ib = NX-1: s1c = level 1 of NX-2, G1 = level 1 of NX-1; level 2 of the outlet column = level 1 of NX-2 (html:301-312)
-        const int co = ib;
-        uint32_t solid4 = 0;
-        if (NONFAST(co)) solid4 = load_site_bytes<S>(p.mask + (long)(co + 1) * g.pitch + site_row<S, OVLF>(j0, g.ny));
-        V3 out[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = s1c[k];
-        if (EMIT) march_outlet_macro(s1c, mac);
-        if (__ballot(solid4 != 0) != 0ULL) { auto own1 = [&](int k) { return G1[k]; }; march_solid<T, S, EMIT>(out, mac, solid4, own1); }
-        const Seam3 sp = seam3_fetch<OVLF>(m);
-        march3_store<EMIT, OVLF>(m, a.voff_st, co, out, mac);
-        seam3_flush<OVLF>(m, seam_col, sp);
-        seam_col = co;
-    }
-    seam3_flush<OVLF>(m, seam_col, seam3_fetch<OVLF>(m));
-#undef NONFAST
-#undef ALLSOLID
-#undef STEP1
 }
 
 // Marched column range of a `depth`-step plan: global edges as in march_range (march_range3(g, 2) is march_range(g)); a local slab edge loses

@@ -105,6 +105,13 @@ static int check(const char *name, int nxl, int ny, int gi0, int nx_g, int win, 
         if (r.i_end - r.i_begin >= min_last && last_len[w] < min_last) bad++;
         if (n_outlet[w] != (r.outlet_after ? 1 : 0)) bad++;
     }
+    if (max_cost == 1) {                // a cost limit of one column: the shortest units there are (tests/_rough_start.py SHORTEST) — one marched column each,
+        for (const MarchUnit &u : pl.units) {       // min_last in a window's last unit (when the window marches that many), whatever the classes
+            if (u.ib <= u.ia) continue;
+            const int want = (u.ib == r.i_end && r.i_end - r.i_begin >= min_last) ? min_last : 1;
+            if (u.ib - u.ia != want) bad++;
+        }
+    }
     if (timed && max_cost <= 0) {       // the cut by time: at most `target` units before block padding (unless the length cap forces more)
         size_t live = 0; for (const MarchUnit &u : pl.units) live += u.ib > u.ia;
         if (target >= nwin && pl.chunk < max_len - 1 && (long)live > target) bad++;
@@ -223,6 +230,7 @@ int main()
         bad += check("long units", 16384, 256, 0, 16384, win, depth, 16, 0, 10);                    // cap-forced cuts
         bad += check("whole lattice, by columns", 4096, 4096, 0, 4096, win, depth, 4096, 0, 11, 0);
         bad += check("short window", 9, 300, 0, 9, win, depth, 2048, 0, 12);
+        for (int rows : {128, 120, 64}) bad += check("shortest units", 64, 262, 0, 64, rows, depth, 2048, 1, 18);      // (tiling, overlapping, fp64 windows)
         bad += check("whole lattice, by time, solo", 4096, 4096, 0, 4096, win, depth, 4096, 0, 13, 2);
         bad += check("middle slab, by time, solo", 544, 4096, 1760, 4096, win, depth, 2048, 0, 14, 2);
         bad += check("whole lattice, measured costs", 4096, 4096, 0, 4096, win, depth, 2048, 0, 15, 3);

@@ -188,6 +188,21 @@ LARGE = (1000, 646)
 SWITCH_NX, SWITCH_NY, SWITCH_FIRST, SWITCH_THEN = 320, (240, 480), 9, 10
 # f. three slabs cut by the caller
 SLAB_NX, SLAB_NY, SLAB_EDGES, SLAB_HALO, SLAB_CALLS = 150, 390, (0, 47, 101, 150), 13, (30, 17)
+# g. the shortest units: (NX, NY, fuse_chunk).  A cost limit of one column (every column costs one or more) makes the cut by columns close a unit
+# after every marched column, whatever the mask, except where that would leave a window's last unit — the one that also emits the outlet column —
+# shorter than a four-step pass allows (two columns): one marched column per unit at two and three steps per pass, at four steps one per unit and
+# two in the last.  tests/_march_plan_check.hip holds that of build_march_plan.  The lattice is SMALL[0]'s: the same references.
+SHORTEST = (64, 262, 1)
+
+
+def shortest_unit_count(nx, ny, depth, dtype, overlap):
+    """fuse_units of a SHORTEST plan without chain blocks: the marched columns 0 .. NX - 2 of every window, one unit each (four steps: the last
+    two columns in one); a plan of overlapping windows is dealt to the eight XCDs in whole workgroups of four units (padded with empty units)
+    once it holds 16 workgroups or more."""
+    rows = 64 if dtype == "float64" else (120 if overlap else 128)          # from window to window
+    live = -(-ny // rows) * (nx - 1 - (1 if depth == 4 else 0))
+    groups = -(-live // 4)
+    return 32 * -(-groups // 8) if overlap and groups >= 16 else live
 
 
 def case_small(nx, ny, mask, dtype):

@@ -269,3 +269,29 @@ def test_slabs(pkg, oracle_c, dtype, overlap, refresh):
                 e.close()
         wrong += _differ(("trim", trim), f, macro, ref_f, ref_m)
     assert not wrong, wrong
+
+
+# g. --------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mask_kind", rs.MASKS)
+def test_shortest_outlet_units(pkg, oracle_c, mask_kind):
+    """Solo units of the least length the planner allows (rs.SHORTEST): one marched column each at two and three steps per pass, at four steps
+    two in a window's last unit.  At three and four steps the loop of the unit that emits the outlet column then ends, by its `break`, before it
+    has stored a column of its own: what it stores is the pipeline's fill (dropped), and every column of the unit comes out of the outlet tail; at
+    two steps the loop stores the unit's one column in its last trip, just before the `break`.  Every other unit is all fill and drain."""
+    nx, ny, chunk = rs.SHORTEST
+    refs = {d: _ref(oracle_c, rs.case_small(nx, ny, mask_kind, d)) for d in rs.DTYPES}
+    wrong, ran = [], 0
+    for name, dtype, opts in _forms():
+        if "fuse_depth" not in opts or opts.get("chain", 0) != 0:
+            continue
+        f0, mask, ref_f, ref_m = refs[dtype]
+
+        def check(e):
+            want = rs.shortest_unit_count(nx, ny, opts["fuse_depth"], dtype, opts.get("window_overlap", 0))
+            assert e.get_option("fuse_units") == want, (name, e.get_option("fuse_units"), want)
+            assert e.get_option("chain_units") == 0, name
+        f, macro, _ = _march(pkg, rs.case_small(nx, ny, mask_kind, dtype), f0, mask, dict(opts, fuse_chunk=chunk, chain=0), check=check)
+        wrong += _differ(name, f, macro, ref_f, ref_m)
+        ran += 1
+    assert ran == 8                                     # fp32 tiling 2, 3, 4; overlapping 3, 4; fp64 2, 3, 4
+    assert not wrong, (mask_kind, wrong)

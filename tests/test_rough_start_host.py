@@ -74,6 +74,18 @@ def test_every_reference_is_sensitive(oracle_c, case):
     assert np.array_equal(rs._bits(f), rs._bits(ref_f))
 
 
+def test_shortest_units_share_the_small_references():
+    """test_shortest_outlet_units runs on the first lattice of SMALL: its references are checked above.  The unit counts it expects: 63 marched
+    columns in 3 windows of 128 or 120 rows or 5 of 64; at four steps 62 units per window; 189 and 186 units of overlapping windows are 48 and 47
+    workgroups, dealt to the XCDs as 8 x 6."""
+    nx, ny, chunk = rs.SHORTEST
+    assert (nx, ny) == rs.SMALL[0][:2] and chunk == 1
+    assert all(rs.case_small(nx, ny, m, d) in rs.ALL_CASES for m in rs.MASKS for d in rs.DTYPES)
+    assert [rs.shortest_unit_count(nx, ny, depth, "float32", 0) for depth in (2, 3, 4)] == [189, 189, 186]
+    assert [rs.shortest_unit_count(nx, ny, depth, "float32", 1) for depth in (3, 4)] == [192, 192]
+    assert [rs.shortest_unit_count(nx, ny, depth, "float64", 0) for depth in (2, 3, 4)] == [315, 315, 310]
+
+
 def test_two_part_reference_equals_the_whole_run(oracle_c):
     """reference(with_prev=True) runs the last step on its own: the same bits as one run (what the GPU file compares with)."""
     case = rs.case_small(64, 262, "body", "float32")

@@ -1,4 +1,9 @@
-"""Developer experiment: per-segment clocks of the lean three-step loop (library built with -DWT_M3_STAMPS into tools/ab/lib_stamps.so)."""
+"""Developer experiment: per-segment clocks of the lean solo loop (library built with -DWT_M3_STAMPS into tools/ab/lib_stamps.so).
+
+The stamps sit in march_unit (csrc/step_march3.hpp), whatever its depth, and EVERY lean solo unit of a launch adds to the same eight counters: run
+one depth at a time (set fuse_depth, and a step count that is a multiple of it, so that no left-over passes of another depth are mixed in).  Segment
+2 ends behind the level-2 stage, segment 3 behind the last stage: at four steps per pass segment 3 holds two stages, at two steps segment 2 is empty
+(the level-2 stage is the last).  The names below are those of a three-step pass."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
