@@ -459,8 +459,32 @@ __device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bo
 }
 
 // What a step kernel writes into a far-field cell (inlet column, top and bottom rows): the equilibrium of the axial free stream (U0, 0)
-// (the page's), or that of an inclined one (U0, V0) (include/wt_polar.h "Inclined free stream").
-enum : int { FAR_AXIAL = 0, FAR_INCLINED = 1 };
+// (the page's), that of an inclined one (U0, V0) (include/wt_polar.h "Inclined free stream"), or that of a prescribed (rho, ux, uy) per
+// cell (include/wt_polar.h "Prescribed far-field profile").
+enum : int { FAR_AXIAL = 0, FAR_INCLINED = 1, FAR_PROFILE = 2 };
+
+// One member's prescribed far-field profile on the device: three tables of three planes (rho, ux, uy) each.  `left` holds the cells
+// (0, j) and has the lattice's pitch between its planes, so that a lane's rows of an inlet tile are one aligned, in-bounds vector load
+// per plane; `bottom` and `top` hold the cells (i, 0) and (i, NY-1), `nxp` (NX rounded up) elements per plane, behind it.  A far-field
+// cell (i, j) takes left[.][j] if i == 0, else bottom[.][i] if j == 0, else top[.][i]: both corners of column 0 belong to `left`.
+template <typename T>
+struct FarProfile {
+    const T *tab = nullptr;      // the member's tables: left [3][pitch], bottom [3][nxp], top [3][nxp]
+    long pitch = 0;
+    long nxp = 0;
+    __device__ __forceinline__ const T *left() const { return tab; }
+    __device__ __forceinline__ const T *bottom() const { return tab + 3 * pitch; }
+    __device__ __forceinline__ const T *top() const { return tab + 3 * pitch + 3 * nxp; }
+    // (rho, ux, uy) of the far-field cell (i, j) of a lattice with `ny` rows
+    __device__ __forceinline__ void cell(int i, int j, T &rho, T &ux, T &uy) const
+    {
+        const T *e = i == 0 ? left() + j : ((j == 0 ? bottom() : top()) + i);
+        const long ps = i == 0 ? pitch : nxp;
+        rho = e[0]; ux = e[ps]; uy = e[2 * ps];
+    }
+};
+// Elements of one member's tables (before the rounding every per-member array gets).
+static inline long far_profile_elems(long pitch, long nxp) { return 3 * pitch + 6 * nxp; }
 
 // The stored element of a lattice and its Load / Store.  Native storage holds the arithmetic type itself; a half batch of libwtpolar holds
 // each population as the binary16 deviation from its lattice weight (the definition is polar.hip's "half-precision population storage").

@@ -40,7 +40,8 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // WALL selects what the interior branch does with a population whose source cell is solid: WALL_HALFWAY, or WALL_INTERP with the wall
 // distances `wq` (wall_incoming, d2q9.hpp): eight planes laid out like population planes 1..8, plane k - 1 holding q of direction k
 // at the link's fluid cell; `wq` points at column 0 of plane 0, as `s` does.  q is read only on lanes whose source cell is solid.
-// FAR selects what the far-field branch writes: FAR_AXIAL, feq(1, U0, 0), or FAR_INCLINED, feq(1, U0, V0) with the member's cross-flow `V0`.
+// FAR selects what the far-field branch writes: FAR_AXIAL, feq(1, U0, 0), FAR_INCLINED, feq(1, U0, V0) with the member's cross-flow `V0`, or
+// FAR_PROFILE, feq(rho, ux, uy) of the cell's entry in the member's tables `prof` (FarProfile, d2q9.hpp), which also become the stored moments.
 // S is the stored element of the lattices `s` and `d`: every population read goes through lat_load and every one written through
 // lat_store (d2q9.hpp), the identity for native storage (S = T) and Load / Store for a half batch (S = half_t, T = float).  The
 // macroscopic planes hold T.  Interpolated walls exist for native storage only.
@@ -49,7 +50,7 @@ template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR =
 __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
                                              T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr, T V0 = T(0.0),
-                                             T lam = T(0.0))
+                                             T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>())
 {
     const long c = (long)i * g.pitch + j;
     const int gi = i + g.gi0;
@@ -68,9 +69,12 @@ __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restr
 #pragma unroll
         for (int k = 0; k < 9; k++) out[k] = q[k];
     } else if (gi == 0 || j == g.ny - 1 || j == 0) {               // html:314-322 far field
-        rho = T(1.0); ux = U0;
-        if constexpr (FAR == FAR_INCLINED) uy = V0;
-        else uy = T(0.0);
+        if constexpr (FAR == FAR_PROFILE) prof.cell(gi, j, rho, ux, uy);
+        else {
+            rho = T(1.0); ux = U0;
+            if constexpr (FAR == FAR_INCLINED) uy = V0;
+            else uy = T(0.0);
+        }
         feq_all(rho, ux, uy, out);
     } else {                                                       // html:324-359 interior fluid
         T fin[9];

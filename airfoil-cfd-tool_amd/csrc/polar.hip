@@ -54,6 +54,12 @@
 // tau that is not above 0.5 in the batch's dtype.  A batch that has it off launches the kernels it always launched, with the arguments
 // they always had.
 //
+// The prescribed far-field profile (wtp_enable_far_profile) is a third far field: while it is on, wtp_step launches
+// k_step_profile_batch, the same step_tile with feq(rho, ux, uy) of the cell's entry in the member's tables in its far-field cells, with
+// every collision and either wall rule.  wtp_set_far_profile checks the tables on the host and uploads them; wtp_step refuses to run
+// while a member has none.  Native storage only.  A batch that has it off launches the kernels it always launched, with the arguments
+// they always had.
+//
 // Every variant above is a kernel of its own name and code object, so that a batch runs the one its switches select and no other.
 // What the variants share is source text: one site (site_general, kernels.hpp, for every storage), one momentum-exchange body
 // (mex_member, with a link rule per wall rule), one prologue of the tiled step kernels (MemberTile), one stepping loop on the host.
@@ -160,6 +166,12 @@ struct wtp_batch {
     bool trt = false;
     void *trt_lam = nullptr;             // [B] of T: the magic number of every member
     void *zero_v = nullptr;              // [B] of T, all zero: the cross-flow its kernels read while the free stream is axial
+    // prescribed far-field profile (wtp_enable_far_profile); the pointer is null until then
+    bool profile = false;
+    void *prof = nullptr;                // [B] tables of T (FarProfile, d2q9.hpp), members p_stride elements apart
+    long p_stride = 0;
+    int p_nxp = 0;                       // elements per plane of `bottom` and `top`: NX rounded up to 64
+    std::vector<uint8_t> prof_set;       // [B]: the member has been given a profile (wtp_set_far_profile)
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -337,6 +349,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(trt_waves<T
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
                                                                   tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
                                                                   c, q, V0, magic);
+}
+
+// The same step with a prescribed far-field profile (include/wt_polar.h "Prescribed far-field profile"), with every collision (COLLIDE_BGK,
+// COLLIDE_LES, COLLIDE_TRT, COLLIDE_TRT_LES) and either wall rule: k_step_trt_batch's grid, walk and arguments, without the cross-flow,
+// which no cell reads, and with the members' tables `prof` (FarProfile, d2q9.hpp; pstride elements apart, nxp elements per plane of
+// `bottom` and `top`).  A far-field cell (not solid, not in the outlet column, in column 0, row 0 or row NY-1) writes feq_k(rho, ux, uy)
+// of its entry and stores (rho, ux, uy); U0 is not read by such a cell.  The branch order does not change, and nothing else in the step
+// changes.  A profile that holds (1, U0, V0) in every entry gives k_step_wind_batch's bits.  cles is read only with the Smagorinsky
+// model, lam only for the two-relaxation-time collisions, wq only for WALL_INTERP.  A kernel of its own name, so that a batch with the
+// model off runs the code object it always ran.
+// Waves per SIMD, from the compiler's resource report as for wind_waves (profiles/polar_profile_isa.txt): every kernel asks for what its
+// FAR_INCLINED twin asks for, wind_waves for the single-relaxation-time collisions and trt_waves for the others, and allocates 79 to 94
+// VGPRs in fp32 and 93 to 111 in fp64 without scratch.  One exception: the plain non-emitting fp32 kernel with interpolated walls, asked
+// for its twin's 6 waves, got 79 VGPRs and 12 bytes of scratch per lane where the twin has none, so it asks for 5.  The entry of a FAST
+// tile's far row is loaded behind the collision, so it adds no live register to it.
+template <typename T, bool EMIT, int COLL, int WALL>
+constexpr int profile_waves()
+{
+    if (coll_is_trt(COLL)) return trt_waves<T>();
+    const int w = wind_waves<T, EMIT, COLL>();
+    return WALL == WALL_INTERP && w > 5 ? 5 : w;
+}
+
+template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(profile_waves<T, EMIT, COLL, WALL>()))) void k_step_profile_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
+                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
+                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
+                                                         const T *__restrict__ lam, const T *__restrict__ prof, long pstride, int nxp, int rev)
+{
+    const int lane = threadIdx.x & 63;
+    const MemberTile w(g, tiles_per_col, rev);
+    if (!w.live()) return;
+    const long m = w.member();
+    const T tau = params[2 * m], U0 = params[2 * m + 1];
+    T c = T(0.0), magic = T(0.0);
+    if constexpr (coll_has_les(COLL)) c = cles[m];
+    if constexpr (coll_is_trt(COLL)) magic = lam[m];
+    const T *q = nullptr;
+    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
+    FarProfile<T> fp;
+    fp.tab = prof + m * pstride; fp.pitch = g.pitch; fp.nxp = nxp;
+    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_PROFILE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                                 tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
+                                                                 c, q, T(0.0), magic, fp);
 }
 
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
@@ -867,7 +924,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -956,7 +1013,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1276,6 +1333,19 @@ static auto trt_half_kernel(bool emit)
     return emit ? k_step_trt_half_batch<true, COLL> : k_step_trt_half_batch<false, COLL>;
 }
 
+// k_step_profile_batch of one collision and one wall rule, emitting or not.
+template <typename T, int COLL, int WALL>
+static auto profile_kernel(bool emit)
+{
+    return emit ? k_step_profile_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_profile_batch<T, false, WT_LOADMODE, COLL, WALL>;
+}
+template <typename T, int WALL>
+static auto profile_kernel(bool trt, bool les, bool emit)
+{
+    return trt ? (les ? profile_kernel<T, COLLIDE_TRT_LES, WALL>(emit) : profile_kernel<T, COLLIDE_TRT, WALL>(emit))
+               : (les ? profile_kernel<T, COLLIDE_LES, WALL>(emit) : profile_kernel<T, COLLIDE_BGK, WALL>(emit));
+}
+
 // The cross-flow array of the two-relaxation-time kernels: the members' V0, or zeros while the free stream is axial.
 static const void *trt_cross_flow(const wtp_batch *b) { return b->wind ? b->wind_v : b->zero_v; }
 
@@ -1329,7 +1399,12 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
     return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
         const T *fs = fptr<T>(b, b->cur, 0);
         T *fd = fptr<T>(b, 1 - b->cur, 0);
-        if (b->trt) {
+        if (b->profile) {
+            const auto k_step = b->ibb ? profile_kernel<T, WALL_INTERP>(b->trt, b->les, emit) : profile_kernel<T, WALL_HALFWAY>(b->trt, b->les, emit);
+            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
+                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
+                               (const T *)b->trt_lam, (const T *)b->prof, b->p_stride, b->p_nxp, rev);
+        } else if (b->trt) {
             const auto k_step = b->ibb ? (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_INTERP>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_INTERP>(emit))
                                        : (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_HALFWAY>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_HALFWAY>(emit));
             hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
@@ -1373,6 +1448,9 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
             if (!(b->dtype == WT_F32 ? (float)tau[m] > 0.5f : tau[m] > 0.5))
                 return fail(WT_ERR_ARG, "tau[%d] must be above 0.5 in the batch's dtype while the two-relaxation-time collision is on", m);
     WT_TRY(check_ready(b));
+    if (b->profile)
+        for (int m = 0; m < b->members; m++)
+            if (!b->prof_set[(size_t)m]) return fail(WT_ERR_STATE, "member %d has no far-field profile (wtp_set_far_profile)", m);
     if (sample_every > 0) {
         const long long samples = (b->steps_done + nsteps) / sample_every - b->steps_done / sample_every;
         if ((long long)b->h_step.size() + samples > b->cap)
@@ -1455,6 +1533,86 @@ extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
     b->wind_host.assign(v0, v0 + b->members);
     b->wind = true;
     return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// prescribed far-field profile
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_far_profile(wtp_batch *b, int on)
+{
+    WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    if (!on) { b->profile = false; return WT_OK; }       // (steps already enqueued were launched with the model on: stream order)
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->prof) {
+        const int nxp = (b->nx + 63) / 64 * 64;
+        const long stride = member_stride((size_t)far_profile_elems(b->g.pitch, nxp) * b->esz, b->esz);
+        const size_t bytes = (size_t)b->members * stride * b->esz;
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // (the batch goes on with its uniform far field: later launches must not see this error)
+            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the far-field tables (%zu bytes) could not be allocated: %s", bytes,
+                        hipGetErrorString(e));
+        }
+        e = hipMemsetAsync(p, 0, bytes, b->st);  // (the entries no cell reads, rows past NY and columns past NX, hold +0)
+        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
+        b->prof = p; b->p_stride = stride; b->p_nxp = nxp;
+        b->prof_set.assign((size_t)b->members, 0);
+    }
+    b->profile = true;
+    return WT_OK;
+}
+
+// One entry of a table: finite, rho in [0.5, 2], ux^2 + uy^2 <= 0.35^2 (the bounds of the stability net).  False for a NaN.
+static bool far_entry_ok(double rho, double ux, double uy)
+{
+    return rho >= 0.5 && rho <= 2.0 && std::isfinite(ux) && std::isfinite(uy) && ux * ux + uy * uy <= 0.35 * 0.35;
+}
+
+template <typename T>
+static int set_far_profile_impl(wtp_batch *b, int first, int count, const T *left, const T *bottom, const T *top)
+{
+    const size_t nx = (size_t)b->nx, ny = (size_t)b->ny;
+    const struct { const T *v; size_t n; const char *name; } tabs[3] = {{left, ny, "left"}, {bottom, nx, "bottom"}, {top, nx, "top"}};
+    for (const auto &t : tabs)
+        for (size_t k = 0; k < (size_t)count; k++)
+            for (size_t e = 0; e < t.n; e++) {
+                const T *p = t.v + k * 3 * t.n + e;
+                if (!far_entry_ok((double)p[0], (double)p[t.n], (double)p[2 * t.n]))
+                    return fail(WT_ERR_ARG, "entry %zu of `%s` of member %d is not finite with rho in [0.5, 2] and a speed of at most 0.35", e, t.name,
+                                first + (int)k);
+            }
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t pitch = (size_t)b->g.pitch, nxp = (size_t)b->p_nxp, elems = (size_t)far_profile_elems(b->g.pitch, b->p_nxp);
+    std::vector<T> host(elems * (size_t)count, T(0.0));          // the device layout of FarProfile, members packed
+    for (size_t k = 0; k < (size_t)count; k++) {
+        T *d = host.data() + k * elems;
+        for (size_t p = 0; p < 3; p++) {
+            std::memcpy(d + p * pitch, left + (k * 3 + p) * ny, ny * sizeof(T));
+            std::memcpy(d + 3 * pitch + p * nxp, bottom + (k * 3 + p) * nx, nx * sizeof(T));
+            std::memcpy(d + 3 * pitch + (3 + p) * nxp, top + (k * 3 + p) * nx, nx * sizeof(T));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(b->st));        // steps already enqueued read the previous values
+    for (size_t k = 0; k < (size_t)count; k++) {
+        HIP_TRY(hipMemcpy(reinterpret_cast<T *>(b->prof) + (long)(first + (int)k) * b->p_stride, host.data() + k * elems, elems * sizeof(T),
+                          hipMemcpyHostToDevice));
+        b->prof_set[(size_t)first + k] = 1;
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_set_far_profile(wtp_batch *b, int first, int count, const void *left, const void *bottom, const void *top)
+{
+    WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    if (!left || !bottom || !top) return fail(WT_ERR_ARG, "left, bottom or top is null");
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    if (!b->prof) return fail(WT_ERR_STATE, "the far-field profile has never been enabled (wtp_enable_far_profile)");
+    return b->dtype == WT_F32 ? set_far_profile_impl<float>(b, first, count, (const float *)left, (const float *)bottom, (const float *)top)
+                              : set_far_profile_impl<double>(b, first, count, (const double *)left, (const double *)bottom, (const double *)top);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -155,23 +155,27 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // WIN: the tile belongs to a grid whose tiles start every `stride` rows (tile height stays 64*N) and
 // only rows in [st_lo, st_hi) are stored — the window-aligned zone passes of step_fused.hpp.
 // COLL: the collision of interior fluid cells, COLLIDE_BGK, COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp), or COLLIDE_TRT /
-// COLLIDE_TRT_LES with the magic number `lam` (collide_trt); the two-relaxation-time kernels always come with FAR_INCLINED.
+// COLLIDE_TRT_LES with the magic number `lam` (collide_trt); the two-relaxation-time kernels never come with FAR_AXIAL.
 // WALL: the wall rule of interior fluid cells, WALL_HALFWAY or WALL_INTERP with the wall distances `wq`, eight planes laid out like
 // population planes 1..8, pad column included (wall_incoming, d2q9.hpp).  Only TILE_GENERAL tiles can own a link: no other path reads them.
-// FAR: what a far-field cell holds, FAR_AXIAL (feq(1, U0, 0)) or FAR_INCLINED with the cross-flow `V0` (feq(1, U0, V0)); the three places
-// that form the far field take it: site_general, the top and bottom rows of a TILE_FAST tile, and TILE_INLET.
+// FAR: what a far-field cell holds, FAR_AXIAL (feq(1, U0, 0)), FAR_INCLINED with the cross-flow `V0` (feq(1, U0, V0)) or FAR_PROFILE with
+// the member's tables `prof` (feq(rho, ux, uy) of the cell's entry); the three places that form the far field take it: site_general,
+// the top and bottom rows of a TILE_FAST tile, and TILE_INLET.  With FAR_PROFILE a TILE_FAST tile collides all its rows and then, on the
+// one lane that holds row 0 (lane 0 of the column's first tile) or row NY-1 (lane 63 of a tile that ends at NY), replaces that row by
+// the equilibrium of bottom[.][i] or top[.][i]: two lanes of a column at most, behind the collision, so that the entry and its nine
+// values are not live across it.  A TILE_INLET lane loads its rows of `left` with one aligned vector load per plane.
 template <typename T, bool EMIT, int LOADMODE, bool WIN = false, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR = FAR_AXIAL>
 __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
                                           int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr,
-                                          T V0 = T(0.0), T lam = T(0.0))
+                                          T V0 = T(0.0), T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>())
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
     constexpr bool NT = (LOADMODE & 1) != 0;
     constexpr bool UNALIGNED = (LOADMODE & 2) != 0;
-    static_assert(!coll_is_trt(COLL) || FAR == FAR_INCLINED, "the two-relaxation-time kernels take the inclined far field");
+    static_assert(!coll_is_trt(COLL) || FAR != FAR_AXIAL, "the two-relaxation-time kernels do not come with the axial far field");
     const int i = i_begin + (int)(tile_local / tiles_per_col);
     const int jt = (int)(tile_local % tiles_per_col);
     const int row0 = WIN ? jt * stride : jt * TJ;
@@ -187,7 +191,9 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
         for (int v = 0; v < N; v++) {
             const int j = row0 + v * 64 + lane;
             if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) {
-                if constexpr (FAR == FAR_INCLINED)
+                if constexpr (FAR == FAR_PROFILE)
+                    site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0, lam, prof);
+                else if constexpr (FAR == FAR_INCLINED)
                     site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0, lam);
                 else if constexpr (WALL == WALL_INTERP) site_general<T, COLL, WALL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch);
                 else site_general<T, COLL>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles);
@@ -224,7 +230,7 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
         }
         T feq0[9];
         if constexpr (FAR == FAR_INCLINED) feq_all<T>(T(1.0), U0, V0, feq0);
-        else feq_all<T>(T(1.0), U0, T(0.0), feq0);      // far-field populations (html:314-322)
+        else if constexpr (FAR == FAR_AXIAL) feq_all<T>(T(1.0), U0, T(0.0), feq0);      // far-field populations (html:314-322)
 #pragma unroll
         for (int v = 0; v < N; v++) {
             T a[9], o[9], rho, ux, uy;
@@ -233,14 +239,39 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
             if constexpr (coll_is_trt(COLL)) collide_trt<T, COLL == COLLIDE_TRT_LES>(a, tau, lam, cles, o, rho, ux, uy);
             else if constexpr (COLL == COLLIDE_LES) collide_les<T>(a, tau, cles, o, rho, ux, uy);
             else collide<T>(a, tau, o, rho, ux, uy);
-            const int j = j0 + v;
-            const bool far = (j == 0) || (j == g.ny - 1);   // top / bottom rows
+            if constexpr (FAR == FAR_PROFILE) {
 #pragma unroll
-            for (int k = 0; k < 9; k++) out[k].v[v] = far ? feq0[k] : o[k];
-            mrho.v[v] = far ? T(1.0) : rho;
-            mux.v[v] = far ? U0 : ux;
-            if constexpr (FAR == FAR_INCLINED) muy.v[v] = far ? V0 : uy;
-            else muy.v[v] = far ? T(0.0) : uy;
+                for (int k = 0; k < 9; k++) out[k].v[v] = o[k];
+                mrho.v[v] = rho; mux.v[v] = ux; muy.v[v] = uy;
+            } else {
+                const int j = j0 + v;
+                const bool far = (j == 0) || (j == g.ny - 1);   // top / bottom rows
+#pragma unroll
+                for (int k = 0; k < 9; k++) out[k].v[v] = far ? feq0[k] : o[k];
+                mrho.v[v] = far ? T(1.0) : rho;
+                mux.v[v] = far ? U0 : ux;
+                if constexpr (FAR == FAR_INCLINED) muy.v[v] = far ? V0 : uy;
+                else muy.v[v] = far ? T(0.0) : uy;
+            }
+        }
+        if constexpr (FAR == FAR_PROFILE) {
+            // (a FAST tile is never column 0, is whole, and is at least 128 rows tall: row 0 is lane 0's first row, row NY-1 lane 63's last)
+            if (j0 == 0) {
+                T rho, ux, uy;
+                prof.cell(i, 0, rho, ux, uy);
+                feq_all<T>(rho, ux, uy, feq0);
+#pragma unroll
+                for (int k = 0; k < 9; k++) out[k].v[0] = feq0[k];
+                mrho.v[0] = rho; mux.v[0] = ux; muy.v[0] = uy;
+            }
+            if (j0 + N == g.ny) {
+                T rho, ux, uy;
+                prof.cell(i, g.ny - 1, rho, ux, uy);
+                feq_all<T>(rho, ux, uy, feq0);
+#pragma unroll
+                for (int k = 0; k < 9; k++) out[k].v[N - 1] = feq0[k];
+                mrho.v[N - 1] = rho; mux.v[N - 1] = ux; muy.v[N - 1] = uy;
+            }
         }
     } else if (cls == TILE_SOLID) {
 #pragma unroll
@@ -248,18 +279,32 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
 #pragma unroll
         for (int v = 0; v < N; v++) { mrho.v[v] = T(1.0); mux.v[v] = T(0.0); muy.v[v] = T(0.0); }
     } else if (cls == TILE_INLET) {
-        T feq0[9];
-        if constexpr (FAR == FAR_INCLINED) feq_all<T>(T(1.0), U0, V0, feq0);
-        else feq_all<T>(T(1.0), U0, T(0.0), feq0);
+        if constexpr (FAR == FAR_PROFILE) {
+            // (an inlet tile is column 0 and whole: its rows are rows j0 .. j0 + N - 1 of `left`, 16-byte aligned like the lattice's)
+            mrho = vload<T>(prof.left() + j0);
+            mux = vload<T>(prof.left() + prof.pitch + j0);
+            muy = vload<T>(prof.left() + 2 * prof.pitch + j0);
 #pragma unroll
-        for (int k = 0; k < 9; k++)
+            for (int v = 0; v < N; v++) {
+                T e[9];
+                feq_all<T>(mrho.v[v], mux.v[v], muy.v[v], e);
 #pragma unroll
-            for (int v = 0; v < N; v++) out[k].v[v] = feq0[k];
+                for (int k = 0; k < 9; k++) out[k].v[v] = e[k];
+            }
+        } else {
+            T feq0[9];
+            if constexpr (FAR == FAR_INCLINED) feq_all<T>(T(1.0), U0, V0, feq0);
+            else feq_all<T>(T(1.0), U0, T(0.0), feq0);
 #pragma unroll
-        for (int v = 0; v < N; v++) {
-            mrho.v[v] = T(1.0); mux.v[v] = U0;
-            if constexpr (FAR == FAR_INCLINED) muy.v[v] = V0;
-            else muy.v[v] = T(0.0);
+            for (int k = 0; k < 9; k++)
+#pragma unroll
+                for (int v = 0; v < N; v++) out[k].v[v] = feq0[k];
+#pragma unroll
+            for (int v = 0; v < N; v++) {
+                mrho.v[v] = T(1.0); mux.v[v] = U0;
+                if constexpr (FAR == FAR_INCLINED) muy.v[v] = V0;
+                else muy.v[v] = T(0.0);
+            }
         }
     } else {   // TILE_OUTLET: copy the un-streamed populations of column i-1 (html:301-312)
 #pragma unroll

@@ -22,6 +22,9 @@ A sweep can be continued without a second warm-up: ``PolarEngine.state`` / ``res
 ``set_step_count``) and ``run_polar(keep_state=True)`` followed by ``run_polar(start=result.state)``.
 With the two-relaxation-time collision (``PolarEngine.enable_trt``, ``run_polar(collision="trt")``) the effective position of a
 half-way wall is set by a magic number and not by tau, so a body keeps its thickness when the Reynolds number of a sweep changes.
+With a prescribed far-field profile (``PolarEngine.enable_far_profile`` / ``set_far_profile``) every far-field cell holds the
+equilibrium of its own (rho, ux, uy); ``run_polar(far_field="vortex")`` uses it for the textbook far-field correction of airfoil
+computations, the free stream plus a point vortex that follows the lift (:func:`far_profile`, :func:`vortex_update`).
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -57,6 +60,7 @@ EXPORTS = (
     "wtp_create_stored", "wtp_read_stored",
     "wtp_write_f", "wtp_write_stored", "wtp_step_count", "wtp_set_step_count",
     "wtp_enable_trt",
+    "wtp_enable_far_profile", "wtp_set_far_profile",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
@@ -64,6 +68,8 @@ WALLS = ("staircase", "interpolated")                              # run_polar's
 STORAGES = ("native", "half")                                      # how a batch stores its populations: in its dtype, or as binary16 deviations from the weights
 COLLISIONS = ("bgk", "trt")                                        # run_polar's collisions: single relaxation time, or two with a magic number
 MAGIC_DEFAULT = 3 / 16                                             # the magic number at which a half-way wall of a Poiseuille flow sits half-way at every tau
+FAR_FIELDS = ("uniform", "vortex", "vortex+source")                 # run_polar's far fields: the free stream alone, plus a point vortex from the lift, plus a source from the drag
+VORTEX_SPEED_MAX = 0.1                                             # the largest speed the vortex and the source together may induce at the nearest far-field cell centre
 FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
 WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
@@ -122,6 +128,8 @@ def load_polar_library(path: str = POLAR_LIB_PATH, optional: Sequence[str] = ())
         "wtp_step_count": ([B, ip], c_int),
         "wtp_set_step_count": ([B, c_int64], c_int),
         "wtp_enable_trt": ([B, dp], c_int),
+        "wtp_enable_far_profile": ([B, c_int], c_int),
+        "wtp_set_far_profile": ([B, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         if name in optional and path != POLAR_LIB_PATH and not hasattr(lib, name):
@@ -200,6 +208,8 @@ class PolarEngine:
         self.interpolated_walls = False
         self._wind = False
         self._trt = False
+        self._far_profile = False
+        self._far_tables = None      # the tables last given to every member, (left [B][3][NY], bottom [B][3][NX], top [B][3][NX]), and which members have some
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         if storage == "half":
             _check(self._lib.wtp_create_stored(self.nx, self.ny, code, WTP_STORE_HALF, self.members, self.history_cap, int(device),
@@ -394,6 +404,44 @@ class PolarEngine:
     def trt_enabled(self) -> bool:
         return self._trt
 
+    def enable_far_profile(self, on: bool = True) -> None:
+        """Hold every far-field cell at the equilibrium of its own (rho, ux, uy) from the next step on (wt_polar.h "Prescribed
+        far-field profile"); set_far_profile gives the tables, and step raises WTError (WT_ERR_STATE) while a member has none.
+        on=False switches back to the uniform far field and its bits and keeps the tables.  u0 of step and v0 of enable_wind are
+        then not read by far-field cells; they still set the start state.  WTError (WT_ERR_STATE) on a storage="half" batch.  The
+        flow state, the history, every running sum and every other enable_* setting are kept; combines with enable_les,
+        enable_interpolated_walls, enable_trt and enable_wind, independent of the read-outs."""
+        _check(self._lib.wtp_enable_far_profile(self._b, 1 if on else 0))
+        self._far_profile = bool(on)
+        if self._far_tables is None:
+            B = self.members
+            self._far_tables = (np.zeros((B, 3, self.ny), self.dtype), np.zeros((B, 3, self.nx), self.dtype),
+                                np.zeros((B, 3, self.nx), self.dtype), np.zeros(B, bool))
+
+    @property
+    def far_profile_enabled(self) -> bool:
+        return self._far_profile
+
+    def set_far_profile(self, left, bottom, top, first: int = 0) -> None:
+        """The tables of members first .. first+count-1: left [count][3][NY] for the cells (0, j), bottom and top [count][3][NX] for
+        the cells (i, 0) and (i, NY-1) (or one member's [3][NY], [3][NX], [3][NX]), planes rho, ux, uy, converted to the batch's
+        dtype.  The corners of column 0 are `left`'s; entries 0 and NX-1 of bottom and top are never read.  Every value finite, rho
+        in [0.5, 2], ux^2 + uy^2 <= 0.35^2, else WTError (WT_ERR_ARG) and the batch is left as it was.  After enable_far_profile.
+        Steps already enqueued see the old tables."""
+        tabs = []
+        for a, n, what in ((left, self.ny, "left"), (bottom, self.nx, "bottom"), (top, self.nx, "top")):
+            a = np.ascontiguousarray(a, dtype=self.dtype)
+            if a.ndim == 2:
+                a = a[None]
+            if a.ndim != 3 or a.shape[1:] != (3, n) or a.shape[0] != (tabs[0].shape[0] if tabs else a.shape[0]):
+                raise ValueError(f"{what} must have shape [count][3][{n}], got {a.shape}")
+            tabs.append(a)
+        count = int(tabs[0].shape[0])
+        _check(self._lib.wtp_set_far_profile(self._b, int(first), count, *(t.ctypes.data_as(c_void_p) for t in tabs)))
+        for held, t in zip(self._far_tables, tabs):
+            held[first:first + count] = t
+        self._far_tables[3][first:first + count] = True
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -451,22 +499,31 @@ class PolarEngine:
     def state(self) -> Dict[str, object]:
         """What a restart needs: nx, ny, dtype (its name), storage, members, steps (the step count) and f [B][9][NY][NX], the
         populations of every member: read_f's values on a native batch, read_stored's raw uint16 halves on a storage="half" batch.
+        With a far-field profile on and given to every member, also far_profile: {"left", "bottom", "top"}, the tables in use.
         Not in it: the history, the running sums (surface, mean fields), the masks, the wall distances and the enable_* settings."""
         read = self.read_stored if self.storage == "half" else self.read_f
-        return {"nx": self.nx, "ny": self.ny, "dtype": self.dtype.name, "storage": self.storage, "members": self.members,
-                "steps": self.step_count, "f": np.stack([read(m) for m in range(self.members)])}
+        state = {"nx": self.nx, "ny": self.ny, "dtype": self.dtype.name, "storage": self.storage, "members": self.members,
+                 "steps": self.step_count, "f": np.stack([read(m) for m in range(self.members)])}
+        if self._far_profile and self._far_tables[3].all():
+            state["far_profile"] = {k: t.copy() for k, t in zip(("left", "bottom", "top"), self._far_tables)}
+        return state
 
     def restore(self, state) -> None:
         """Write every member's populations from a state() and set its step count.  ValueError where the state's nx, ny, dtype,
         storage or members are not the engine's.  Call init_equilibrium first: it is what gives the pad columns and the lattice
         that is not written defined contents, and it clears the history, so that the restored count cannot fall below a row held.
         Masks, wall distances and enable_* settings are the caller's to set as they were; the running sums start empty and the
-        macroscopic planes are valid again after the first step."""
+        macroscopic planes are valid again after the first step.  A state that carries far_profile tables switches the far-field
+        profile on and puts them back."""
         _check_state(state, self.nx, self.ny, self.dtype, self.storage, self.members)
         write = self.write_stored if self.storage == "half" else self.write_f
         for m in range(self.members):
             write(m, state["f"][m])
         self.set_step_count(state["steps"])
+        tables = state.get("far_profile")
+        if tables is not None:                   # a state taken with a far-field profile on: the model on again, with the state's tables
+            self.enable_far_profile()
+            self.set_far_profile(tables["left"], tables["bottom"], tables["top"])
 
     def read_macro(self, member: int):
         rho, ux, uy = (np.empty((self.ny, self.nx), dtype=self.dtype) for _ in range(3))
@@ -508,6 +565,10 @@ class PolarPoint:
     cm_total_std: InitVar[Optional[float]] = None
     cd_friction_mean: InitVar[Optional[float]] = None      # cd_total_mean - cd_mean
     mean: InitVar[Optional[Dict[str, object]]] = None      # mean_flow() of this angle (None: not sampled); init-only like the totals
+    # The last strengths of the far-field vortex and source of a run_polar(far_field="vortex" / "vortex+source") sweep (None: uniform far field).
+    # Plain attributes that run_polar sets: no fields and no constructor arguments, so that the constructor ends with `mean` as it did.
+    vortex_strength = None
+    vortex_source = None
 
     def __post_init__(self, cl_total_mean, cl_total_std, cd_total_mean, cd_total_std, cm_total_mean, cm_total_std, cd_friction_mean,
                       mean):
@@ -544,8 +605,14 @@ class PolarResult:
     # The collision of the sweep, "bgk" or "trt", and the magic number of a "trt" sweep (None for "bgk").  Init-only too.
     collision: InitVar[str] = "bgk"
     magic: InitVar[Optional[float]] = None
+    # The far field of the sweep, "uniform", "vortex" or "vortex+source", and for the latter two one entry per update of the strengths: step [U], fx, fy
+    # (lattice axes), strength, source [U][B] float64 and clipped [U][B] bool (None for "uniform").  Init-only too.
+    far_field: InitVar[str] = "uniform"
+    vortex_history: InitVar[Optional[Dict[str, np.ndarray]]] = None
 
-    def __post_init__(self, walls, frame, storage, state, collision, magic):
+    def __post_init__(self, walls, frame, storage, state, collision, magic, far_field="uniform", vortex_history=None):
+        self.far_field = far_field
+        self.vortex_history = vortex_history
         self.walls = walls
         self.frame = frame
         self.storage = storage
@@ -667,12 +734,62 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
                       surface=surface, **total)
 
 
+# ---- the far-field correction ------------------------------------------------------------------
+def far_profile(nx: int, ny: int, u0: float, v0: float, strength: float, source: float, xc: float, yc: float, dtype="float32"):
+    """The tables (left [3][NY], bottom [3][NX], top [3][NX]; planes rho, ux, uy) of PolarEngine.set_far_profile for the free stream
+    (u0, v0) plus a point vortex and a point source at (xc, yc), lattice units.  All arithmetic in float64, each value rounded to
+    `dtype` once.  For a cell centre (i + 0.5, j + 0.5):
+        dx = i + 0.5 - xc, dy = j + 0.5 - yc, r2 = dx*dx + dy*dy
+        ux = u0 + strength*dy/r2 + source*dx/r2
+        uy = v0 - strength*dx/r2 + source*dy/r2
+        rho = 1 + 1.5*((u0*u0 + v0*v0) - (ux*ux + uy*uy))          (Bernoulli with p = rho/3)
+    `strength` is the clockwise circulation over 2 pi, positive for positive lift with the flow in +x; `source` is the volume flux
+    over 2 pi.  With both zero every entry is (1, u0, v0) exactly."""
+    u0, v0, strength, source, xc, yc = (float(v) for v in (u0, v0, strength, source, xc, yc))
+
+    def table(i, j):
+        dx, dy = i + 0.5 - xc, j + 0.5 - yc
+        r2 = dx * dx + dy * dy
+        ux = u0 + strength * dy / r2 + source * dx / r2
+        uy = v0 - strength * dx / r2 + source * dy / r2
+        rho = 1 + 1.5 * ((u0 * u0 + v0 * v0) - (ux * ux + uy * uy))
+        return np.stack([rho, ux, uy]).astype(_np_dtype(dtype))
+
+    i, j = np.arange(int(nx), dtype=np.float64), np.arange(int(ny), dtype=np.float64)
+    return table(np.zeros_like(j), j), table(i, np.zeros_like(i)), table(i, np.full_like(i, ny - 1))
+
+
+def vortex_bound(nx: int, ny: int, xc: float, yc: float) -> float:
+    """The distance from (xc, yc) to the nearest far-field cell centre: min(xc - 0.5, yc - 0.5, NY - 0.5 - yc)."""
+    return min(xc - 0.5, yc - 0.5, ny - 0.5 - yc)
+
+
+def vortex_update(strength, source, fx, fy, alpha, u0: float, relax: float, bound: float, with_source: bool = True):
+    """The update rule of the far-field vortex and source, elementwise over the members; pure.  D, L = wind_axes(fx, fy, alpha), the
+    drag and the lift in lattice units.  The targets are L/(2 pi u0) for the strength (Kutta-Joukowski with rho = 1) and D/(2 pi u0)
+    for the source (0 when with_source is false); new = old + relax*(target - old).  Then both are scaled by one factor, where
+    needed, so that the speed they induce together at the nearest far-field cell centre, hypot(strength, source)/bound, stays at
+    most VORTEX_SPEED_MAX = 0.1: this keeps every profile inside set_far_profile's limits for u0 <= 0.25.
+    Returns (strength, source, clipped): float64, float64, bool."""
+    old_s, old_q = np.asarray(strength, np.float64), np.asarray(source, np.float64)
+    drag, lift = wind_axes(fx, fy, alpha)
+    tgt_s = lift / (2 * math.pi * u0)
+    tgt_q = drag / (2 * math.pi * u0) if with_source else np.zeros_like(tgt_s)
+    new_s = old_s + relax * (tgt_s - old_s)
+    new_q = old_q + relax * (tgt_q - old_q)
+    speed = np.hypot(new_s, new_q) / bound
+    clipped = speed > VORTEX_SPEED_MAX
+    scale = np.where(clipped, VORTEX_SPEED_MAX / np.where(clipped, speed, 1.0), 1.0)
+    return new_s * scale, new_q * scale, clipped
+
+
 # ---- the sweep -------------------------------------------------------------------------------
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
               total_forces: bool = False, mean_fields: bool = False, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
               collision: str = "bgk", magic: float = MAGIC_DEFAULT,
+              far_field: str = "uniform", vortex_every: int = 96, vortex_relax: float = 0.3, vortex_after: Optional[int] = None,
               storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
@@ -724,7 +841,24 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     is with `re`.  It needs a tau above 0.5 in `dtype` and combines with `les`, `walls`, `frame`, `storage` and `start`.  What it
     does to CL and CD was measured, not assumed: README, profiles/polar_trt_sweep.txt.  PolarResult.collision and .magic say what ran
     (magic is None for "bgk").  An unknown collision, a magic outside (0, 1] or "trt" with such a tau raises ValueError before an
-    engine is created."""
+    engine is created.
+    `far_field`: "uniform", the default, holds every far-field cell (inlet column, top and bottom rows) at the free stream, with the
+    code path and the bits it always had.  Those rows lie 0.46 chords from the body and act like the walls of a closed tunnel.
+    "vortex" prescribes there the free stream plus the velocity of a point vortex at the quarter chord whose circulation follows
+    the current lift (Kutta-Joukowski), the textbook far-field correction of airfoil computations; "vortex+source" adds a source
+    that follows the current drag (PolarEngine.enable_far_profile, far_profile, vortex_update).  The warm-up and the sampling then run
+    in chunks of `vortex_every` steps, counted from this call's first step; chunking does not move the samples, which fall on the
+    multiples of `sample_every` of the step count.  After each chunk whose end lies at or beyond step `vortex_after` (default one
+    chord transit, ceil(chord_cells(nx)/u0)) the pressure force of the state the chunk's last step emitted (PolarEngine.forces)
+    moves the strengths by `vortex_relax` of the way to their targets and the new tables are uploaded.  The angle in the update is
+    the member's in the wind frame and 0 in the body frame.  relax 0.3 every 100 steps from step 1000 is what was tried on the CPU
+    definition and stayed stable; other values are untested.  It works with both frames, every collision, both wall rules and
+    `start` / `keep_state`: the state carries the tables and the strengths, and a continued sweep goes on from them; when the first
+    run's length is a multiple of `vortex_every`, the two runs together are one run of the combined length, bit for bit.  The
+    correction removes a part of the tunnel effect, not all of it, and a taller lattice (`ny`) removes more, at its cost in work
+    (README, profiles/polar_profile_sweep.txt).  PolarResult.far_field says what ran, PolarResult.vortex_history holds every update
+    and PolarPoint.vortex_strength / .vortex_source the last values.  storage="half" with a far field other than "uniform", an
+    unknown far_field, vortex_every < 1 or a vortex_relax outside (0, 1] raises ValueError before an engine is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -748,6 +882,17 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         magic = float(magic)
         if not math.isfinite(magic) or not 0.0 < magic <= 1.0:
             raise ValueError(f"magic must be a finite magic number in (0, 1], got {magic!r}")
+    if not isinstance(far_field, str) or far_field not in FAR_FIELDS:
+        raise ValueError(f"far_field must be one of {FAR_FIELDS}, got {far_field!r}")
+    vortex = far_field != "uniform"
+    if vortex:
+        if storage == "half":
+            raise ValueError(f'storage="half" does not combine with far_field={far_field!r}')
+        if int(vortex_every) != vortex_every or vortex_every < 1:
+            raise ValueError(f"vortex_every must be a number of steps >= 1, got {vortex_every!r}")
+        vortex_relax = float(vortex_relax)
+        if not 0.0 < vortex_relax <= 1.0:                      # (false for a NaN)
+            raise ValueError(f"vortex_relax must be in (0, 1], got {vortex_relax!r}")
     wind = frame == "wind"
     if wind and any(not abs(a) <= WIND_ALPHA_MAX for a in alphas):
         raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
@@ -791,15 +936,56 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_trt(magic)
         if start is not None:
             eng.restore(start)
-        if warmup_steps:
-            eng.step(warmup_steps, tau, ux0)
-        # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
-        eng.step(samples * sample_every, tau, ux0, sample_every=sample_every)
+        if not vortex:
+            if warmup_steps:
+                eng.step(warmup_steps, tau, ux0)
+            # the samples fall on the multiples of sample_every in (warm-up, warm-up + samples * sample_every]: exactly `samples` of them
+            eng.step(samples * sample_every, tau, ux0, sample_every=sample_every)
+        else:
+            B = len(alphas)
+            xc, yc = quarter_chord(nx, ny)
+            bound = vortex_bound(nx, ny, xc, yc)
+            after = int(math.ceil(chord_cells(nx) / u0)) if vortex_after is None else int(vortex_after)
+            u_far, v_far = np.broadcast_to(np.asarray(ux0, np.float64), (B,)), (vy0 if wind else np.zeros(B))
+            alpha_far = np.asarray(alphas if wind else [0.0] * B, np.float64)
+            held = start.get("vortex") if start is not None else None
+            strength = np.array(held["strength"], np.float64) if held else np.zeros(B)
+            source = np.array(held["source"], np.float64) if held else np.zeros(B)
+            vh = {k: [] for k in ("step", "fx", "fy", "strength", "source", "clipped")}
+
+            def upload():
+                tabs = [far_profile(nx, ny, u_far[m], v_far[m], strength[m], source[m], xc, yc, eng.dtype) for m in range(B)]
+                eng.set_far_profile(*(np.stack([t[k] for t in tabs]) for k in range(3)))
+
+            eng.enable_far_profile()
+            upload()
+            total, done = warmup_steps + samples * sample_every, 0
+            while done < total:
+                n = min(int(vortex_every), total - done)
+                quiet = min(n, max(warmup_steps - done, 0))    # the chunk's steps that still belong to the warm-up take no sample
+                if quiet:
+                    eng.step(quiet, tau, ux0)
+                if n > quiet:
+                    eng.step(n - quiet, tau, ux0, sample_every=sample_every)
+                done += n
+                count = eng.step_count
+                if count >= after:
+                    fx, fy, _, _ = eng.forces()
+                    strength, source, clipped = vortex_update(strength, source, fx, fy, alpha_far, u0, vortex_relax, bound,
+                                                              with_source=far_field == "vortex+source")
+                    upload()
+                    for k, v in zip(vh, (count, fx, fy, strength, source, clipped)):
+                        vh[k].append(v)
+            U = len(vh["step"])
+            vortex_history = {"step": np.asarray(vh["step"], np.int64), **{k: np.asarray(vh[k], np.float64).reshape(U, B) for k in ("fx", "fy", "strength", "source")},
+                              "clipped": np.asarray(vh["clipped"], bool).reshape(U, B)}
         h = eng.history()
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), 0.0 if wind else a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
         means = [mean_flow(eng.mean_sums(m), u0) for m in range(len(alphas))] if mean_fields else [None] * len(alphas)
         state = eng.state() if keep_state else None
+        if vortex and state is not None:
+            state["vortex"] = {"strength": strength.copy(), "source": source.copy()}
     if wind:                                                   # lattice axes -> wind axes, every sample of every member
         h["fx"], h["fy"] = wind_axes(h["fx"], h["fy"], alphas)
         if total_forces:
@@ -810,8 +996,12 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               for m, a in enumerate(alphas)]
     for p, mean in zip(points, means):
         p.mean = mean
+    if vortex:
+        for m, p in enumerate(points):
+            p.vortex_strength, p.vortex_source = float(strength[m]), float(source[m])
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
-                       walls=walls, frame=frame, storage=storage, state=state, collision=collision, magic=magic if trt else None)
+                       walls=walls, frame=frame, storage=storage, state=state, collision=collision, magic=magic if trt else None,
+                       far_field=far_field, vortex_history=vortex_history if vortex else None)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

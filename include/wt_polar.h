@@ -363,6 +363,48 @@ WTP_API int wtp_set_step_count(wtp_batch *b, int64_t steps);
  * wrote them.  A batch that never calls it launches the kernels it always launched.
  */
 WTP_API int wtp_enable_trt(wtp_batch *b, const double *magic);
+/*
+ * Prescribed far-field profile: every far-field cell of a member holds the equilibrium of its own (rho, ux, uy), given by the caller.
+ * The uniform far field, axial or inclined, holds the rows 0.46 chords above and below the body at the free stream, which acts like the
+ * walls of a closed tunnel.  The textbook correction for airfoil computations prescribes on the outer boundary the free stream plus the
+ * velocity of a point vortex whose circulation follows the lift (and of a source that follows the drag); sheared inflow and gusts are
+ * other uses.  The library holds the tables and writes their equilibrium; what goes into them is host arithmetic
+ * (airfoil_cfd_tool_amd.polar.far_profile, vortex_update).  It is another far field, per member and opt-in.  Definition:
+ *   Far field.  A far-field cell is, as always, one that is not solid, not in the outlet column, and lies in column 0, row 0 or row
+ *   NY-1.  The branch order (solid, then outlet, then far field, then interior) does not change.  With the model on, member m holds
+ *   three tables of the batch's dtype T, each with three planes (rho, ux, uy):
+ *     left[3][NY]    for the cells (0, j)
+ *     bottom[3][NX]  for the cells (i, 0)
+ *     top[3][NX]     for the cells (i, NY-1)
+ *   A far-field cell (i, j) takes left[.][j] if i == 0, else bottom[.][i] if j == 0, else top[.][i].  The two corners of column 0
+ *   therefore belong to `left`, and entries 0 and NX-1 of `bottom` and `top` are never read.  The cell writes feq_k(rho, ux, uy) and
+ *   stores (rho, ux, uy).  feq is the step's own: oracle/lbm_numpy.feq's order, one rounding per operation in T, no contraction.
+ *   u0[m] of wtp_step and V0[m] of wtp_enable_wind are not read by far-field cells while the model is on; they still set the start
+ *   state.  Nothing else in the step changes: the interior branch with every collision and either wall rule, the outlet, the solid
+ *   cells and the stability net all stay as they are.
+ *   Consequence.  A profile that is (1, (T)u0, (T)v0) in every entry gives the bits of a batch with wtp_enable_wind, and with v0 = 0
+ *   those of a plain batch.
+ *   Read-outs.  Forces, loads, momentum exchange and mean fields are unchanged and stand on whatever state the step produced.
+ * On the device a member's tables take (3 * pitch + 6 * NX64) * sizeof(T) bytes, pitch = NY rounded up to 256 and NX64 = NX rounded
+ * up to 64, rounded up like every per-member array (25 KB at 320x160 fp32).
+ *
+ * wtp_enable_far_profile with on != 0 switches the model on: on first use it allocates the tables of all members.  Where the
+ * allocation fails it returns WT_ERR_OOM, holds nothing, and the batch goes on as before.  on == 0 switches back to the kernels, and
+ * the bits, of a batch that never enabled it; the tables are kept.  Either takes effect from the next wtp_step.  On a half batch both
+ * calls return WT_ERR_STATE and leave the batch working: half storage is out of scope, as interpolated walls are.  The flow state, the
+ * step count, the history, every running sum and every other wtp_enable_* setting are kept.  It combines with wtp_enable_les,
+ * wtp_enable_ibb, wtp_enable_trt and wtp_enable_wind (whose V0 then only sets the start state).  A batch that never calls it launches
+ * the kernels it always launched.  A member with a profile has no libwindtunnel twin.
+ * wtp_set_far_profile gives members [first, first+count) their tables: left [count][3][NY], bottom and top [count][3][NX] of T.  Every
+ * value must be finite, rho in [0.5, 2] and ux*ux + uy*uy <= 0.35*0.35 (the bounds of the stability net; the sum is formed in double).
+ * A null pointer, a value outside those bounds or a member range outside the batch is WT_ERR_ARG, before any device call, and the batch
+ * is left as it was.  WT_ERR_STATE while the model has never been enabled.  Steps already enqueued see the old values, later ones the
+ * new, as with every per-member upload.  The tables survive wtp_set_masks and wtp_init_equilibrium.
+ * While the model is on, wtp_step fails with WT_ERR_STATE, before anything is enqueued, as long as any member has never been given a
+ * profile.
+ */
+WTP_API int wtp_enable_far_profile(wtp_batch *b, int on);
+WTP_API int wtp_set_far_profile(wtp_batch *b, int first, int count, const void *left, const void *bottom, const void *top);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -1,0 +1,338 @@
+"""GPU: the prescribed far-field profile of batched sweeps (k_step_profile_batch, wtp_enable_far_profile, wtp_set_far_profile) against its
+definition in NumPy (tests/_profile_reference.py), on the cases of tests/_profile_cases.py.
+
+There is no tolerance on the state: the kernel and the reference form the far field by the same operations, rounded once each, so
+populations and macroscopic fields are the same bits, with every collision and either wall rule.  Every lattice runs with tables from
+far_profile (member 0 without vortex and source, the others with one sign of the strength each) and with random tables in which no two
+entries are alike: a vortex profile is smooth, forgives an entry shifted by one in most bits of most cells, and cannot tell from which
+table a corner of column 0 came (tests/test_polar_profile_host.py).
+"""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from conftest import bits_equal
+import lbm_numpy
+import _profile_cases as pc
+import _profile_reference as prof
+import _wind_reference as wind
+from _loads_reference import loads_reference, surface_sums
+from _mean_reference import SUMS, accumulate
+from _mex_reference import mex_reference
+from _rough_start import rough_state
+
+pytestmark = pytest.mark.gpu
+
+WT_ERR_ARG, WT_ERR_STATE = -1, -5
+STEPS = pc.STEPS
+
+
+def _assert_state(b, ref, what):
+    for m, (want_f, want_macro) in enumerate(ref):
+        f, macro = b.read_f(m), b.read_macro(m)
+        bad = int((f.view(np.uint8) != want_f.view(np.uint8)).reshape(9, f.shape[1], -1).any(axis=(0, 2)).sum())
+        assert bits_equal(f, want_f), (what, m, bad, "rows differ")
+        for got, want, plane in zip(macro, want_macro, ("rho", "ux", "uy")):
+            assert bits_equal(got, want), (what, m, plane)
+
+
+def _engine(pkg, name, masks, tables, **kw):
+    """A batch of the lattice `name` with its masks, the members' start state of (u0, v0), and the profile on with `tables`."""
+    nx, ny, dtype, B = pc.lattice(name)
+    _, u0, v0, _ = pc.params(name)
+    b = pkg.PolarEngine(nx, ny, B, dtype=dtype.name, **kw)
+    b.set_masks(masks)
+    b.enable_wind(v0)                                                      # sets the start state; the far field no longer reads it
+    b.init_equilibrium(u0)
+    if tables is not None:
+        b.enable_far_profile()
+        b.set_far_profile(*pc.stack(tables))
+    return b
+
+
+# ---- 1. bit identity by tile class -------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["vortex", "random"])
+@pytest.mark.parametrize("name", list(pc.CASES))
+def test_state_is_the_references_bits(pkg, name, kind):
+    tau, u0, v0, _ = pc.params(name)
+    masks, _, ref = pc.reference(name, kind)
+    plain = pc.reference(name, "uniform")[2]
+    for m in range(1, len(ref)):                                           # the comparison is not vacuous, on the reference itself
+        assert not bits_equal(ref[m][0], plain[m][0]), (name, kind, m)
+    with _engine(pkg, name, masks, pc.tables_of(name, kind)) as b:
+        assert b.far_profile_enabled
+        b.step(STEPS, tau, u0)
+        _assert_state(b, ref, (name, kind))
+
+
+# ---- 2. every collision and wall rule ----------------------------------------------------------
+@pytest.mark.parametrize("variant", pc.VARIANTS)
+@pytest.mark.parametrize("name", list(pc.COMBINED))
+def test_state_is_the_references_bits_with_every_collision_and_wall_rule(pkg, name, variant):
+    tau, u0, v0, cs = pc.params(name)
+    masks, q, ref = pc.reference(name, "vortex", variant)
+    other = pc.reference(name, "vortex", "" if "ibb" not in variant else "ibb")[2]
+    if variant != "ibb":
+        assert any(not bits_equal(ref[m][0], other[m][0]) for m in range(len(ref))), (name, variant)      # the model under the wrapper acts
+    with _engine(pkg, name, masks, pc.tables_of(name, "vortex")) as b:
+        pc.configure(b, variant, q, cs)
+        b.step(STEPS, tau, u0)
+        _assert_state(b, ref, (name, variant))
+
+
+# ---- 3. a uniform profile is a wind batch, and with v0 = 0 a plain batch ------------------------
+@pytest.mark.parametrize("name", ["40x300-f32", "24x256-f32", "24x140-f64"])
+def test_a_uniform_profile_is_a_wind_batch(pkg, name):
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    zero = v0.index(0.0)
+    got = {}
+    for mode in ("profile", "wind", "plain"):
+        with pkg.PolarEngine(nx, ny, B, dtype=dtype.name) as b:
+            b.set_masks(masks)
+            if mode != "plain":
+                b.enable_wind(v0)
+            b.init_equilibrium(u0)
+            if mode == "profile":
+                b.enable_far_profile()
+                b.set_far_profile(*pc.stack(pc.tables_of(name, "uniform")))
+            b.step(STEPS, tau, u0)
+            got[mode] = [(b.read_f(m), b.read_macro(m)) for m in range(B)]
+
+    def same(x, y):
+        return x[0].tobytes() == y[0].tobytes() and all(a.tobytes() == c.tobytes() for a, c in zip(x[1], y[1]))
+    for m in range(B):
+        assert same(got["profile"][m], got["wind"][m]), (name, m)           # device against device
+    assert same(got["profile"][zero], got["plain"][zero])
+    assert not same(got["profile"][(zero + 1) % B], got["plain"][(zero + 1) % B])
+    ref = pc.reference(name, "uniform")[2]                                  # ... and against the reference
+    for m in range(B):
+        assert bits_equal(got["profile"][m][0], ref[m][0]), (name, m)
+        want = wind.run(masks[m], STEPS, tau[m], u0[m], v0[m], dtype=dtype)
+        assert bits_equal(got["profile"][m][0], want[0]), (name, m)
+
+
+# ---- 4. new tables between calls ---------------------------------------------------------------
+@pytest.mark.parametrize("name", ["37x299-f32", "24x140-f64"])
+def test_a_schedule_of_tables_is_the_references(pkg, name):
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    first, second, third = pc.tables_of(name, "vortex"), pc.tables_of(name, "random"), pc.vortex_tables(name, -0.5)
+    with _engine(pkg, name, masks, first) as b:
+        b.step(20, tau, u0)
+        b.set_far_profile(*pc.stack(second))
+        b.step(20, tau, u0)
+        mid = b.read_f(0)
+        # members [1, 2) only: member 0 and member 2 keep the second tables
+        b.set_far_profile(*(t[None] for t in third[1]), first=1)
+        b.step(20, tau, u0)
+        for m in range(B):
+            last = third[m] if m == 1 else second[m]
+            want = prof.run(masks[m], [(20, first[m]), (20, second[m]), (20, last)], tau[m], u0[m], dtype=dtype, v0=v0[m])
+            assert bits_equal(b.read_f(m), want[0]), (name, m)
+            assert all(bits_equal(a, c) for a, c in zip(b.read_macro(m), want[1])), (name, m)
+        wrong = prof.run(masks[0], [(20, third[0])], tau[0], u0[0], dtype=dtype, f=mid)
+        assert not bits_equal(b.read_f(0), wrong[0])                        # member 0 with the third tables would have been another state
+
+
+# ---- 5. from a start with no two sites alike ---------------------------------------------------
+@pytest.mark.parametrize("name", ["37x299-f32", "24x140-f64"])
+def test_rough_start(pkg, name):
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    tables = pc.tables_of(name, "random")
+    rough = [rough_state(nx, ny, u0[m], dtype, 900 + m) for m in range(B)]
+    with _engine(pkg, name, masks, tables) as b:
+        for m in range(B):
+            b.write_f(m, rough[m])
+        b.step(7, tau, u0)
+        for m in range(B):
+            want = prof.run(masks[m], [(7, tables[m])], tau[m], u0[m], dtype=dtype, f=rough[m])
+            assert lbm_numpy.clamp_events(*want[1], masks[m]) == (0, 0)
+            assert bits_equal(b.read_f(m), want[0]), (name, m)
+            assert all(bits_equal(a, c) for a, c in zip(b.read_macro(m), want[1])), (name, m)
+            plain = wind.run(masks[m], 7, tau[m], u0[m], v0[m], dtype=dtype, f=rough[m])
+            assert not bits_equal(want[0], plain[0])
+
+
+# ---- 6. off again; the read-outs stand on the profile state ------------------------------------
+def test_switching_off_returns_to_the_uniform_far_field_and_keeps_the_history(pkg):
+    name, every = "96x48-f32", 12
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    tables = pc.tables_of(name, "vortex")
+    with _engine(pkg, name, masks, tables, history_cap=8) as b:
+        b.step(24, tau, u0, sample_every=every)
+        first = b.history()
+        _assert_state(b, pc.reference(name, "vortex", steps=24)[2], "first half")
+        at_switch = [b.read_f(m) for m in range(B)]
+        b.enable_far_profile(False)
+        assert not b.far_profile_enabled and b.wind_enabled
+        b.step(24, tau, u0, sample_every=every)
+        h = b.history()
+        assert list(h["step"]) == [12, 24, 36, 48]
+        for k in ("fx", "fy", "surf", "rev"):
+            assert h[k][:2].tobytes() == first[k].tobytes(), k
+        after = [b.read_f(m) for m in range(B)]
+        for m in range(B):                                                  # the wind batch's bits from that step on
+            want = wind.run(masks[m], 24, tau[m], u0[m], v0[m], f=at_switch[m])
+            assert bits_equal(after[m], want[0]), m
+            assert all(bits_equal(a, c) for a, c in zip(b.read_macro(m), want[1])), m
+        b.enable_far_profile()                                              # on again: the tables were kept
+        b.step(12, tau, u0)
+        for m in range(B):
+            want = prof.run(masks[m], [(12, tables[m])], tau[m], u0[m], f=after[m])
+            assert bits_equal(b.read_f(m), want[0]), m
+
+
+def test_readouts_are_defined_on_the_profile_state(pkg):
+    name, every, calls = "96x48-f32", 12, 4
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    xr, yr = [0.3641 * nx + 1.7 * m for m in range(B)], [0.5 * ny - 0.85 * m - 3.3 for m in range(B)]
+    macros, fs, forces = [[] for _ in range(B)], [[] for _ in range(B)], []
+    with _engine(pkg, name, masks, pc.tables_of(name, "vortex"), history_cap=calls) as b:
+        b.enable_loads(xr, yr)
+        b.enable_momentum_exchange(xr, yr)
+        b.enable_mean_fields()
+        for _ in range(calls):
+            b.step(every, tau, u0, sample_every=every)
+            forces.append(b.forces())
+            for m in range(B):
+                macros[m].append(b.read_macro(m))
+                fs[m].append(b.read_f(m))
+        h = b.history()
+        surface = [b.surface(m) for m in range(B)]
+        sums = [b.mean_sums(m) for m in range(B)]
+    ref = pc.reference(name, "vortex", steps=every)[2]
+    assert bits_equal(fs[1][0], ref[1][0])                                  # the state under the read-outs is the model's
+    for r in range(calls):
+        for k, v in zip(("fx", "fy", "surf", "rev"), forces[r]):
+            assert h[k][r].tobytes() == v.tobytes(), (r, k)
+    for m in range(B):
+        for r in range(calls):
+            rho, ux, _ = macros[m][r]
+            fx, fy, surf, rev = lbm_numpy.compute_forces_raw(rho, ux, masks[m])
+            assert (int(h["surf"][r, m]), int(h["rev"][r, m])) == (surf, rev) and surf > 0
+            assert abs(h["fx"][r, m] - fx) <= 1e-12 * surf and abs(h["fy"][r, m] - fy) <= 1e-12 * surf      # (p < 1 per face, summed in double)
+            lo = loads_reference(rho, masks[m], xr[m], yr[m])
+            mx = mex_reference(fs[m][r], masks[m], xr[m], yr[m])
+            assert mx.links == int(h["links"][r, m]) > 50
+            for got, want, bound in ((h["mz"][r, m], lo.mz, lo.mz_bound), (h["fx_mex"][r, m], mx.fx, mx.fx_bound),
+                                     (h["fy_mex"][r, m], mx.fy, mx.fy_bound), (h["mz_mex"][r, m], mx.mz, mx.mz_bound)):
+                assert abs(got - want) <= bound, (m, r, got, want, bound)
+        su, sl, nu, nl = surface_sums([mac[0] for mac in macros[m]], masks[m])
+        assert np.array_equal(surface[m]["n_upper"], nu) and np.array_equal(surface[m]["n_lower"], nl)
+        assert bits_equal(surface[m]["rho_upper"], su) and bits_equal(surface[m]["rho_lower"], sl)
+        want = accumulate(macros[m])
+        assert sums[m]["n"] == want["n"] == calls
+        for k in SUMS:
+            assert bits_equal(sums[m][k], want[k]), (m, k)
+
+
+# ---- 7. errors ---------------------------------------------------------------------------------
+def test_errors_leave_the_batch_working(pkg):
+    name = "96x48-f32"
+    nx, ny, dtype, B = pc.lattice(name)
+    tau, u0, v0, _ = pc.params(name)
+    masks = pc.masks_of(name)
+    tables = pc.tables_of(name, "vortex")
+    left, bottom, top = (a.copy() for a in pc.stack(tables))
+    vp = ctypes.c_void_p
+    with _engine(pkg, name, masks, None) as b:
+        with pytest.raises(pkg.WTError) as ei:                              # before enable_far_profile
+            b.set_far_profile(left, bottom, top)
+        assert ei.value.code == WT_ERR_STATE
+        b.enable_far_profile()
+        with pytest.raises(pkg.WTError) as ei:                              # no member has a profile
+            b.step(5, tau, u0)
+        assert ei.value.code == WT_ERR_STATE and "member 0" in str(ei.value)
+        b.set_far_profile(*(t[:2] for t in (left, bottom, top)))
+        with pytest.raises(pkg.WTError) as ei:                              # member 2 still has none
+            b.step(5, tau, u0)
+        assert ei.value.code == WT_ERR_STATE and "member 2" in str(ei.value) and b.step_count == 0
+        b.set_far_profile(left, bottom, top)
+        for plane, value, where in ((1, float("nan"), "left"), (0, 2.5, "top"), (0, 0.4, "bottom"), (1, 0.36, "bottom"), (2, float("inf"), "left")):
+            bad = {"left": left.copy(), "bottom": bottom.copy(), "top": top.copy()}
+            bad[where][1, plane, 5] = value
+            if plane == 1 and value == 0.36:
+                bad[where][1, 2, 5] = 0.0                                   # a speed of 0.36
+            with pytest.raises(pkg.WTError) as ei:
+                b.set_far_profile(bad["left"], bad["bottom"], bad["top"])
+            assert ei.value.code == WT_ERR_ARG and f"`{where}` of member 1" in str(ei.value), (where, value)
+        for args in ((-1, 1), (B, 1), (1, B), (0, 0)):                      # member ranges outside the batch
+            assert b._lib.wtp_set_far_profile(b._b, args[0], args[1], left.ctypes.data_as(vp), bottom.ctypes.data_as(vp), top.ctypes.data_as(vp)) == WT_ERR_ARG
+        assert b._lib.wtp_set_far_profile(b._b, 0, B, left.ctypes.data_as(vp), None, top.ctypes.data_as(vp)) == WT_ERR_ARG      # a null pointer
+        b.step(STEPS, tau, u0)                                              # after each refusal: the tables last accepted
+        _assert_state(b, pc.reference(name, "vortex")[2], "after the refusals")
+    with pkg.PolarEngine(nx, ny, B, storage="half") as b:                   # a half batch
+        b.set_masks(masks)
+        b.init_equilibrium(u0)
+        with pytest.raises(pkg.WTError) as ei:
+            b.enable_far_profile()
+        assert ei.value.code == WT_ERR_STATE and not b.far_profile_enabled
+        assert b._lib.wtp_set_far_profile(b._b, 0, B, left.ctypes.data_as(vp), bottom.ctypes.data_as(vp), top.ctypes.data_as(vp)) == WT_ERR_STATE
+        b.step(10, tau, u0)
+        with pkg.PolarEngine(nx, ny, B, storage="half") as c:
+            c.set_masks(masks)
+            c.init_equilibrium(u0)
+            c.step(10, tau, u0)
+            assert all(b.read_stored(m).tobytes() == c.read_stored(m).tobytes() for m in range(B))
+
+
+# ---- 8. run_polar ------------------------------------------------------------------------------
+def test_run_polar_with_the_vortex_and_the_source(pkg):
+    from airfoil_cfd_tool_amd.polar import chord_cells, far_profile, quarter_chord, vortex_bound, vortex_update
+    nx, ny, alphas, u0, every, relax = 96, 48, [2.0, 4.0, 6.0], 0.06, 58, 0.3
+    kw = dict(shape="naca2412", nx=nx, ny=ny, frame="wind", far_field="vortex+source", vortex_every=every, vortex_after=174, vortex_relax=relax)
+    one = pkg.run_polar(alphas, warmup_steps=600, samples=8, keep_state=True, **kw)            # 696 steps: 12 chunks of 58
+    assert one.far_field == "vortex+source" and one.frame == "wind" and one.u0 == u0
+    vh = one.vortex_history
+    assert list(vh["step"]) == [58 * k for k in range(3, 13)]
+    assert vh["strength"].shape == (10, 3) and not vh["clipped"].any()
+    # the recorded strengths and sources replay from the recorded forces
+    xc, yc = quarter_chord(nx, ny)
+    s, q = np.zeros(3), np.zeros(3)
+    for u in range(10):
+        s, q, clipped = vortex_update(s, q, vh["fx"][u], vh["fy"][u], alphas, u0, relax, vortex_bound(nx, ny, xc, yc))
+        assert s.tobytes() == vh["strength"][u].tobytes() and q.tobytes() == vh["source"][u].tobytes(), u
+    assert [p.vortex_strength for p in one.points] == list(s) and [p.vortex_source for p in one.points] == list(q)
+    assert all(v > 0 for v in s) and s[2] > s[0] and all(v > 0 for v in q)                    # lift and drag at positive angles
+    # the final populations are the reference's, stepped with the recorded schedule
+    mask = pkg.geometry.build_geometry(nx, ny, 0.0, [], "naca2412").mask
+    steps = [0] + [int(v) for v in vh["step"]]
+    for m, a in enumerate(alphas):
+        um, vm = u0 * math.cos(math.radians(a)), u0 * math.sin(math.radians(a))
+        strengths = [(0.0, 0.0)] + [(vh["strength"][u, m], vh["source"][u, m]) for u in range(9)]
+        schedule = [(steps[1], far_profile(nx, ny, um, vm, 0.0, 0.0, xc, yc))]
+        schedule += [(steps[k + 1] - steps[k], far_profile(nx, ny, um, vm, *strengths[k], xc, yc)) for k in range(1, 10)]
+        assert sum(n for n, _ in schedule) == 696
+        want = prof.run(mask, schedule, one.tau, um, v0=vm)
+        assert bits_equal(one.state["f"][m], want[0]), m
+        for k, t in zip(("left", "bottom", "top"), far_profile(nx, ny, um, vm, s[m], q[m], xc, yc)):
+            assert bits_equal(one.state["far_profile"][k][m], t), (m, k)     # the state carries the tables in use ...
+    assert one.state["vortex"]["strength"].tobytes() == s.tobytes()          # ... and the strengths
+    # a second call continues: both together are one run of the combined length
+    two = pkg.run_polar(alphas, samples=8, start=one.state, **kw)
+    both = pkg.run_polar(alphas, warmup_steps=600, samples=16, **kw)
+    assert list(both.vortex_history["step"]) == [58 * k for k in range(3, 13)] + [754, 792]
+    for m in range(3):
+        for k in ("step", "fx", "fy", "surf", "rev", "mz"):
+            joined = np.concatenate([one.points[m].history[k], two.points[m].history[k]])
+            assert joined.tobytes() == both.points[m].history[k].tobytes(), (m, k)
+    assert two.vortex_history["strength"].tobytes() == both.vortex_history["strength"][10:].tobytes()
+    # "uniform" is the call without the argument
+    plain = dict(shape="naca2412", nx=nx, ny=ny, frame="wind", warmup_steps=120, samples=4)
+    a, b = pkg.run_polar(alphas, **plain), pkg.run_polar(alphas, far_field="uniform", **plain)
+    assert b.far_field == "uniform" and b.vortex_history is None and b.points[0].vortex_strength is None
+    for m in range(3):
+        for k in ("step", "fx", "fy", "surf", "rev", "mz"):
+            assert a.points[m].history[k].tobytes() == b.points[m].history[k].tobytes(), (m, k)
+    assert chord_cells(nx) / u0 > 696                                       # (why the test sets vortex_after: the default lies beyond this run)

@@ -58,6 +58,13 @@ half batch k_step_trt_half_batch) in place of the kernel the other switches sele
 leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.  Without --trt, --lib may name a
 build from before the collision existed, so that a parent commit's library is timed by the same script.
 
+    python tools/polar_bench.py --profile [--les CS] [--ibb] [--wind] [--trt MAGIC] [--repeats 5] [the options of the first form]
+
+The batched step with a prescribed far-field profile (wtp_enable_far_profile; every member with the tables of its free stream plus a
+point vortex at the quarter chord that induces 0.01 at the nearest far-field cell): k_step_profile_batch in place of the kernel the
+other switches select.  The line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --profile,
+--lib may name a build from before the entry points existed.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -97,10 +104,21 @@ def _cross_flow(b):
     return U0 * np.sin(np.radians(_alphas(b)))
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native", trt=None):
+def _far_profile(eng, nx, ny, b, wind):
+    """Switch the prescribed far-field profile on: member m's free stream plus a vortex that induces 0.01 at the nearest far-field cell."""
+    xc, yc = pkg.polar.quarter_chord(nx, ny)
+    strength = 0.01 * pkg.polar.vortex_bound(nx, ny, xc, yc)
+    v0 = _cross_flow(b) if wind else np.zeros(b)
+    tabs = [pkg.polar.far_profile(nx, ny, U0, v0[m], strength, 0.0, xc, yc) for m in range(b)]
+    eng.enable_far_profile()
+    eng.set_far_profile(*(np.stack([t[k] for t in tabs]) for k in range(3)))
+
+
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native", trt=None, profile=False):
     """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
     ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across;
-    trt: the magic number of the two-relaxation-time collision in every member (None: one relaxation time)."""
+    trt: the magic number of the two-relaxation-time collision in every member (None: one relaxation time); profile: a prescribed
+    far-field profile, the free stream plus a weak vortex."""
     out = []
     with pkg.PolarEngine(nx, ny, b, storage=storage) as eng:
         eng.set_masks(masks)
@@ -113,6 +131,8 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False,
             _interpolated_walls(eng, nx, ny, b)
         if trt is not None:
             eng.enable_trt(trt)
+        if profile:
+            _far_profile(eng, nx, ny, b, wind)
         eng.step(warmup, TAU, U0)
         eng.sync()
         for _ in range(repeats):
@@ -269,6 +289,7 @@ def main():
     ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
     ap.add_argument("--storage", default="native", choices=pkg.polar.STORAGES, help="how the batch stores its populations (half: binary16 deviations)")
     ap.add_argument("--trt", type=float, default=None, metavar="MAGIC", help="step with the two-relaxation-time collision, magic number MAGIC in every member")
+    ap.add_argument("--profile", action="store_true", help="step with a prescribed far-field profile, the free stream plus a weak vortex in every member")
     ap.add_argument("--lib", default=None, help="another build of libwtpolar.so to load instead of the package's")
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
@@ -277,10 +298,15 @@ def main():
     if a.repeats is None:
         a.repeats = 1 if plain else 7
     if a.lib:
-        pkg.polar.load_polar_library(a.lib, optional=() if a.trt is not None else ("wtp_enable_trt",))
+        unused = (("wtp_enable_trt", a.trt is None), ("wtp_enable_far_profile", not a.profile), ("wtp_set_far_profile", not a.profile))
+        pkg.polar.load_polar_library(a.lib, optional=tuple(name for name, free in unused if free))
     if a.storage == "half" and a.ibb:
         ap.error("--storage half does not combine with --ibb")
     half = a.storage == "half"
+    if half and a.profile:
+        ap.error("--storage half does not combine with --profile")
+    if a.profile and not plain:
+        ap.error("--profile times the plain stepping form only")
     global LES, IBB, WIND, STORAGE, TRT
     LES, IBB, WIND, STORAGE, TRT = a.les, a.ibb, a.wind, a.storage, a.trt
     if a.mean:
@@ -294,7 +320,8 @@ def main():
         for b in (int(v) for v in a.members.split(",")):
             masks = _masks(nx, ny, b)
             sites = nx * ny
-            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage, trt=a.trt)
+            ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage, trt=a.trt,
+                             profile=a.profile)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
@@ -302,7 +329,7 @@ def main():
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.ibb or a.wind or half or a.trt is not None or a.repeats > 1:
+            if a.les is not None or a.ibb or a.wind or half or a.trt is not None or a.profile or a.repeats > 1:
                 line["les"] = a.les
                 if a.trt is not None:
                     line["trt"] = a.trt
@@ -314,8 +341,10 @@ def main():
                     line["ibb"] = True
                 if a.wind:
                     line["wind"] = True
+                if a.profile:
+                    line["profile"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half and a.trt is None:
+            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half and a.trt is None and not a.profile:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
