@@ -21,24 +21,28 @@
 // Mean fields (wtp_enable_mean) are no reduction: k_mean_batch, launched behind the three, streams every member's emitted rho,
 // ux, uy once and adds them and their products to seven planes of running sums, one owner thread per entry.
 //
-// The Smagorinsky subgrid viscosity (wtp_enable_les) is no read-out but another collision: while it is on, wtp_step launches
-// k_step_les_batch, the same step_tile with collide_les in its interior cells and one more value per member, in place of
-// k_step_batch.  A batch that has it off launches k_step_batch with the arguments it always had.
+// The step has one tiled kernel, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR>: step_tile (step_fast.hpp) of the wave's tile with
+// the collision, the wall rule and the far field as template arguments, and the values each of them reads per member in one argument
+// whose members exist only in the variants that read them (StepModel).  The models below select among its instantiations.
 //
-// Interpolated bounce-back (wtp_enable_ibb) is another wall rule: while it is on, wtp_step launches k_step_ibb_batch, the same
+// The Smagorinsky subgrid viscosity (wtp_enable_les) is no read-out but another collision: while it is on, wtp_step launches
+// k_step_batch with COLLIDE_LES, the same step_tile with collide_les in its interior cells and one more value per member.  A batch
+// that has it off launches the plain instantiation with the arguments it always had.
+//
+// Interpolated bounce-back (wtp_enable_ibb) is another wall rule: while it is on, wtp_step launches k_step_batch with WALL_INTERP, the same
 // step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
 // collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction (mex_member) with the interpolated link
 // rule.  A batch that has it off launches the kernels it always launched, with the arguments they always had.
 //
-// The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_wind_batch, the same
+// The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_batch with FAR_INCLINED, the same
 // step_tile with feq(1, U0, V0) in its far-field cells and one more value per member, with either collision and either wall rule,
 // and wtp_init_equilibrium fills the members by k_fill_wind.  A batch that has it off launches the kernels it always launched, with
 // the arguments they always had.
 //
 // Half-precision population storage (wtp_create_stored with WTP_STORE_HALF) is another storage of an fp32 batch: its lattices hold
 // each population as the binary16 deviation from its lattice weight, in wt_create's layout with 2-byte elements.  wtp_step launches
-// k_step_half_batch, site_general with half_t as its stored element: a Load in front of its branches and a Store behind, fp32 between,
-// with either collision and either far field; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
+// k_step_half_batch<EMIT, COLL, FAR>, site_general with half_t as its stored element: a Load in front of its branches and a Store behind,
+// fp32 between, with every collision and either far field, and k_step_batch's model argument; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
 // read-outs read the fp32 macroscopic planes and run unchanged.  A native batch launches the kernels it always launched, with the
 // arguments they always had.
 //
@@ -47,22 +51,23 @@
 // stale until a step has emitted and zeroes the member's running sums; with wtp_set_step_count a sweep continues where another stopped.
 // A batch that never writes launches the kernels it always launched.
 //
-// The two-relaxation-time collision (wtp_enable_trt) is a third collision: while it is on, wtp_step launches k_step_trt_batch (in a half
-// batch k_step_trt_half_batch), the same step_tile (site_general) with collide_trt in its interior cells and one more value per member,
-// the magic number, without or with the Smagorinsky eddy viscosity, with either wall rule and either storage.  Its kernels always take
+// The two-relaxation-time collision (wtp_enable_trt) is a third collision: while it is on, wtp_step launches k_step_batch (in a half
+// batch k_step_half_batch) with COLLIDE_TRT or COLLIDE_TRT_LES, the same step_tile (site_general) with collide_trt in its interior cells and one more value per member,
+// the magic number, without or with the Smagorinsky eddy viscosity, with either wall rule and either storage.  Its instantiations always take
 // the inclined far field, with an array of zeros as the cross-flow while wtp_enable_wind is off.  While it is on, wtp_step refuses a
 // tau that is not above 0.5 in the batch's dtype.  A batch that has it off launches the kernels it always launched, with the arguments
 // they always had.
 //
 // The prescribed far-field profile (wtp_enable_far_profile) is a third far field: while it is on, wtp_step launches
-// k_step_profile_batch, the same step_tile with feq(rho, ux, uy) of the cell's entry in the member's tables in its far-field cells, with
+// k_step_batch with FAR_PROFILE, the same step_tile with feq(rho, ux, uy) of the cell's entry in the member's tables in its far-field cells, with
 // every collision and either wall rule.  wtp_set_far_profile checks the tables on the host and uploads them; wtp_step refuses to run
 // while a member has none.  Native storage only.  A batch that has it off launches the kernels it always launched, with the arguments
 // they always had.
 //
-// Every variant above is a kernel of its own name and code object, so that a batch runs the one its switches select and no other.
-// What the variants share is source text: one site (site_general, kernels.hpp, for every storage), one momentum-exchange body
-// (mex_member, with a link rule per wall rule), one prologue of the tiled step kernels (MemberTile), one stepping loop on the host.
+// Every variant above is an instantiation of its own, so a batch runs the code object its switches select and no other.  What the
+// variants share is source text: one site (site_general, kernels.hpp, for every storage), one tiled step kernel and one half step kernel
+// with one selection and one launch on the host (with_step_variant, step_model), one momentum-exchange body (mex_member, with a link
+// rule per wall rule), one stepping loop on the host.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -70,6 +75,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wt_polar.h"
@@ -212,7 +218,7 @@ struct wtp_batch {
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
-// A wave's place in a tiled step launch, the prologue of the four tiled step kernels: blockIdx.y is the member, blockIdx.x * 4 + wave
+// A wave's place in a tiled step launch, the prologue of k_step_batch: blockIdx.y is the member, blockIdx.x * 4 + wave
 // the tile inside it (k_step's grid).  rev walks members and tiles backwards on every other step, as k_step walks its tiles.  A wave
 // past the last tile is not live and returns.
 struct MemberTile {
@@ -225,175 +231,87 @@ struct MemberTile {
     __device__ __forceinline__ long tile() const { return rev ? ntiles - 1 - t : t; }
 };
 
-// One step of every member.
-template <typename T, bool EMIT, int LOADMODE>
-__global__ __launch_bounds__(256) void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                    const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                    int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                    int rev)
+// The model arguments of a step kernel, by value behind the arguments every variant takes: each piece exists only in the variants
+// that read it, so that a variant's kernel arguments are the ones it uses and no other.  (One unused pointer argument costs the
+// fp32 kernels about 30 VGPRs and two waves; see step_waves.)  In argument order:
+//   cles     [B]: c = (T)(18 sqrt(2) Cs^2) of every member                                        the Smagorinsky collisions
+//   wq       the members' wall distances, eight planes each, qstride elements apart               WALL_INTERP
+//   vwind    [B]: the cross-flow V0 of every member                                               FAR_INCLINED
+//   lam      [B]: the magic number of every member                                                the two-relaxation-time collisions
+//   prof     the members' tables (FarProfile, d2q9.hpp), pstride elements apart, nxp elements per plane of `bottom` and `top`   FAR_PROFILE
+//   rev      walk members and tiles backwards (MemberTile)                                        every variant
+template <typename T, bool ON> struct ArgLes { const T *__restrict__ cles; };
+template <typename T, bool ON> struct ArgWallQ { const T *__restrict__ wq; long qstride; };
+template <typename T, bool ON> struct ArgWind { const T *__restrict__ vwind; };
+template <typename T, bool ON> struct ArgTrt { const T *__restrict__ lam; };
+template <typename T, bool ON> struct ArgProfile { const T *__restrict__ prof; long pstride; int nxp; };
+template <typename T> struct ArgLes<T, false> {};
+template <typename T> struct ArgWallQ<T, false> {};
+template <typename T> struct ArgWind<T, false> {};
+template <typename T> struct ArgTrt<T, false> {};
+template <typename T> struct ArgProfile<T, false> {};
+template <typename T, int COLL, int WALL, int FAR>
+struct StepModel : ArgLes<T, coll_has_les(COLL)>, ArgWallQ<T, WALL == WALL_INTERP>, ArgWind<T, FAR == FAR_INCLINED>, ArgTrt<T, coll_is_trt(COLL)>,
+                   ArgProfile<T, FAR == FAR_PROFILE> {
+    int rev;
+};
+
+// Waves per SIMD that a tiled step kernel asks for (0: nothing asked, the kernels with the axial far field), from the compiler's resource
+// report (profiles/polar_trt_isa.txt, profiles/polar_profile_isa.txt).  Left to itself the compiler gives every
+// kernel with more arguments than the axial ones 109 to 124 VGPRs in fp32 (4 waves), whatever the far field, the collision or the wall
+// rule is; an unused pointer argument added to the plain kernel does the same.
+//  * inclined, single relaxation time: asked for the axial kernels' occupancy (6 waves; 5 emitting or with the Smagorinsky model; 4 in
+//    fp64) it allocates 79 to 95 VGPRs, theirs within 2, without scratch, interpolated walls included.
+//  * two relaxation times: the emitting and the Smagorinsky kernels allocate 84 to 92 VGPRs in fp32 (5 waves) and 108 to 122 in fp64
+//    (4 waves) without scratch, but the plain non-emitting fp32 kernels, asked for 6 waves, get 80 VGPRs and 12 to 16 bytes of scratch
+//    per lane: the split keeps n[k], the half-sums and the half-differences alive together.  So every fp32 kernel asks for 5.
+//  * profile: every kernel asks for what its inclined twin asks for and allocates 79 to 94 VGPRs in fp32 and 93 to 111 in fp64 without
+//    scratch (the entry of a FAST tile's far row is loaded behind the collision, so it adds no live register to it).  One exception: the
+//    plain non-emitting fp32 kernel with interpolated walls, asked for its twin's 6 waves, got 79 VGPRs and 12 bytes of scratch per lane
+//    where the twin has none, so it asks for 5.
+template <typename T, bool EMIT, int COLL, int WALL, int FAR>
+constexpr int step_waves()
+{
+    if (FAR == FAR_AXIAL) return 0;
+    if (sizeof(T) == 8) return 4;
+    if (EMIT || COLL != COLLIDE_BGK) return 5;
+    return FAR == FAR_PROFILE && WALL == WALL_INTERP ? 5 : 6;
+}
+
+// One step of every member: step_tile (step_fast.hpp) of the wave's tile (MemberTile) with the member's tau and U0, on the member's
+// lattices, planes, mask and tile classes.  COLL, WALL and FAR are step_tile's: the collision of the interior fluid cells, the wall rule
+// and the far field; `a` holds what they read per member (StepModel).  A member with cles = 0, with wall distances that are all 0.5, with
+// V0 = 0 or with a profile that holds (1, U0, V0) in every entry computes the bits of the variant without that model.
+// The far fields (include/wt_polar.h "Inclined free stream", "Prescribed far-field profile"): in the step, a far-field cell is one that
+// is not solid, not in the outlet column, and lies in column 0, row 0 or row NY-1.  With FAR_INCLINED such a cell writes
+// feq_k(1, U0, V0) and stores (1, U0, V0), feq being feq_all, V0 = vwind[m]; with FAR_PROFILE it writes feq_k(rho, ux, uy) of its entry
+// in the member's tables and stores (rho, ux, uy), and U0 is not read by such a cell.  The branch order (solid, then outlet, then far
+// field, then interior) does not change, and nothing else in the step changes.
+// The two-relaxation-time collisions are not built with FAR_AXIAL: a batch without wtp_enable_wind hands them an array of zeros as
+// vwind, and V0 = 0 gives the axial far field's bits because ex*U0 + ey*0 and U0*U0 + 0*0 are exact, so that the collision costs
+// eight instantiations per dtype and not sixteen.
+template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL, int FAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL, FAR>())))
+void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
+                  const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                  StepModel<T, COLL, WALL, FAR> a)
 {
     const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
+    const MemberTile w(g, tiles_per_col, a.rev);
     if (!w.live()) return;
     const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1];
-    step_tile<T, EMIT, LOADMODE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask, tiles + m * ms.tiles,
-                                 tiles_per_col, g, 0, tau, U0, w.tile(), lane);
-}
-
-// The same step with the Smagorinsky collision (collide_les, d2q9.hpp) in every member's interior fluid cells: k_step_batch's grid,
-// walk (MemberTile) and arguments, and cles[m] = (T)(18 sqrt(2) Cs[m]^2) beside the member's tau and U0.  A member with cles = 0 computes
-// k_step_batch's bits.  A kernel of its own name, so that a batch with the model off runs the code object it always ran.
-template <typename T, bool EMIT, int LOADMODE>
-__global__ __launch_bounds__(256) void k_step_les_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                        const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                        int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                        const T *__restrict__ cles, int rev)
-{
-    const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
-    if (!w.live()) return;
-    const long m = w.member();
-    const T tau = params[2 * m], U0 = params[2 * m + 1], c = cles[m];
-    step_tile<T, EMIT, LOADMODE, false, COLLIDE_LES>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                     tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0, c);
-}
-
-// The same step with interpolated bounce-back (wall_incoming, d2q9.hpp) at every member's links, and with either collision:
-// k_step_batch's grid, walk and arguments, the members' wall distances wq (eight planes each, qstride elements apart) and, for
-// COLLIDE_LES, cles as in k_step_les_batch (not read otherwise).  A member whose distances are all 0.5 computes k_step_batch's
-// (k_step_les_batch's) numbers.  A kernel of its own name, so that a batch with the model off runs the code object it always ran.
-template <typename T, bool EMIT, int LOADMODE, int COLL>
-__global__ __launch_bounds__(256) void k_step_ibb_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                        const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                        int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                        const T *__restrict__ cles, const T *__restrict__ wq, long qstride, int rev)
-{
-    const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
-    if (!w.live()) return;
-    const long m = w.member();
-    const T tau = params[2 * m], U0 = params[2 * m + 1];
-    T c = T(0.0);
-    if constexpr (COLL == COLLIDE_LES) c = cles[m];
-    step_tile<T, EMIT, LOADMODE, false, COLL, WALL_INTERP>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                           tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0, c,
-                                                           wq + m * qstride);
-}
-
-// The same step with an inclined free stream (include/wt_polar.h "Inclined free stream"), with either collision and either wall rule:
-// k_step_ibb_batch's grid, walk and arguments, and vwind[m] = V0 of the member beside its tau and U0.  In the step, a far-field cell is
-// one that is not solid, not in the outlet column, and lies in column 0, row 0 or row NY-1.  Such a cell writes feq_k(1, U0, V0) and
-// stores (1, U0, V0), feq being feq_all.  The branch order (solid, then outlet, then far field, then interior) does not change, and
-// nothing else in the step changes.  With V0 = 0 every value has k_step_batch's (k_step_les_batch's, k_step_ibb_batch's) bits, because
-// ex*U0 + ey*0 and U0*U0 + 0*0 are exact.  cles is read only for COLLIDE_LES and wq only for WALL_INTERP.  A kernel of its own name, so
-// that a batch with the model off runs the code object it always ran.
-// Waves per SIMD: left to itself the compiler gives every kernel with this many arguments 109 to 124 VGPRs in fp32 (4 waves), whatever the
-// far field, the collision or the wall rule is; an unused pointer argument added to k_step_batch does the same.  Asked for k_step_batch's
-// (k_step_les_batch's) occupancy it allocates 79 to 95 VGPRs, theirs within 2, without scratch, interpolated walls included.
-template <typename T, bool EMIT, int COLL>
-constexpr int wind_waves() { return sizeof(T) == 8 ? 4 : (EMIT || COLL == COLLIDE_LES ? 5 : 6); }
-
-template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wind_waves<T, EMIT, COLL>()))) void k_step_wind_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
-                                                         const T *__restrict__ vwind, int rev)
-{
-    const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
-    if (!w.live()) return;
-    const long m = w.member();
-    const T tau = params[2 * m], U0 = params[2 * m + 1], V0 = vwind[m];
-    T c = T(0.0);
-    if constexpr (COLL == COLLIDE_LES) c = cles[m];
+    T c = T(0.0), V0 = T(0.0), magic = T(0.0);
     const T *q = nullptr;
-    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
-    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
-                                                                  c, q, V0);
-}
-
-// The same step with the two-relaxation-time collision (collide_trt, d2q9.hpp; include/wt_polar.h "Two-relaxation-time collision") in
-// every member's interior fluid cells, without (COLLIDE_TRT) or with (COLLIDE_TRT_LES) the Smagorinsky eddy viscosity, and with either
-// wall rule: k_step_wind_batch's grid, walk and arguments, and lam[m], the member's magic number, behind vwind.  The far field is always
-// the inclined one: a batch without wtp_enable_wind hands an array of zeros as vwind, and V0 = 0 gives the axial far field's bits (see
-// k_step_wind_batch), so that the collision costs eight instantiations per dtype and not sixteen.  cles is read only for
-// COLLIDE_TRT_LES and wq only for WALL_INTERP.  A kernel of its own name, so that a batch with the model off runs the code object it
-// always ran.
-// Waves per SIMD, from the compiler's resource report as for wind_waves (profiles/polar_trt_isa.txt): asked for wind_waves' occupancy
-// the emitting and the Smagorinsky kernels allocate 84 to 92 VGPRs in fp32 (5 waves) and 108 to 122 in fp64 (4 waves) without scratch,
-// but the plain non-emitting fp32 kernels, asked for 6 waves, get 80 VGPRs and 12 to 16 bytes of scratch per lane: the split keeps
-// n[k], the half-sums and the half-differences alive together.  So every fp32 kernel asks for 5 waves.
-template <typename T>
-constexpr int trt_waves() { return sizeof(T) == 8 ? 4 : 5; }
-
-template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(trt_waves<T>()))) void k_step_trt_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
-                                                         const T *__restrict__ vwind, const T *__restrict__ lam, int rev)
-{
-    static_assert(coll_is_trt(COLL), "COLLIDE_TRT or COLLIDE_TRT_LES");
-    const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
-    if (!w.live()) return;
-    const long m = w.member();
-    const T tau = params[2 * m], U0 = params[2 * m + 1], V0 = vwind[m], magic = lam[m];
-    T c = T(0.0);
-    if constexpr (COLL == COLLIDE_TRT_LES) c = cles[m];
-    const T *q = nullptr;
-    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
-    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_INCLINED>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                                  tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
-                                                                  c, q, V0, magic);
-}
-
-// The same step with a prescribed far-field profile (include/wt_polar.h "Prescribed far-field profile"), with every collision (COLLIDE_BGK,
-// COLLIDE_LES, COLLIDE_TRT, COLLIDE_TRT_LES) and either wall rule: k_step_trt_batch's grid, walk and arguments, without the cross-flow,
-// which no cell reads, and with the members' tables `prof` (FarProfile, d2q9.hpp; pstride elements apart, nxp elements per plane of
-// `bottom` and `top`).  A far-field cell (not solid, not in the outlet column, in column 0, row 0 or row NY-1) writes feq_k(rho, ux, uy)
-// of its entry and stores (rho, ux, uy); U0 is not read by such a cell.  The branch order does not change, and nothing else in the step
-// changes.  A profile that holds (1, U0, V0) in every entry gives k_step_wind_batch's bits.  cles is read only with the Smagorinsky
-// model, lam only for the two-relaxation-time collisions, wq only for WALL_INTERP.  A kernel of its own name, so that a batch with the
-// model off runs the code object it always ran.
-// Waves per SIMD, from the compiler's resource report as for wind_waves (profiles/polar_profile_isa.txt): every kernel asks for what its
-// FAR_INCLINED twin asks for, wind_waves for the single-relaxation-time collisions and trt_waves for the others, and allocates 79 to 94
-// VGPRs in fp32 and 93 to 111 in fp64 without scratch.  One exception: the plain non-emitting fp32 kernel with interpolated walls, asked
-// for its twin's 6 waves, got 79 VGPRs and 12 bytes of scratch per lane where the twin has none, so it asks for 5.  The entry of a FAST
-// tile's far row is loaded behind the collision, so it adds no live register to it.
-template <typename T, bool EMIT, int COLL, int WALL>
-constexpr int profile_waves()
-{
-    if (coll_is_trt(COLL)) return trt_waves<T>();
-    const int w = wind_waves<T, EMIT, COLL>();
-    return WALL == WALL_INTERP && w > 5 ? 5 : w;
-}
-
-template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(profile_waves<T, EMIT, COLL, WALL>()))) void k_step_profile_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro,
-                                                         const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
-                                                         int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                                                         const T *__restrict__ cles, const T *__restrict__ wq, long qstride,
-                                                         const T *__restrict__ lam, const T *__restrict__ prof, long pstride, int nxp, int rev)
-{
-    const int lane = threadIdx.x & 63;
-    const MemberTile w(g, tiles_per_col, rev);
-    if (!w.live()) return;
-    const long m = w.member();
-    const T tau = params[2 * m], U0 = params[2 * m + 1];
-    T c = T(0.0), magic = T(0.0);
-    if constexpr (coll_has_les(COLL)) c = cles[m];
-    if constexpr (coll_is_trt(COLL)) magic = lam[m];
-    const T *q = nullptr;
-    if constexpr (WALL == WALL_INTERP) q = wq + m * qstride;
     FarProfile<T> fp;
-    fp.tab = prof + m * pstride; fp.pitch = g.pitch; fp.nxp = nxp;
-    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR_PROFILE>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
-                                                                 tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
-                                                                 c, q, T(0.0), magic, fp);
+    if constexpr (coll_has_les(COLL)) c = a.cles[m];
+    if constexpr (WALL == WALL_INTERP) q = a.wq + m * a.qstride;
+    if constexpr (FAR == FAR_INCLINED) V0 = a.vwind[m];
+    if constexpr (coll_is_trt(COLL)) magic = a.lam[m];
+    if constexpr (FAR == FAR_PROFILE) { fp.tab = a.prof + m * a.pstride; fp.pitch = g.pitch; fp.nxp = a.nxp; }
+    step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
+                                                         tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
+                                                         c, q, V0, magic, fp);
 }
 
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
@@ -443,15 +361,16 @@ static unsigned half_step_blocks(const Geom &g)
 // Two rows per lane with packed halves (dword loads of two rows, packed conversion, a clean pair's two sites collided in one lane,
 // every other pair through the general site) was built, computed the same bits and measured slower in every walk tried, 26.9 us at best
 // against 21.7 at 320x160 with 32 members (profiles/polar_half_cost.txt), and is not kept.
-// COLL is the collision of the interior branch (collide or collide_les with cles[m]), FAR the far field (feq(1, U0, 0), or
-// feq(1, U0, V0) with vwind[m]); cles is read only for COLLIDE_LES and vwind only for FAR_INCLINED.  fp32 arithmetic only.  ms.lat
-// counts halves, ms.macro floats.
+// COLL is the collision of the interior branch and FAR the far field, FAR_AXIAL or FAR_INCLINED, as in k_step_batch, with the same
+// arguments per variant (StepModel, with float values); the two-relaxation-time collisions come with FAR_INCLINED only, as there.  fp32
+// arithmetic only.  ms.lat counts halves, ms.macro floats.
 template <bool EMIT, int COLL, int FAR>
 __global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restrict__ fs, half_t *__restrict__ fd, float *__restrict__ macro,
                                                          const uint8_t *__restrict__ mask, Geom g, MemberStrides ms,
-                                                         const float *__restrict__ params, const float *__restrict__ cles,
-                                                         const float *__restrict__ vwind, int rev)
+                                                         const float *__restrict__ params, StepModel<float, COLL, WALL_HALFWAY, FAR> a)
 {
+    static_assert(FAR != FAR_PROFILE && (!coll_is_trt(COLL) || FAR == FAR_INCLINED), "no profile; two relaxation times with FAR_INCLINED only");
+    const int rev = a.rev;
     const int runs = (int)(g.pitch / 256);                          // runs of 256 rows in a column
     const long nruns = (long)g.nxl * runs;
     const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -460,9 +379,10 @@ __global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restric
     const int i = (int)(t / runs), j0 = (int)(t % runs) * 256;
     const long mb = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
     const float tau = params[2 * mb], U0 = params[2 * mb + 1];
-    float c_les = 0.0f, V0 = 0.0f;
-    if constexpr (COLL == COLLIDE_LES) c_les = cles[mb];
-    if constexpr (FAR == FAR_INCLINED) V0 = vwind[mb];
+    float c_les = 0.0f, V0 = 0.0f, magic = 0.0f;
+    if constexpr (coll_has_les(COLL)) c_les = a.cles[mb];
+    if constexpr (FAR == FAR_INCLINED) V0 = a.vwind[mb];
+    if constexpr (coll_is_trt(COLL)) magic = a.lam[mb];
     const half_t *s = fs + mb * ms.lat + g.pitch;
     half_t *d = fd + mb * ms.lat + g.pitch;
     const uint8_t *m = mask + mb * ms.mask + g.pitch;
@@ -471,40 +391,7 @@ __global__ __launch_bounds__(256) void k_step_half_batch(const half_t *__restric
 #pragma unroll 1
     for (int v = 0; v < 4; v++) {
         const int j = j0 + v * 64 + lane;
-        if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0);
-    }
-}
-
-// One step of every member of a half batch with the two-relaxation-time collision: k_step_half_batch's grid, walk and arguments, and
-// lam[m], the member's magic number, behind vwind.  COLL is COLLIDE_TRT or COLLIDE_TRT_LES (cles is read only for the latter); the far
-// field is always the inclined one, with an array of zeros as vwind in a batch without wtp_enable_wind (see k_step_trt_batch).  Load
-// comes in front of the site's branches and Store behind them, as for the other collisions.
-template <bool EMIT, int COLL>
-__global__ __launch_bounds__(256) void k_step_trt_half_batch(const half_t *__restrict__ fs, half_t *__restrict__ fd, float *__restrict__ macro,
-                                                             const uint8_t *__restrict__ mask, Geom g, MemberStrides ms,
-                                                             const float *__restrict__ params, const float *__restrict__ cles,
-                                                             const float *__restrict__ vwind, const float *__restrict__ lam, int rev)
-{
-    static_assert(coll_is_trt(COLL), "COLLIDE_TRT or COLLIDE_TRT_LES");
-    const int runs = (int)(g.pitch / 256);                          // runs of 256 rows in a column
-    const long nruns = (long)g.nxl * runs;
-    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nruns) return;
-    const long t = rev ? nruns - 1 - q : q;
-    const int i = (int)(t / runs), j0 = (int)(t % runs) * 256;
-    const long mb = rev ? (long)gridDim.y - 1 - blockIdx.y : (long)blockIdx.y;
-    const float tau = params[2 * mb], U0 = params[2 * mb + 1], V0 = vwind[mb], magic = lam[mb];
-    float c_les = 0.0f;
-    if constexpr (COLL == COLLIDE_TRT_LES) c_les = cles[mb];
-    const half_t *s = fs + mb * ms.lat + g.pitch;
-    half_t *d = fd + mb * ms.lat + g.pitch;
-    const uint8_t *m = mask + mb * ms.mask + g.pitch;
-    float *mm = macro + mb * ms.macro;
-    const int lane = threadIdx.x & 63;
-#pragma unroll 1
-    for (int v = 0; v < 4; v++) {
-        const int j = j0 + v * 64 + lane;
-        if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR_INCLINED>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0, magic);
+        if (j < g.ny) site_general<float, COLL, WALL_HALFWAY, FAR>(s, d, mm, m, g, i, j, tau, U0, EMIT, c_les, nullptr, V0, magic);
     }
 }
 
@@ -1306,48 +1193,44 @@ static int sample_into(wtp_batch *b, int row)
     return WT_OK;
 }
 
-// k_step_wind_batch of one collision and one wall rule, emitting or not: all of them take the same arguments.
-template <typename T, int COLL, int WALL>
-static auto wind_kernel(bool emit)
+// f(std::integral_constant<int, v>()) for the v in [0, N) that `v` holds: a run-time switch handed on as a compile-time value.
+template <int N, typename F>
+static void with_constant(int v, F f)
 {
-    return emit ? k_step_wind_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_wind_batch<T, false, WT_LOADMODE, COLL, WALL>;
+    if constexpr (N > 0) {
+        if (v == N - 1) f(std::integral_constant<int, N - 1>());
+        else with_constant<N - 1>(v, f);
+    }
 }
 
-// k_step_half_batch of one collision and one far field, emitting or not: all of them take the same arguments.
-template <int COLL, int FAR>
-static auto half_kernel(bool emit)
+// The step variant that the batch's switches select: launch(EMIT, COLL, WALL, FAR) with the variant's template arguments as compile-time
+// values.  The two-relaxation-time collisions take the inclined far field where the free stream is axial (k_step_batch).
+template <typename Launch>
+static void with_step_variant(const wtp_batch *b, bool emit, Launch launch)
 {
-    return emit ? k_step_half_batch<true, COLL, FAR> : k_step_half_batch<false, COLL, FAR>;
+    const int coll = b->trt ? (b->les ? COLLIDE_TRT_LES : COLLIDE_TRT) : (b->les ? COLLIDE_LES : COLLIDE_BGK);
+    const int wall = b->ibb ? WALL_INTERP : WALL_HALFWAY;
+    const int far = b->profile ? FAR_PROFILE : (b->wind || b->trt ? FAR_INCLINED : FAR_AXIAL);
+    with_constant<2>(emit, [&](auto EMIT) { with_constant<4>(coll, [&](auto COLL) { with_constant<2>(wall, [&](auto WALL) {
+        with_constant<3>(far, [&](auto FAR) {
+            if constexpr (!coll_is_trt(COLL) || FAR != FAR_AXIAL) launch(EMIT, COLL, WALL, FAR);
+        }); }); }); });
 }
 
-// k_step_trt_batch of one collision and one wall rule, and k_step_trt_half_batch of one collision, emitting or not.
-template <typename T, int COLL, int WALL>
-static auto trt_kernel(bool emit)
+// The model arguments of one variant from the batch, with values of type T.  A two-relaxation-time variant of a batch without
+// wtp_enable_wind reads the array of zeros as its cross-flow.
+template <typename T, int COLL, int WALL, int FAR>
+static StepModel<T, COLL, WALL, FAR> step_model(const wtp_batch *b, int rev)
 {
-    return emit ? k_step_trt_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_trt_batch<T, false, WT_LOADMODE, COLL, WALL>;
+    StepModel<T, COLL, WALL, FAR> a;
+    if constexpr (coll_has_les(COLL)) a.cles = (const T *)b->les_c;
+    if constexpr (WALL == WALL_INTERP) { a.wq = (const T *)b->wq; a.qstride = b->q_stride; }
+    if constexpr (FAR == FAR_INCLINED) a.vwind = (const T *)(b->wind ? b->wind_v : b->zero_v);
+    if constexpr (coll_is_trt(COLL)) a.lam = (const T *)b->trt_lam;
+    if constexpr (FAR == FAR_PROFILE) { a.prof = (const T *)b->prof; a.pstride = b->p_stride; a.nxp = b->p_nxp; }
+    a.rev = rev;
+    return a;
 }
-
-template <int COLL>
-static auto trt_half_kernel(bool emit)
-{
-    return emit ? k_step_trt_half_batch<true, COLL> : k_step_trt_half_batch<false, COLL>;
-}
-
-// k_step_profile_batch of one collision and one wall rule, emitting or not.
-template <typename T, int COLL, int WALL>
-static auto profile_kernel(bool emit)
-{
-    return emit ? k_step_profile_batch<T, true, WT_LOADMODE, COLL, WALL> : k_step_profile_batch<T, false, WT_LOADMODE, COLL, WALL>;
-}
-template <typename T, int WALL>
-static auto profile_kernel(bool trt, bool les, bool emit)
-{
-    return trt ? (les ? profile_kernel<T, COLLIDE_TRT_LES, WALL>(emit) : profile_kernel<T, COLLIDE_TRT, WALL>(emit))
-               : (les ? profile_kernel<T, COLLIDE_LES, WALL>(emit) : profile_kernel<T, COLLIDE_BGK, WALL>(emit));
-}
-
-// The cross-flow array of the two-relaxation-time kernels: the members' V0, or zeros while the free stream is axial.
-static const void *trt_cross_flow(const wtp_batch *b) { return b->wind ? b->wind_v : b->zero_v; }
 
 // The stepping loop of wtp_step: which steps sample and which emit, the flip of the lattices, the step count and the history rows.
 // `launch(emit, rev)` enqueues one step of every member from the current lattice into the other; T is the type of the read-outs.
@@ -1370,66 +1253,34 @@ static int step_loop(wtp_batch *b, int nsteps, int sample_every, Launch launch)
     return WT_OK;
 }
 
-// The steps of a half batch: k_step_half_batch, with the fp32 read-outs.
+// The steps of a half batch: k_step_half_batch, with the fp32 read-outs.  wtp_enable_ibb and wtp_enable_far_profile refuse a half
+// batch, so the variants that k_step_half_batch does not have are never selected; were one selected, that is an error and no launch.
 static int step_half(wtp_batch *b, int nsteps, int sample_every)
 {
+    if (b->ibb || b->profile) return fail(WT_ERR_STATE, "a half batch has no step kernel with interpolated walls or a far-field profile");
     const dim3 grid(half_step_blocks(b->g), (unsigned)b->members), block(256);
     return step_loop<float>(b, nsteps, sample_every, [&](bool emit, int rev) {
-        if (b->trt) {
-            const auto k_trt = b->les ? trt_half_kernel<COLLIDE_TRT_LES>(emit) : trt_half_kernel<COLLIDE_TRT>(emit);
-            hipLaunchKernelGGL(k_trt, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
-                               macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
-                               (const float *)trt_cross_flow(b), (const float *)b->trt_lam, rev);
-            return;
-        }
-        const auto k_step = b->wind ? (b->les ? half_kernel<COLLIDE_LES, FAR_INCLINED>(emit) : half_kernel<COLLIDE_BGK, FAR_INCLINED>(emit))
-                                    : (b->les ? half_kernel<COLLIDE_LES, FAR_AXIAL>(emit) : half_kernel<COLLIDE_BGK, FAR_AXIAL>(emit));
-        hipLaunchKernelGGL(k_step, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), fptr<half_t>(b, 1 - b->cur, 0),
-                           macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms, (const float *)b->params, (const float *)b->les_c,
-                           (const float *)b->wind_v, rev);
+        with_step_variant(b, emit, [&](auto EMIT, auto COLL, auto WALL, auto FAR) {
+            if constexpr (WALL == WALL_HALFWAY && FAR != FAR_PROFILE)
+                hipLaunchKernelGGL((k_step_half_batch<EMIT != 0, COLL, FAR>), grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0),
+                                   fptr<half_t>(b, 1 - b->cur, 0), macro_of<float>(b, 0), (const uint8_t *)b->mask, b->g, b->ms,
+                                   (const float *)b->params, step_model<float, COLL, WALL, FAR>(b, rev));
+        });
     });
 }
 
-// The steps of a native batch: the tiled kernel that the free stream, the wall rule and the collision select.
+// The steps of a native batch: the tiled kernel that the collision, the wall rule and the far field select.
 template <typename T>
 static int step_impl(wtp_batch *b, int nsteps, int sample_every)
 {
     const long ntiles = (long)b->g.nxl * b->tiles_per_col;
     const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)b->members), block(256);
     return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
-        const T *fs = fptr<T>(b, b->cur, 0);
-        T *fd = fptr<T>(b, 1 - b->cur, 0);
-        if (b->profile) {
-            const auto k_step = b->ibb ? profile_kernel<T, WALL_INTERP>(b->trt, b->les, emit) : profile_kernel<T, WALL_HALFWAY>(b->trt, b->les, emit);
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
-                               (const T *)b->trt_lam, (const T *)b->prof, b->p_stride, b->p_nxp, rev);
-        } else if (b->trt) {
-            const auto k_step = b->ibb ? (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_INTERP>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_INTERP>(emit))
-                                       : (b->les ? trt_kernel<T, COLLIDE_TRT_LES, WALL_HALFWAY>(emit) : trt_kernel<T, COLLIDE_TRT, WALL_HALFWAY>(emit));
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
-                               (const T *)trt_cross_flow(b), (const T *)b->trt_lam, rev);
-        } else if (b->wind) {
-            const auto k_step = b->ibb ? (b->les ? wind_kernel<T, COLLIDE_LES, WALL_INTERP>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_INTERP>(emit))
-                                       : (b->les ? wind_kernel<T, COLLIDE_LES, WALL_HALFWAY>(emit) : wind_kernel<T, COLLIDE_BGK, WALL_HALFWAY>(emit));
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride,
-                               (const T *)b->wind_v, rev);
-        } else if (b->ibb) {
-            const auto k_step = b->les ? (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_LES> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_LES>)
-                                       : (emit ? k_step_ibb_batch<T, true, WT_LOADMODE, COLLIDE_BGK> : k_step_ibb_batch<T, false, WT_LOADMODE, COLLIDE_BGK>);
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, (const T *)b->wq, b->q_stride, rev);
-        } else if (b->les) {
-            const auto k_step = emit ? k_step_les_batch<T, true, WT_LOADMODE> : k_step_les_batch<T, false, WT_LOADMODE>;
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, (const T *)b->les_c, rev);
-        } else {
-            const auto k_step = emit ? k_step_batch<T, true, WT_LOADMODE> : k_step_batch<T, false, WT_LOADMODE>;
-            hipLaunchKernelGGL(k_step, grid, block, 0, b->st, fs, fd, macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles,
-                               b->tiles_per_col, b->g, b->ms, (const T *)b->params, rev);
-        }
+        with_step_variant(b, emit, [&](auto EMIT, auto COLL, auto WALL, auto FAR) {
+            hipLaunchKernelGGL((k_step_batch<T, EMIT != 0, WT_LOADMODE, COLL, WALL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
+                               fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
+                               b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
+        });
     });
 }
 

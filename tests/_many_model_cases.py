@@ -45,10 +45,10 @@ HALF_CASES = ("67-96x48-f32", "67-24x300-f32")
 # family -> (its models, the cases it runs on, the step kernel)
 FAMILIES = {
     "half": (Model(stored=True, wind=True, les=True), HALF_CASES),                              # k_step_half_batch<COLLIDE_LES, FAR_INCLINED>
-    "half-trt": (Model(stored=True, trt=True, wind=True, les=True), HALF_CASES),                # k_step_trt_half_batch<COLLIDE_TRT_LES>
-    "trt": (Model(trt=True, wind=True, les=True, ibb=True), mc.BODY),                           # k_step_trt_batch
-    "profile": (Model(profile=True, trt=True, les=True, ibb=True), ("67-96x48-f32", "35-24x140-f64")),      # k_step_profile_batch (TRT, interpolated)
-    "profile-plain": (Model(profile=True), ("67-24x300-f32",)),                                 # k_step_profile_batch (BGK, half-way walls)
+    "half-trt": (Model(stored=True, trt=True, wind=True, les=True), HALF_CASES),                # k_step_half_batch<COLLIDE_TRT_LES, FAR_INCLINED>
+    "trt": (Model(trt=True, wind=True, les=True, ibb=True), mc.BODY),                           # k_step_batch<COLLIDE_TRT_LES, WALL_INTERP, FAR_INCLINED>
+    "profile": (Model(profile=True, trt=True, les=True, ibb=True), ("67-96x48-f32", "35-24x140-f64")),      # k_step_batch<FAR_PROFILE> (TRT, interpolated)
+    "profile-plain": (Model(profile=True), ("67-24x300-f32",)),                                 # k_step_batch<FAR_PROFILE> (BGK, half-way walls)
     "max-half-trt": (Model(stored=True, trt=True, wind=True, les=True), (mc.MAX,)),             # both at WTP_MAX_MEMBERS
     "max-profile": (Model(profile=True, trt=True, les=True), (mc.MAX,)),
 }

@@ -2,7 +2,7 @@
 tests/test_gpu_polar_net.py compares the kernels with.  Test infrastructure only.
 
 A case is a lattice (chosen by step_tile's tile classes, as in tests/test_gpu_polar_les.py), a configuration is a pair of wall rule
-and collision: "les" (half-way walls, k_step_les_batch), "ibb-bgk" and "ibb-les" (interpolated walls, k_step_ibb_batch with either
+and collision: "les" (half-way walls, k_step_batch with COLLIDE_LES), "ibb-bgk" and "ibb-les" (interpolated walls, k_step_batch with WALL_INTERP and either
 collision).  Every batch has the same three kinds of member: one driven onto the net with a weak model (cs > 0), one driven onto it
 with cs = 0, one healthy.  These cases reach the net by stepping from equilibrium, as a sweep does: tau - 0.5 of 4e-4 and an inflow
 of 0.31 against the velocity bound of 0.35, started impulsively on a body of blocks, slots and single cells.  (They were written when

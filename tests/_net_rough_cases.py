@@ -1,7 +1,7 @@
 """Every batch step kernel on the stability net from a rough start: the cases, their inputs and the reference runs that
 tests/test_polar_net_rough_host.py pins and tests/test_gpu_polar_net_rough.py compares the kernels with.  Test infrastructure only.
 
-_net_cases reaches the net by 170 steps from equilibrium and covers k_step_les_batch and k_step_ibb_batch; the rough-start cases of
+_net_cases reaches the net by 170 steps from equilibrium and covers k_step_batch with the Smagorinsky collision and with interpolated walls; the rough-start cases of
 _restart_cases and _trt_cases cover every step kernel and stay off the net on purpose.  Here the two meet: the variants, members and
 steppers of _restart_cases and _trt_cases (all 24 model combinations), the lattices they share with _net_cases, and _net_cases' masks and
 wall distances (net_mask keeps TILE_FAST tiles up- and downstream of the body).  Members 0 and 2 start from a rough state whose noise

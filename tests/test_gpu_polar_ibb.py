@@ -1,4 +1,4 @@
-"""GPU: interpolated bounce-back of batched sweeps (k_step_ibb_batch, k_mex_ibb_batch, wtp_enable_ibb, wtp_set_wall_q) against its
+"""GPU: interpolated bounce-back of batched sweeps (k_step_batch with WALL_INTERP, k_mex_ibb_batch, wtp_enable_ibb, wtp_set_wall_q) against its
 definition in NumPy (tests/_ibb_reference.py).
 
 There is no tolerance on the state: the kernel and the reference round every operation of the wall rule once, in the same order, so

@@ -1,4 +1,4 @@
-"""GPU: the Smagorinsky subgrid viscosity of batched sweeps (k_step_les_batch, wtp_enable_les) against its definition in NumPy
+"""GPU: the Smagorinsky subgrid viscosity of batched sweeps (k_step_batch with COLLIDE_LES, wtp_enable_les) against its definition in NumPy
 (tests/_les_reference.py).
 
 There is no tolerance on the state: the kernel and the reference round every operation of the collision once, in the same order,

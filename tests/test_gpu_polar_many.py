@@ -11,7 +11,7 @@ batch, _wind_reference over _ibb_reference / _les_reference with the models on),
 Loads, Mex and MexIbb, the surface and mean sums are the references' bits.
 
 The lookups by member index of the features that came after this file live in tests/test_gpu_polar_many_models.py, on the same
-batches (tests/_many_model_cases.py): the member walk of the half kernels (k_step_half_batch, k_step_trt_half_batch, init_half,
+batches (tests/_many_model_cases.py): the member walk of the half kernels (k_step_half_batch, init_half,
 k_mex_half_batch) and the lattice counted in halves, lam[m], zero_v and the per-member tau check of the two-relaxation-time collision,
 prof + m * p_stride, the (first, count) loop of wtp_set_far_profile and prof_set[m] of the far-field profile, and the member offsets of
 wtp_write_f / wtp_write_stored, of the sums they clear and of state() / restore().  That file imports this one's assertion helpers.

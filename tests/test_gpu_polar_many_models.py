@@ -2,8 +2,8 @@
 (libwtpolar.so) at many members, every member against its own reference: the batches of tests/test_gpu_polar_many.py (67, 35 and 1024
 members) under the families of tests/_many_model_cases.py, every member with a magic number, a rough start state and far-field tables of
 its own (tests/test_polar_many_models_host.py shows on the references alone that a member which ran with its neighbour's would be seen).
-What is exercised is every lookup by the member index that these four features added: the member walk of k_step_half_batch and
-k_step_trt_half_batch into params, cles, vwind, lam, the lattice counted in halves, the mask and the macro planes; init_half's and
+What is exercised is every lookup by the member index that these four features added: the member walk of k_step_half_batch
+into params, cles, vwind, lam, the lattice counted in halves, the mask and the macro planes; init_half's and
 k_mex_half_batch's; fptr<half_t>(b, cur, member) of the reads and writes of a half batch; lam[m], zero_v and the per-member tau check of
 TRT; prof + m * p_stride, the (first, count) loop of wtp_set_far_profile, prof_set[m] and the Python side's tables behind state(); the
 member offset of wtp_write_f / wtp_write_stored and of the sums they clear.

@@ -1,5 +1,5 @@
 """GPU: the step kernels of batched sweeps at the stability net: the density clamp (0.5 / 2.0) and the velocity clamp (0.35) under the
-Smagorinsky collision (k_step_les_batch) and under interpolated walls with either collision (k_step_ibb_batch), in the straight-line
+Smagorinsky collision (k_step_batch with COLLIDE_LES) and under interpolated walls with either collision (WALL_INTERP), in the straight-line
 path of TILE_FAST tiles and in site_general, against the NumPy references of tests/_net_cases.py.
 
 There is no tolerance on the state: the kernels and the references round every operation once, in the same order, so populations

@@ -1,7 +1,7 @@
 """GPU: every batch step kernel on the stability net from a rough start: the density clamp (0.5 / 2.0) and the velocity clamp (0.35) in
 collide, collide_les and collide_trt, in the straight-line path of TILE_FAST tiles and in site_general, with half-way and interpolated
-walls, the inclined free stream and half storage (k_step_batch, k_step_les_batch, k_step_ibb_batch, k_step_wind_batch, k_step_trt_batch,
-k_step_half_batch, k_step_trt_half_batch), against the NumPy references of tests/_net_rough_cases.py.
+walls, the inclined free stream and half storage (the instantiations of k_step_batch and
+k_step_half_batch), against the NumPy references of tests/_net_rough_cases.py.
 
 There is no tolerance on the state: the kernels and the references round every operation once, in the same order, so populations (or
 stored halves) and macroscopic fields are the same bits at every checkpoint, clamped cells included, and the event counts are equal.

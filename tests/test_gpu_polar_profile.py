@@ -1,4 +1,4 @@
-"""GPU: the prescribed far-field profile of batched sweeps (k_step_profile_batch, wtp_enable_far_profile, wtp_set_far_profile) against its
+"""GPU: the prescribed far-field profile of batched sweeps (k_step_batch with FAR_PROFILE, wtp_enable_far_profile, wtp_set_far_profile) against its
 definition in NumPy (tests/_profile_reference.py), on the cases of tests/_profile_cases.py.
 
 There is no tolerance on the state: the kernel and the reference form the far field by the same operations, rounded once each, so

@@ -1,4 +1,4 @@
-"""GPU: the two-relaxation-time collision of batched sweeps (k_step_trt_batch, k_step_trt_half_batch, wtp_enable_trt) against its
+"""GPU: the two-relaxation-time collision of batched sweeps (k_step_batch and k_step_half_batch with COLLIDE_TRT / COLLIDE_TRT_LES, wtp_enable_trt) against its
 definition in NumPy (tests/_trt_reference.py), on the cases of tests/_trt_cases.py (tests/test_polar_trt_host.py shows on the references
 that they are sensitive).
 

@@ -1,4 +1,4 @@
-"""GPU: the inclined free stream of batched sweeps (k_step_wind_batch, k_fill_wind, wtp_enable_wind) against its definition in NumPy
+"""GPU: the inclined free stream of batched sweeps (k_step_batch with FAR_INCLINED, k_fill_wind, wtp_enable_wind) against its definition in NumPy
 (tests/_wind_reference.py).
 
 There is no tolerance on the state: the kernel and the reference form the far field by the same operations, rounded once each, so

@@ -209,12 +209,14 @@ def polar_isa():
 def test_half_kernels_have_their_instantiations_and_no_scratch(polar_isa):
     """k_step_half_batch: emitting and not, BGK and Smagorinsky, axial and inclined.  No spill."""
     chk, files = polar_isa
+    family = lambda v: v[0] == "half" and v[3] in (_polar_isa.BGK, _polar_isa.LES)      # noqa: E731
+    step = _polar_isa.step_kernels(chk, files, family)
     seen = {}
     for f in files:
         for name, r in chk.resources(f).items():
-            if "k_step_half_batch" in name or "k_mex_half_batch" in name or "k_fill_half" in name:
+            if name in step or "k_mex_half_batch" in name or "k_fill_half" in name:
                 seen[name] = r
                 assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: v.get("num_vgpr") for k, v in seen.items()})
-    assert sum("k_step_half_batch" in n for n in seen) == 8, sorted(seen)
+    assert sum(n in step for n in seen) == 8, sorted(seen)
     assert sum("k_mex_half_batch" in n for n in seen) == 1 and sum("k_fill_half" in n for n in seen) == 1, sorted(seen)

@@ -139,11 +139,24 @@ def polar_isa():
 def test_batched_kernels_have_no_scratch_and_no_store_hazard(polar_isa):
     chk, files = polar_isa
     assert files
+    plain = _polar_isa.step_kernels(chk, files, lambda v: v[0] == "native" and v[3:] == (_polar_isa.BGK, _polar_isa.HALFWAY, _polar_isa.AXIAL))
     seen = []
     for f in files:
         for name, r in chk.resources(f).items():
-            if "k_step_batch" in name or "k_forces_batch" in name:
+            if name in plain or "k_forces_batch" in name:
                 seen.append(name)
                 assert r.get("private_seg_size", 0) == 0, (name, r)
         assert chk.check(f)[1] == []
-    assert sum("k_step_batch" in n for n in seen) == 4 and sum("k_forces_batch" in n for n in seen) == 2, seen
+    assert sum(n in plain for n in seen) == 4 and sum("k_forces_batch" in n for n in seen) == 2, seen
+
+
+def test_the_step_kernels_are_exactly_the_built_variants(polar_isa):
+    """k_step_batch and k_step_half_batch hold the 80 + 12 variants that wtp_step can select, each once: no combination dropped, none added,
+    and no step kernel of another name."""
+    chk, files = polar_isa
+    names = [n for f in files for n in chk.resources(f) if "k_step" in n]
+    variants = [_polar_isa.step_variant(n) for n in names]
+    assert None not in variants, [n for n, v in zip(names, variants) if v is None]
+    assert len(variants) == len(set(variants)) == 92
+    assert set(variants) == _polar_isa.step_variants_built()
+    assert sum(v[0] == "native" and v[5] == _polar_isa.PROFILE for v in variants) == 32

@@ -221,12 +221,10 @@ def polar_isa():
 def test_ibb_kernels_have_their_instantiations_and_no_scratch(polar_isa):
     """The step: fp32 and fp64, emitting and not, BGK and Smagorinsky; the momentum exchange: fp32 and fp64.  No spill."""
     chk, files = polar_isa
-    step, mex = {}, {}
-    for f in files:
-        for name, r in chk.resources(f).items():
-            for needle, seen in (("k_step_ibb_batch", step), ("k_mex_ibb_batch", mex)):
-                if needle in name:
-                    seen[name] = r
-                    assert r.get("private_seg_size", 0) == 0, (name, r)
+    family = lambda v: v[0] == "native" and v[4:] == (_polar_isa.INTERP, _polar_isa.AXIAL)      # noqa: E731
+    step = {name: r for name, (_, r) in _polar_isa.step_kernels(chk, files, family).items()}
+    mex = {name: r for f in files for name, r in chk.resources(f).items() if "k_mex_ibb_batch" in name}
+    for name, r in {**step, **mex}.items():
+        assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: v.get("num_vgpr") for k, v in {**step, **mex}.items()})
     assert len(step) == 8 and len(mex) == 2, (sorted(step), sorted(mex))

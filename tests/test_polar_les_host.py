@@ -152,11 +152,9 @@ def polar_isa():
 def test_les_step_has_four_instantiations_and_no_scratch(polar_isa):
     """fp32 and fp64, emitting and not; no spill: the per-site relaxation time costs registers, not scratch."""
     chk, files = polar_isa
-    seen = {}
-    for f in files:
-        for name, r in chk.resources(f).items():
-            if "k_step_les_batch" in name:
-                seen[name] = r
-                assert r.get("private_seg_size", 0) == 0, (name, r)
+    family = lambda v: v[0] == "native" and v[3:] == (_polar_isa.LES, _polar_isa.HALFWAY, _polar_isa.AXIAL)      # noqa: E731
+    seen = {name: r for name, (_, r) in _polar_isa.step_kernels(chk, files, family).items()}
+    for name, r in seen.items():
+        assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: v.get("num_vgpr") for k, v in seen.items()})
     assert len(seen) == 4, sorted(seen)

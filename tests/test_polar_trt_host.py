@@ -163,21 +163,20 @@ def test_equilibrium_case_is_finite_off_the_net_and_not_bgk(name):
 
 # ---- the kernels' code objects -------------------------------------------------------------------
 def test_trt_step_kernels_are_built_and_have_no_scratch():
-    """k_step_trt_batch: fp32 and fp64, emitting and not, without and with the Smagorinsky model, half-way and interpolated walls (16);
-    k_step_trt_half_batch: emitting and not, without and with the model (4).  No spill; fp32 within 5 waves' 96 VGPRs, fp64 within 4 waves' 128."""
+    """k_step_batch with the two-relaxation-time collisions and the inclined far field: fp32 and fp64, emitting and not, without and with the
+    Smagorinsky model, half-way and interpolated walls (16); k_step_half_batch with them: emitting and not, without and with the model (4).
+    No spill; fp32 within 5 waves' 96 VGPRs, fp64 within 4 waves' 128."""
     import _polar_isa
     chk, files = _polar_isa.polar_isa()
-    seen = {}
-    for f in files:
-        for name, r in chk.resources(f).items():
-            if "k_step_trt" in name:
-                seen[name] = r
-                assert r.get("private_seg_size", 0) == 0, (name, r)
-    print({k: v.get("num_vgpr") for k, v in seen.items()})
-    tiled = {k: v for k, v in seen.items() if "k_step_trt_batch" in k}
-    assert len(tiled) == 16 and sum("k_step_trt_half_batch" in k for k in seen) == 4, sorted(seen)
-    for name, r in tiled.items():
-        assert r["num_vgpr"] <= (96 if "k_step_trt_batchIf" in name else 128), (name, r)
+    family = lambda v: v[3] in (_polar_isa.TRT, _polar_isa.TRT_LES) and v[5] == _polar_isa.INCLINED      # noqa: E731
+    seen = _polar_isa.step_kernels(chk, files, family)
+    for name, (_, r) in seen.items():
+        assert r.get("private_seg_size", 0) == 0, (name, r)
+    print({k: r.get("num_vgpr") for k, (_, r) in seen.items()})
+    tiled = {k: (v, r) for k, (v, r) in seen.items() if v[0] == "native"}
+    assert len(tiled) == 16 and sum(v[0] == "half" for v, _ in seen.values()) == 4, sorted(seen)
+    for name, (v, r) in tiled.items():
+        assert r["num_vgpr"] <= (96 if v[1] == "f" else 128), (name, r)
 
 
 # ---- 6. the wall position ----------------------------------------------------------------------

@@ -27,42 +27,42 @@ measured) and what the added time per sample makes of them against 8 TB/s.
 
     python tools/polar_bench.py --les CS [--repeats 5] [the options of the first form]
 
-The batched step with the Smagorinsky subgrid viscosity (wtp_enable_les, Smagorinsky constant CS in every member): k_step_les_batch in
-place of k_step_batch.  The line gives `repeats` timings of the same window and their median; without --les the same repeats time the
+The batched step with the Smagorinsky subgrid viscosity (wtp_enable_les, Smagorinsky constant CS in every member): the COLLIDE_LES
+instantiation of k_step_batch in place of the plain one.  The line gives `repeats` timings of the same window and their median; without --les the same repeats time the
 BGK step, so that two lines compare.  No sequential leg: a single handle has no such collision.  With --loads / --mex / --mean the
 model is on in both variants of those protocols.
 
     python tools/polar_bench.py --ibb [--les CS] [--repeats 5] [the options of the first form]
 
 The batched step with interpolated bounce-back (wtp_enable_ibb, every member with the wall distances of its own airfoil):
-k_step_ibb_batch in place of k_step_batch (or, with --les, of k_step_les_batch).  The line has the shape of --les's; no sequential
-leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
+the WALL_INTERP instantiation of k_step_batch with the collision the other switches select.  The line has the shape of --les's; no
+sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
 
     python tools/polar_bench.py --wind [--les CS] [--ibb] [--repeats 5] [the options of the first form]
 
-The batched step with an inclined free stream (wtp_enable_wind): k_step_wind_batch in place of the kernel the other switches select.
+The batched step with an inclined free stream (wtp_enable_wind): the FAR_INCLINED instantiation of the kernel the other switches select.
 The masks stay those of the other forms, so that the tile classes are the same; member m's cross-flow is U0 sin(alpha_m).  The line
 has the shape of --les's; no sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.
 
     python tools/polar_bench.py --storage half [--les CS] [--wind] [--repeats 5] [the options of the first form]
 
-The batched step of a half batch (PolarEngine(storage="half")): k_step_half_batch in place of the kernel the other switches select,
-on lattices of binary16 deviations from the weights.  The line has the shape of --les's and counts 37 B per site (nine 2-byte loads,
+The batched step of a half batch (PolarEngine(storage="half")): k_step_half_batch, with the collision and the far field the other switches
+select, on lattices of binary16 deviations from the weights.  The line has the shape of --les's and counts 37 B per site (nine 2-byte loads,
 nine 2-byte stores and the mask byte) in place of 72; no sequential leg.  Not with --ibb.  With --loads / --mex / --mean the batch is
 a half batch in both variants of those protocols (and --mex then times k_mex_half_batch).
 
     python tools/polar_bench.py --trt MAGIC [--les CS] [--ibb] [--wind] [--storage half] [--repeats 5] [the options of the first form]
 
-The batched step with the two-relaxation-time collision (wtp_enable_trt, magic number MAGIC in every member): k_step_trt_batch (in a
-half batch k_step_trt_half_batch) in place of the kernel the other switches select.  The line has the shape of --les's; no sequential
+The batched step with the two-relaxation-time collision (wtp_enable_trt, magic number MAGIC in every member): the COLLIDE_TRT (with --les
+COLLIDE_TRT_LES) instantiation of k_step_batch, in a half batch of k_step_half_batch, with the inclined far field.  The line has the shape of --les's; no sequential
 leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols.  Without --trt, --lib may name a
 build from before the collision existed, so that a parent commit's library is timed by the same script.
 
     python tools/polar_bench.py --profile [--les CS] [--ibb] [--wind] [--trt MAGIC] [--repeats 5] [the options of the first form]
 
 The batched step with a prescribed far-field profile (wtp_enable_far_profile; every member with the tables of its free stream plus a
-point vortex at the quarter chord that induces 0.01 at the nearest far-field cell): k_step_profile_batch in place of the kernel the
-other switches select.  The line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --profile,
+point vortex at the quarter chord that induces 0.01 at the nearest far-field cell): the FAR_PROFILE instantiation of the kernel the other
+switches select.  The line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --profile,
 --lib may name a build from before the entry points existed.
 
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
