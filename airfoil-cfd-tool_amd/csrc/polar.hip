@@ -64,6 +64,11 @@
 // while a member has none.  Native storage only.  A batch that has it off launches the kernels it always launched, with the arguments
 // they always had.
 //
+// The device-side far-field vortex (wtp_enable_far_vortex) is an owner of those tables: while it is on, the stepping loop follows every
+// `every`-th step by k_forces_batch into a scratch row and one launch of k_far_vortex, which moves every member's vortex and source
+// strength by the force, clips them and rebuilds the member's three tables, all in stream order, and logs the update.  The step kernels
+// do not know who wrote the tables.  A batch that has it off launches the kernels it always launched.
+//
 // Every variant above is an instantiation of its own, so a batch runs the code object its switches select and no other.  What the
 // variants share is source text: one site (site_general, kernels.hpp, for every storage), one tiled step kernel and one half step kernel
 // with one selection and one launch on the host (with_step_variant, step_model), one momentum-exchange body (mex_member, with a link
@@ -142,6 +147,11 @@ struct SampleTable {
     void release() { for (void *&p : col) { if (p) (void)hipFree(p); p = nullptr; } }
 };
 
+// The per-batch settings of the device-side far-field vortex (include/wt_polar.h "Device-side far-field vortex"), by value to its kernel:
+// den = (2 pi) u_ref and bound = min(xc - 0.5, yc - 0.5, NY - 0.5 - yc), both formed on the host.
+struct VortexSet { double relax, den, bound, xc, yc; int with_source; };
+static const int kVortexBlock = 256;       // table entries (lanes) of one k_far_vortex block
+
 struct wtp_batch {
     int nx = 0, ny = 0, dtype = WT_F32, device = 0, members = 0, cap = 0;
     size_t esz = 4;
@@ -178,6 +188,19 @@ struct wtp_batch {
     long p_stride = 0;
     int p_nxp = 0;                       // elements per plane of `bottom` and `top`: NX rounded up to 64
     std::vector<uint8_t> prof_set;       // [B]: the member has been given a profile (wtp_set_far_profile)
+    // device-side far-field vortex (wtp_enable_far_vortex); every pointer is null until then
+    bool vortex = false;
+    VortexSet v_set{};                   // the per-batch settings the update kernel reads
+    int v_every = 0;
+    long long v_after = 0, v_since = 0;  // the first absolute step count that may update; steps enqueued while the model is on since it was enabled
+    double *v_member = nullptr;          // [4][B]: u_far, v_far, cos_a, sin_a
+    double *v_str = nullptr;             // [2][2][B]: the strengths and the sources, double-buffered; v_str[v_par] holds the current ones
+    int v_par = 0;
+    void *v_forces = nullptr;            // [4][B] of 8 bytes: the scratch row of the update's force read-out (fx, fy, surf, rev)
+    double *v_log = nullptr;             // [4][v_cap][B]: fx, fy, strength, source of every update
+    int32_t *v_clip = nullptr;           // [v_cap][B]: the update clipped
+    int v_cap = 0;
+    std::vector<int64_t> v_step;         // step count of each log row held
     ForcePartial *partials = nullptr;    // [B][nb]
     unsigned int *tickets = nullptr;     // [B]: blocks of a member's reduction done (reset by its last block)
     SampleTable forces;                  // fx, fy (double), surf, rev (long long)
@@ -785,6 +808,77 @@ __global__ __launch_bounds__(256) void k_mean_batch(const T *__restrict__ macro,
     for (int k = 0; k < kMeanPlanes; k++) *reinterpret_cast<RowRun<double, R> *>(acc + k * ap) = s[k];
 }
 
+// The device-side far-field vortex (include/wt_polar.h "Device-side far-field vortex") of every member in one launch, behind
+// k_forces_batch: grid (ceil((NY + 2 NX) / kVortexBlock), B), blockIdx.y the member, one lane per table entry, the entries in the order
+// left[0 .. NY), bottom[0 .. NX), top[0 .. NX), so that consecutive lanes write consecutive entries of a table plane.  Definition, all in
+// double, one rounding per operation, left to right as written, no contraction, IEEE division and square root:
+//   Update (UPDATE only) of member m from (fx, fy), wtp_forces' values of the last emitted state, with c = cos_a[m], s = sin_a[m]:
+//     drag = fx*c + fy*s;   lift = (-fx)*s + fy*c
+//     ts   = lift/den;      tq = with_source ? drag/den : 0.0
+//     ns   = strength + relax*(ts - strength);   nq = source + relax*(tq - source)
+//     speed   = sqrt(ns*ns + nq*nq)/bound
+//     clipped = speed > 0.1;   scale = clipped ? 0.1/speed : 1.0
+//     strength = ns*scale;  source = nq*scale
+//   Tables, for the cell (i, j) of an entry (left: (0, j); bottom: (i, 0); top: (i, NY-1)), each value rounded to T once:
+//     dx = i + 0.5 - xc;  dy = j + 0.5 - yc;  r2 = dx*dx + dy*dy
+//     ux = u_far + strength*dy/r2 + source*dx/r2
+//     uy = v_far - strength*dx/r2 + source*dy/r2
+//     rho = 1 + 1.5*((u_far*u_far + v_far*v_far) - (ux*ux + uy*uy))
+// The update is scalar work that every lane repeats for its member: the same operations on the same inputs, the same bits in every
+// block, so that no block waits for another.  The strengths are double-buffered by update parity: every block reads the pair of
+// `cur`, which an earlier launch wrote, and block 0 of the member alone writes the new pair to `next` and the log row, so no block
+// reads what another replaces.  No atomics, no fence.  Without UPDATE the tables are built from `cur` as it is (wtp_enable_far_vortex,
+// wtp_set_far_vortex) and fx, fy, next and the log are not touched.  member: [4][B] u_far, v_far, cos_a, sin_a; cur, next: [2][B]
+// strength, source; log: row r of column c (fx, fy, strength, source) at log[c * log_col + m]; clip[m].  Entries past NY of `left` and
+// past NX of `bottom` and `top` are not written and keep their +0.
+template <typename T, bool UPDATE>
+__global__ __launch_bounds__(kVortexBlock) void k_far_vortex(T *__restrict__ prof, long pstride, long pitch, int nxp, int nx, int ny, VortexSet v,
+                                                             const double *__restrict__ member, const double *__restrict__ fx,
+                                                             const double *__restrict__ fy, const double *__restrict__ cur,
+                                                             double *__restrict__ next, double *__restrict__ log, long log_col,
+                                                             int32_t *__restrict__ clip)
+{
+    const long m = blockIdx.y, B = gridDim.y;
+    const double u_far = member[m], v_far = member[B + m];
+    double strength = cur[m], source = cur[B + m];
+    if (UPDATE) {
+        const double c = member[2 * B + m], s = member[3 * B + m];
+        const double f_x = fx[m], f_y = fy[m];
+        const double drag = f_x * c + f_y * s, lift = (-f_x) * s + f_y * c;
+        const double ts = lift / v.den, tq = v.with_source ? drag / v.den : 0.0;
+        const double ns = strength + v.relax * (ts - strength), nq = source + v.relax * (tq - source);
+        const double speed = sqrt(ns * ns + nq * nq) / v.bound;
+        const bool clipped = speed > 0.1;
+        const double scale = clipped ? 0.1 / speed : 1.0;
+        strength = ns * scale;
+        source = nq * scale;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            next[m] = strength; next[B + m] = source;
+            log[m] = f_x; log[log_col + m] = f_y; log[2 * log_col + m] = strength; log[3 * log_col + m] = source;
+            clip[m] = clipped ? 1 : 0;
+        }
+    }
+    int e = (int)blockIdx.x * kVortexBlock + (int)threadIdx.x;     // the entry: left, then bottom, then top
+    T *tab = prof + m * pstride;
+    long ps = pitch;                                                // elements between the planes of the entry's table
+    int i = 0, j = e;
+    if (e >= ny) {
+        e -= ny;
+        if (e >= 2 * nx) return;
+        const bool top = e >= nx;
+        if (top) e -= nx;
+        tab += 3 * pitch + (top ? 3 * (long)nxp : 0);
+        ps = nxp;
+        i = e; j = top ? ny - 1 : 0;
+    }
+    const double dx = ((double)i + 0.5) - v.xc, dy = ((double)j + 0.5) - v.yc;
+    const double r2 = dx * dx + dy * dy;
+    const double ux = (u_far + strength * dy / r2) + source * dx / r2;
+    const double uy = (v_far - strength * dx / r2) + source * dy / r2;
+    const double rho = 1.0 + 1.5 * ((u_far * u_far + v_far * v_far) - (ux * ux + uy * uy));
+    tab[e] = (T)rho; tab[ps + e] = (T)ux; tab[2 * ps + e] = (T)uy;
+}
+
 // ------------------------------------------------------------------------------------------
 // life cycle
 // ------------------------------------------------------------------------------------------
@@ -811,7 +905,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->v_member, b->v_str, b->v_forces, b->v_log, b->v_clip, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
@@ -900,7 +994,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile, device-side far-field vortex)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1088,6 +1182,8 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
     b->macro_stale = false;
     b->steps_done = 0;
     b->h_step.clear();
+    b->v_since = 0;                              // (the far-field vortex keeps its strengths)
+    b->v_step.clear();
     return clear_sums(b, 0, b->members);
 }
 
@@ -1125,14 +1221,52 @@ static int upload_params(wtp_batch *b, const double *tau, const double *u0)
     return WT_OK;
 }
 
+// wt_forces of every member on the last emitted state, into four [B] arrays of the device.
+template <typename T>
+static int launch_forces_to(wtp_batch *b, double *fx, double *fy, long long *surf, long long *rev)
+{
+    hipLaunchKernelGGL(k_forces_batch<T>, dim3((unsigned)b->nb, (unsigned)b->members), dim3(256), 0, b->st,
+                       (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, b->nb, b->partials, b->tickets, fx, fy, surf, rev);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 template <typename T>
 static int launch_forces(wtp_batch *b, int row)
 {
     const SampleTable &t = b->forces;
-    hipLaunchKernelGGL(k_forces_batch<T>, dim3((unsigned)b->nb, (unsigned)b->members), dim3(256), 0, b->st,
-                       (const T *)b->macro, (const uint8_t *)b->mask, b->g, b->ms, b->nb, b->partials, b->tickets,
-                       t.at<double>(0, row), t.at<double>(1, row), t.at<long long>(2, row), t.at<long long>(3, row));
+    return launch_forces_to<T>(b, t.at<double>(0, row), t.at<double>(1, row), t.at<long long>(2, row), t.at<long long>(3, row));
+}
+
+// The far-field vortex's kernel over every table entry of every member.  UPDATE: the strengths of v_str[v_par] move by the forces in
+// v_forces into the other half, with log row `row`, and the tables follow the new ones (the caller flips v_par); else the tables are
+// built from v_str[v_par] as it is.
+template <typename T, bool UPDATE>
+static int launch_far_vortex(wtp_batch *b, int row)
+{
+    const size_t B = (size_t)b->members;
+    const int entries = b->ny + 2 * b->nx;
+    const double *forces = (const double *)b->v_forces;
+    hipLaunchKernelGGL((k_far_vortex<T, UPDATE>), dim3((unsigned)((entries + kVortexBlock - 1) / kVortexBlock), (unsigned)B), dim3(kVortexBlock), 0, b->st,
+                       (T *)b->prof, b->p_stride, b->g.pitch, b->p_nxp, b->nx, b->ny, b->v_set, (const double *)b->v_member, forces, forces + B,
+                       (const double *)(b->v_str + (size_t)b->v_par * 2 * B), b->v_str + (size_t)(1 - b->v_par) * 2 * B,
+                       UPDATE ? b->v_log + (size_t)row * B : nullptr, (long)b->v_cap * (long)B, UPDATE ? b->v_clip + (size_t)row * B : nullptr);
     HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+// One update of the far-field vortex from the last emitted state, logged as row v_step.size() with the current step count: the force
+// read-out into the update's own scratch row, then the update and the tables.  The caller has checked that the log has room.
+template <typename T>
+static int far_vortex_update_now(wtp_batch *b)
+{
+    const size_t B = (size_t)b->members;
+    double *f = (double *)b->v_forces;
+    long long *n = (long long *)b->v_forces;
+    WT_TRY(launch_forces_to<T>(b, f, f + B, n + 2 * B, n + 3 * B));
+    WT_TRY((launch_far_vortex<T, true>(b, (int)b->v_step.size())));
+    b->v_par = 1 - b->v_par;
+    b->v_step.push_back(b->steps_done);
     return WT_OK;
 }
 
@@ -1234,23 +1368,38 @@ static StepModel<T, COLL, WALL, FAR> step_model(const wtp_batch *b, int rev)
 
 // The stepping loop of wtp_step: which steps sample and which emit, the flip of the lattices, the step count and the history rows.
 // `launch(emit, rev)` enqueues one step of every member from the current lattice into the other; T is the type of the read-outs.
+// While the device-side far-field vortex is on, the step that brings `since` to a multiple of `every` at an absolute count of at least
+// `after` also emits and is followed, behind its sample, by the update of the strengths and the tables (far_vortex_update_now).
 template <typename T, typename Launch>
 static int step_loop(wtp_batch *b, int nsteps, int sample_every, Launch launch)
 {
     for (int s = 0; s < nsteps; s++) {
         const long long n = b->steps_done + 1;
         const bool sample = sample_every > 0 && n % sample_every == 0;
-        const bool emit = sample || s + 1 == nsteps;
+        const bool update = b->vortex && (b->v_since + 1) % b->v_every == 0 && n >= b->v_after;
+        const bool emit = sample || update || s + 1 == nsteps;
         launch(emit, (int)(b->steps_done & 1));
         HIP_TRY(hipGetLastError());
         b->cur = 1 - b->cur;
         b->steps_done = n;
+        if (b->vortex) b->v_since += 1;
         if (sample) {
             WT_TRY(sample_into<T>(b, (int)b->h_step.size()));
             b->h_step.push_back(n);
         }
+        if (update) WT_TRY(far_vortex_update_now<T>(b));
     }
     return WT_OK;
+}
+
+// The updates of the far-field vortex that the next nsteps steps hold: the s in [1, nsteps] with (since + s) % every == 0 and
+// steps_done + s >= after.
+static long long far_vortex_updates(const wtp_batch *b, int nsteps)
+{
+    if (!b->vortex) return 0;
+    const long long s0 = std::max<long long>(1, b->v_after - b->steps_done);
+    if (s0 > nsteps) return 0;
+    return (b->v_since + nsteps) / b->v_every - (b->v_since + s0 - 1) / b->v_every;
 }
 
 // The steps of a half batch: k_step_half_batch, with the fp32 read-outs.  wtp_enable_ibb and wtp_enable_far_profile refuse a half
@@ -1308,6 +1457,9 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
             return fail(WT_ERR_STATE, "%lld samples would overflow the history (%zu of %d rows held): read it and wtp_clear_history",
                         samples, b->h_step.size(), b->cap);
     }
+    if (const long long updates = far_vortex_updates(b, nsteps); (long long)b->v_step.size() + updates > b->v_cap)
+        return fail(WT_ERR_STATE, "%lld updates would overflow the far-field vortex's log (%zu of %d rows held): read it and wtp_clear_history",
+                    updates, b->v_step.size(), b->v_cap);
     HIP_TRY(hipSetDevice(b->device));
     if (b->dtype == WT_F32) {
         WT_TRY(upload_params<float>(b, tau, u0));
@@ -1393,7 +1545,7 @@ extern "C" int wtp_enable_far_profile(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
     if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
-    if (!on) { b->profile = false; return WT_OK; }       // (steps already enqueued were launched with the model on: stream order)
+    if (!on) { b->profile = false; b->vortex = false; return WT_OK; }       // (steps already enqueued were launched with the model on: stream order)
     HIP_TRY(hipSetDevice(b->device));
     if (!b->prof) {
         const int nxp = (b->nx + 63) / 64 * 64;
@@ -1462,8 +1614,195 @@ extern "C" int wtp_set_far_profile(wtp_batch *b, int first, int count, const voi
     if (first < 0 || count < 1 || first + count > b->members)
         return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
     if (!b->prof) return fail(WT_ERR_STATE, "the far-field profile has never been enabled (wtp_enable_far_profile)");
+    if (b->vortex) return fail(WT_ERR_STATE, "the device-side far-field vortex owns the tables (wtp_enable_far_vortex with every = 0 hands them back)");
     return b->dtype == WT_F32 ? set_far_profile_impl<float>(b, first, count, (const float *)left, (const float *)bottom, (const float *)top)
                               : set_far_profile_impl<double>(b, first, count, (const double *)left, (const double *)bottom, (const double *)top);
+}
+
+// The device layout of FarProfile of members [first, first + count) unpacked into wtp_set_far_profile's host layouts.
+template <typename T>
+static int read_far_profile_impl(wtp_batch *b, int first, int count, T *left, T *bottom, T *top)
+{
+    const size_t nx = (size_t)b->nx, ny = (size_t)b->ny;
+    const size_t pitch = (size_t)b->g.pitch, nxp = (size_t)b->p_nxp, elems = (size_t)far_profile_elems(b->g.pitch, b->p_nxp);
+    std::vector<T> host(elems);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    for (size_t k = 0; k < (size_t)count; k++) {
+        HIP_TRY(hipMemcpy(host.data(), reinterpret_cast<const T *>(b->prof) + (long)(first + (int)k) * b->p_stride, elems * sizeof(T), hipMemcpyDeviceToHost));
+        const T *d = host.data();
+        for (size_t p = 0; p < 3; p++) {
+            if (left) std::memcpy(left + (k * 3 + p) * ny, d + p * pitch, ny * sizeof(T));
+            if (bottom) std::memcpy(bottom + (k * 3 + p) * nx, d + 3 * pitch + p * nxp, nx * sizeof(T));
+            if (top) std::memcpy(top + (k * 3 + p) * nx, d + 3 * pitch + (3 + p) * nxp, nx * sizeof(T));
+        }
+    }
+    return WT_OK;
+}
+
+extern "C" int wtp_read_far_profile(wtp_batch *b, int first, int count, void *left, void *bottom, void *top)
+{
+    WT_TRY(check_batch(b));
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    if (!b->prof) return fail(WT_ERR_STATE, "the far-field profile has never been enabled (wtp_enable_far_profile)");
+    for (int m = first; m < first + count; m++)
+        if (!b->prof_set[(size_t)m]) return fail(WT_ERR_STATE, "member %d has no far-field profile (wtp_set_far_profile)", m);
+    return b->dtype == WT_F32 ? read_far_profile_impl<float>(b, first, count, (float *)left, (float *)bottom, (float *)top)
+                              : read_far_profile_impl<double>(b, first, count, (double *)left, (double *)bottom, (double *)top);
+}
+
+// ------------------------------------------------------------------------------------------
+// device-side far-field vortex (include/wt_polar.h "Device-side far-field vortex")
+// ------------------------------------------------------------------------------------------
+// A pair of strengths is inside the clip: finite, with sqrt(s*s + q*q)/bound <= 0.1.  False for a NaN.
+static bool far_vortex_pair_ok(double s, double q, double bound)
+{
+    return std::isfinite(s) && std::isfinite(q) && std::sqrt(s * s + q * q) / bound <= 0.1;
+}
+
+// All tables from the current strengths, behind whatever is enqueued.
+static int far_vortex_tables(wtp_batch *b)
+{
+    return b->dtype == WT_F32 ? launch_far_vortex<float, false>(b, 0) : launch_far_vortex<double, false>(b, 0);
+}
+
+extern "C" int wtp_enable_far_vortex(wtp_batch *b, int every, int64_t after, double relax, double u_ref, int with_source, double xc, double yc,
+                                     const double *u_far, const double *v_far, const double *cos_a, const double *sin_a, int log_cap)
+{
+    WT_TRY(check_batch(b));
+    if (every == 0) { b->vortex = false; return WT_OK; }      // (updates already enqueued were launched with the model on: stream order)
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    if (!b->profile) return fail(WT_ERR_STATE, "the far-field profile is not enabled (wtp_enable_far_profile)");
+    if (every < 0) return fail(WT_ERR_ARG, "every must be >= 0 (got %d)", every);
+    if (after < 0) return fail(WT_ERR_ARG, "after must be >= 0 (got %lld)", (long long)after);
+    if (!(relax > 0.0 && relax <= 1.0)) return fail(WT_ERR_ARG, "relax must be in (0, 1]");
+    if (!(u_ref > 0.0) || !std::isfinite(u_ref)) return fail(WT_ERR_ARG, "u_ref must be positive and finite");
+    if (with_source != 0 && with_source != 1) return fail(WT_ERR_ARG, "with_source must be 0 or 1 (got %d)", with_source);
+    if (!std::isfinite(xc) || !std::isfinite(yc)) return fail(WT_ERR_ARG, "xc and yc must be finite");
+    const double bound = std::min(std::min(xc - 0.5, yc - 0.5), ((double)b->ny - 0.5) - yc);
+    if (!(bound >= 1.0)) return fail(WT_ERR_ARG, "(xc, yc) must lie at least one cell from the nearest far-field cell centre (bound %g)", bound);
+    if (log_cap < 0) return fail(WT_ERR_ARG, "log_cap must be >= 0 (got %d)", log_cap);
+    if (!u_far || !v_far || !cos_a || !sin_a) return fail(WT_ERR_ARG, "u_far, v_far, cos_a or sin_a is null");
+    const size_t B = (size_t)b->members;
+    for (size_t m = 0; m < B; m++) {
+        if (!(u_far[m] * u_far[m] + v_far[m] * v_far[m] <= 0.25 * 0.25))       // (false for a NaN)
+            return fail(WT_ERR_ARG, "the far stream of member %d must be finite with a speed of at most 0.25", (int)m);
+        if (!(std::fabs(cos_a[m]) <= 1.0) || !(std::fabs(sin_a[m]) <= 1.0))
+            return fail(WT_ERR_ARG, "cos_a and sin_a of member %d must be finite and in [-1, 1]", (int)m);
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    std::vector<double> held(2 * B, 0.0);
+    if (b->v_str) {                              // the strengths are kept: they have to fit the new bound
+        HIP_TRY(hipStreamSynchronize(b->st));
+        HIP_TRY(hipMemcpy(held.data(), b->v_str + (size_t)b->v_par * 2 * B, 2 * B * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t m = 0; m < B; m++)
+            if (!far_vortex_pair_ok(held[m], held[B + m], bound))
+                return fail(WT_ERR_ARG, "the strengths held by member %d induce more than 0.1 at the new bound %g", (int)m, bound);
+    }
+    // the buffers: everything of the first enable at once, a log of another size on a later one
+    void *member = b->v_member, *str = b->v_str, *forces = b->v_forces, *log = nullptr, *clip = nullptr;
+    const size_t rows = (size_t)std::max(log_cap, 1);
+    hipError_t e = hipSuccess;
+    if (!member && e == hipSuccess) e = hipMalloc(&member, 4 * B * sizeof(double));
+    if (!str && e == hipSuccess) e = hipMalloc(&str, 4 * B * sizeof(double));
+    if (!forces && e == hipSuccess) e = hipMalloc(&forces, 4 * B * 8);
+    if ((!b->v_log || log_cap != b->v_cap) && e == hipSuccess) {
+        e = hipMalloc(&log, 4 * rows * B * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&clip, rows * B * sizeof(int32_t));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(b->st);      // updates already enqueued read the previous settings and write the previous log
+    if (e == hipSuccess && !b->v_str) e = hipMemcpy(str, held.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice);      // (zeros, into half 0)
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                 // (the batch goes on as it was: later launches must not see this error)
+        for (void *p : {b->v_member ? nullptr : member, b->v_str ? nullptr : str, b->v_forces ? nullptr : forces, log, clip}) if (p) (void)hipFree(p);
+        return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the far-field vortex's buffers could not be set up: %s", hipGetErrorString(e));
+    }
+    if (!b->v_str) b->v_par = 0;
+    b->v_member = (double *)member; b->v_str = (double *)str; b->v_forces = forces;
+    if (log) {
+        if (b->v_log) (void)hipFree(b->v_log);
+        if (b->v_clip) (void)hipFree(b->v_clip);
+        b->v_log = (double *)log; b->v_clip = (int32_t *)clip;
+    }
+    std::vector<double> set(4 * B);
+    for (size_t m = 0; m < B; m++) { set[m] = u_far[m]; set[B + m] = v_far[m]; set[2 * B + m] = cos_a[m]; set[3 * B + m] = sin_a[m]; }
+    HIP_TRY(hipMemcpy(b->v_member, set.data(), set.size() * sizeof(double), hipMemcpyHostToDevice));
+    b->v_set.relax = relax; b->v_set.den = (2.0 * M_PI) * u_ref; b->v_set.bound = bound; b->v_set.xc = xc; b->v_set.yc = yc;
+    b->v_set.with_source = with_source;
+    b->v_every = every; b->v_after = after; b->v_since = 0; b->v_cap = log_cap;
+    b->v_step.clear();
+    b->vortex = true;
+    b->prof_set.assign(B, 1);
+    return far_vortex_tables(b);
+}
+
+static int check_far_vortex(const wtp_batch *b)
+{
+    if (!b->vortex) return fail(WT_ERR_STATE, "the device-side far-field vortex is not enabled (wtp_enable_far_vortex)");
+    return WT_OK;
+}
+
+extern "C" int wtp_set_far_vortex(wtp_batch *b, const double *strength, const double *source)
+{
+    WT_TRY(check_batch(b));
+    if (!strength || !source) return fail(WT_ERR_ARG, "strength or source is null");
+    WT_TRY(check_far_vortex(b));
+    const size_t B = (size_t)b->members;
+    for (size_t m = 0; m < B; m++)
+        if (!far_vortex_pair_ok(strength[m], source[m], b->v_set.bound))
+            return fail(WT_ERR_ARG, "strength and source of member %d must be finite and induce at most 0.1 at the bound %g", (int)m, b->v_set.bound);
+    HIP_TRY(hipSetDevice(b->device));
+    std::vector<double> pair(2 * B);
+    for (size_t m = 0; m < B; m++) { pair[m] = strength[m]; pair[B + m] = source[m]; }
+    HIP_TRY(hipStreamSynchronize(b->st));        // updates already enqueued read and replace the previous values
+    HIP_TRY(hipMemcpy(b->v_str + (size_t)b->v_par * 2 * B, pair.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice));
+    return far_vortex_tables(b);
+}
+
+extern "C" int wtp_far_vortex(wtp_batch *b, double *strength, double *source)
+{
+    WT_TRY(check_batch(b));
+    if (!strength || !source) return fail(WT_ERR_ARG, "strength or source is null");
+    if (!b->v_str) return fail(WT_ERR_STATE, "the device-side far-field vortex has never been enabled (wtp_enable_far_vortex)");
+    const size_t B = (size_t)b->members;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const double *cur = b->v_str + (size_t)b->v_par * 2 * B;
+    HIP_TRY(hipMemcpy(strength, cur, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(source, cur + B, B * sizeof(double), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+extern "C" int wtp_far_vortex_update(wtp_batch *b)
+{
+    WT_TRY(check_batch(b));
+    WT_TRY(check_far_vortex(b));
+    WT_TRY(check_ready(b));
+    WT_TRY(check_macro(b));
+    if ((int)b->v_step.size() >= b->v_cap)
+        return fail(WT_ERR_STATE, "the far-field vortex's log is full (%d rows): read it and wtp_clear_history", b->v_cap);
+    HIP_TRY(hipSetDevice(b->device));
+    return b->dtype == WT_F32 ? far_vortex_update_now<float>(b) : far_vortex_update_now<double>(b);
+}
+
+extern "C" int wtp_far_vortex_log(wtp_batch *b, int first, int count, int64_t *step, double *fx, double *fy, double *strength, double *source,
+                                  int32_t *clipped)
+{
+    WT_TRY(check_batch(b));
+    const int held = (int)b->v_step.size();
+    if (first < 0 || count < 0 || first + count > held) return fail(WT_ERR_ARG, "rows [%d, %d) outside the %d held", first, first + count, held);
+    if (count > 0) {
+        const size_t B = (size_t)b->members, n = (size_t)count * B;
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipStreamSynchronize(b->st));
+        double *const dst[4] = {fx, fy, strength, source};
+        for (int c = 0; c < 4; c++)
+            if (dst[c]) HIP_TRY(hipMemcpy(dst[c], b->v_log + ((size_t)c * b->v_cap + first) * B, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (clipped) HIP_TRY(hipMemcpy(clipped, b->v_clip + (size_t)first * B, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (step) for (int r = 0; r < count; r++) step[r] = b->v_step[(size_t)(first + r)];
+    }
+    return held;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1561,6 +1900,7 @@ extern "C" int wtp_clear_history(wtp_batch *b)
 {
     WT_TRY(check_batch(b));
     b->h_step.clear();                           // (rows are only written by later, stream-ordered reductions)
+    b->v_step.clear();                           // (so are the rows of the far-field vortex's log)
     if (!b->loads && !b->mean) return WT_OK;
     HIP_TRY(hipSetDevice(b->device));
     return clear_sums(b, 0, b->members);

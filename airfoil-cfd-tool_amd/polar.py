@@ -24,7 +24,8 @@ With the two-relaxation-time collision (``PolarEngine.enable_trt``, ``run_polar(
 half-way wall is set by a magic number and not by tau, so a body keeps its thickness when the Reynolds number of a sweep changes.
 With a prescribed far-field profile (``PolarEngine.enable_far_profile`` / ``set_far_profile``) every far-field cell holds the
 equilibrium of its own (rho, ux, uy); ``run_polar(far_field="vortex")`` uses it for the textbook far-field correction of airfoil
-computations, the free stream plus a point vortex that follows the lift (:func:`far_profile`, :func:`vortex_update`).
+computations, the free stream plus a point vortex that follows the lift (:func:`far_profile`, :func:`vortex_update`);
+``run_polar(vortex_on="device")`` leaves those updates to the device (``PolarEngine.enable_far_vortex``), in stream order and without a wait.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -60,7 +61,8 @@ EXPORTS = (
     "wtp_create_stored", "wtp_read_stored",
     "wtp_write_f", "wtp_write_stored", "wtp_step_count", "wtp_set_step_count",
     "wtp_enable_trt",
-    "wtp_enable_far_profile", "wtp_set_far_profile",
+    "wtp_enable_far_profile", "wtp_set_far_profile", "wtp_read_far_profile",
+    "wtp_enable_far_vortex", "wtp_set_far_vortex", "wtp_far_vortex", "wtp_far_vortex_update", "wtp_far_vortex_log",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
@@ -70,6 +72,8 @@ COLLISIONS = ("bgk", "trt")                                        # run_polar's
 MAGIC_DEFAULT = 3 / 16                                             # the magic number at which a half-way wall of a Poiseuille flow sits half-way at every tau
 FAR_FIELDS = ("uniform", "vortex", "vortex+source")                 # run_polar's far fields: the free stream alone, plus a point vortex from the lift, plus a source from the drag
 VORTEX_SPEED_MAX = 0.1                                             # the largest speed the vortex and the source together may induce at the nearest far-field cell centre
+VORTEX_ON = ("host", "device")                                     # who updates the vortex of run_polar: the host between chunks of steps, or the device in stream order
+VORTEX_NORMS = ("hypot", "sqrt")                                   # vortex_update's norm of (strength, source): np.hypot, or sqrt(s*s + q*q) as the device forms it
 FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
 WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
@@ -130,6 +134,12 @@ def load_polar_library(path: str = POLAR_LIB_PATH, optional: Sequence[str] = ())
         "wtp_enable_trt": ([B, dp], c_int),
         "wtp_enable_far_profile": ([B, c_int], c_int),
         "wtp_set_far_profile": ([B, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+        "wtp_read_far_profile": ([B, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+        "wtp_enable_far_vortex": ([B, c_int, c_int64, c_double, c_double, c_int, c_double, c_double, dp, dp, dp, dp, c_int], c_int),
+        "wtp_set_far_vortex": ([B, dp, dp], c_int),
+        "wtp_far_vortex": ([B, dp, dp], c_int),
+        "wtp_far_vortex_update": ([B], c_int),
+        "wtp_far_vortex_log": ([B, c_int, c_int, ip, dp, dp, dp, dp, POINTER(c_int32)], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         if name in optional and path != POLAR_LIB_PATH and not hasattr(lib, name):
@@ -209,7 +219,8 @@ class PolarEngine:
         self._wind = False
         self._trt = False
         self._far_profile = False
-        self._far_tables = None      # the tables last given to every member, (left [B][3][NY], bottom [B][3][NX], top [B][3][NX]), and which members have some
+        self._far_vortex = False
+        self._far_given = np.zeros(self.members, bool)      # which members have tables (set_far_profile, enable_far_vortex)
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         if storage == "half":
             _check(self._lib.wtp_create_stored(self.nx, self.ny, code, WTP_STORE_HALF, self.members, self.history_cap, int(device),
@@ -413,10 +424,8 @@ class PolarEngine:
         enable_interpolated_walls, enable_trt and enable_wind, independent of the read-outs."""
         _check(self._lib.wtp_enable_far_profile(self._b, 1 if on else 0))
         self._far_profile = bool(on)
-        if self._far_tables is None:
-            B = self.members
-            self._far_tables = (np.zeros((B, 3, self.ny), self.dtype), np.zeros((B, 3, self.nx), self.dtype),
-                                np.zeros((B, 3, self.nx), self.dtype), np.zeros(B, bool))
+        if not on:
+            self._far_vortex = False             # (the library switches the device-side vortex off with the profile)
 
     @property
     def far_profile_enabled(self) -> bool:
@@ -438,9 +447,71 @@ class PolarEngine:
             tabs.append(a)
         count = int(tabs[0].shape[0])
         _check(self._lib.wtp_set_far_profile(self._b, int(first), count, *(t.ctypes.data_as(c_void_p) for t in tabs)))
-        for held, t in zip(self._far_tables, tabs):
-            held[first:first + count] = t
-        self._far_tables[3][first:first + count] = True
+        self._far_given[first:first + count] = True
+
+    def read_far_profile(self, first: int = 0, count: Optional[int] = None):
+        """The read twin of set_far_profile: (left [count][3][NY], bottom [count][3][NX], top [count][3][NX]) of members first ..
+        first+count-1 (default: to the last) as the device holds them, whether set_far_profile uploaded them or the device-side
+        vortex wrote them.  WTError (WT_ERR_STATE) while the model was never enabled or a member has no profile."""
+        count = self.members - int(first) if count is None else int(count)
+        n = max(count, 0)
+        tabs = (np.empty((n, 3, self.ny), self.dtype), np.empty((n, 3, self.nx), self.dtype), np.empty((n, 3, self.nx), self.dtype))
+        _check(self._lib.wtp_read_far_profile(self._b, int(first), count, *(t.ctypes.data_as(c_void_p) for t in tabs)))
+        return tabs
+
+    def enable_far_vortex(self, every: int, after: int, relax: float, u_ref: float, with_source: bool, xc: float, yc: float, u_far, v_far,
+                          alpha=0.0, log_cap: int = 0) -> None:
+        """Keep the tables of the far-field profile up to date on the device (wt_polar.h "Device-side far-field vortex"): the free
+        stream (u_far, v_far) plus a point vortex and, with `with_source`, a source at (xc, yc) whose strengths follow the pressure
+        force, in stream order between two steps, with nothing synchronised.  The step that brings the count of steps since this call
+        to a multiple of `every`, at an absolute step count of at least `after`, is followed by one update: forces() on the device,
+        vortex_update(..., norm="sqrt") with `relax`, `u_ref` and the member's `alpha` (degrees; its cosine and sine are formed here as
+        wind_axes forms them), far_profile of the new strengths into the tables, and one row of the log (far_vortex_log), which holds
+        `log_cap` updates; a step whose updates would overflow it raises WTError (WT_ERR_STATE).  u_far, v_far, alpha: one value or
+        [B].  After enable_far_profile; every member then has a profile, built from the current strengths (zero at the first call, kept
+        afterwards).  every=0 switches the update off and keeps tables and strengths (the other arguments are not read).  While it is
+        on, set_far_profile raises WTError (WT_ERR_STATE).  The same run updated by the host (forces, vortex_update, far_profile,
+        set_far_profile) has the same bits unless an update clips."""
+        B = self.members
+        a = np.radians(_f64(alpha, B))
+        u, v, c, s = _f64(u_far, B), _f64(v_far, B), np.ascontiguousarray(np.cos(a)), np.ascontiguousarray(np.sin(a))
+        _check(self._lib.wtp_enable_far_vortex(self._b, int(every), int(after), float(relax), float(u_ref), 1 if with_source else 0, float(xc),
+                                               float(yc), _dp(u), _dp(v), _dp(c), _dp(s), int(log_cap)))
+        self._far_vortex = int(every) != 0
+        if self._far_vortex:
+            self._far_given[:] = True
+
+    @property
+    def far_vortex_enabled(self) -> bool:
+        return self._far_vortex
+
+    def set_far_vortex(self, strength, source) -> None:
+        """Replace the strengths and the sources (one value or [B]) of the device-side vortex and rebuild every table on the device: the
+        restart path.  WTError (WT_ERR_ARG) for a pair that induces more than VORTEX_SPEED_MAX at the bound or is not finite."""
+        s, q = _f64(strength, self.members), _f64(source, self.members)
+        _check(self._lib.wtp_set_far_vortex(self._b, _dp(s), _dp(q)))
+
+    def far_vortex(self):
+        """(strength, source), [B] float64 each: the current values of the device-side vortex."""
+        s, q = np.empty(self.members), np.empty(self.members)
+        _check(self._lib.wtp_far_vortex(self._b, _dp(s), _dp(q)))
+        return s, q
+
+    def far_vortex_update(self) -> None:
+        """One update of the device-side vortex now, from the last emitted state, logged with the current step count."""
+        _check(self._lib.wtp_far_vortex_update(self._b))
+
+    def far_vortex_log(self) -> Dict[str, np.ndarray]:
+        """Every update held: step [U] int64, fx, fy (the forces the update read, lattice axes), strength, source [U][B] float64 (the
+        values after the update) and clipped [U][B] bool.  init_equilibrium and clear_history empty it."""
+        rows = _check(self._lib.wtp_far_vortex_log(self._b, 0, 0, None, None, None, None, None, None))
+        B = self.members
+        out = {"step": np.empty(rows, np.int64), **{k: np.empty((rows, B)) for k in ("fx", "fy", "strength", "source")}}
+        clipped = np.empty((rows, B), np.int32)
+        _check(self._lib.wtp_far_vortex_log(self._b, 0, rows, _ip(out["step"]), *(_dp(out[k]) for k in ("fx", "fy", "strength", "source")),
+                                            clipped.ctypes.data_as(POINTER(c_int32))))
+        out["clipped"] = clipped != 0
+        return out
 
     def clamp_events(self):
         """(density events, speed events), [B] each."""
@@ -499,13 +570,14 @@ class PolarEngine:
     def state(self) -> Dict[str, object]:
         """What a restart needs: nx, ny, dtype (its name), storage, members, steps (the step count) and f [B][9][NY][NX], the
         populations of every member: read_f's values on a native batch, read_stored's raw uint16 halves on a storage="half" batch.
-        With a far-field profile on and given to every member, also far_profile: {"left", "bottom", "top"}, the tables in use.
+        With a far-field profile on and given to every member, also far_profile: {"left", "bottom", "top"}, the tables in use, read
+        back from the device (read_far_profile), which holds what set_far_profile gave it or what the device-side vortex wrote.
         Not in it: the history, the running sums (surface, mean fields), the masks, the wall distances and the enable_* settings."""
         read = self.read_stored if self.storage == "half" else self.read_f
         state = {"nx": self.nx, "ny": self.ny, "dtype": self.dtype.name, "storage": self.storage, "members": self.members,
                  "steps": self.step_count, "f": np.stack([read(m) for m in range(self.members)])}
-        if self._far_profile and self._far_tables[3].all():
-            state["far_profile"] = {k: t.copy() for k, t in zip(("left", "bottom", "top"), self._far_tables)}
+        if self._far_profile and self._far_given.all():
+            state["far_profile"] = dict(zip(("left", "bottom", "top"), self.read_far_profile()))
         return state
 
     def restore(self, state) -> None:
@@ -514,7 +586,7 @@ class PolarEngine:
         that is not written defined contents, and it clears the history, so that the restored count cannot fall below a row held.
         Masks, wall distances and enable_* settings are the caller's to set as they were; the running sums start empty and the
         macroscopic planes are valid again after the first step.  A state that carries far_profile tables switches the far-field
-        profile on and puts them back."""
+        profile on and puts them back (before enable_far_vortex: while the device owns the tables, set_far_profile is refused)."""
         _check_state(state, self.nx, self.ny, self.dtype, self.storage, self.members)
         write = self.write_stored if self.storage == "half" else self.write_f
         for m in range(self.members):
@@ -764,20 +836,25 @@ def vortex_bound(nx: int, ny: int, xc: float, yc: float) -> float:
     return min(xc - 0.5, yc - 0.5, ny - 0.5 - yc)
 
 
-def vortex_update(strength, source, fx, fy, alpha, u0: float, relax: float, bound: float, with_source: bool = True):
+def vortex_update(strength, source, fx, fy, alpha, u0: float, relax: float, bound: float, with_source: bool = True, norm: str = "hypot"):
     """The update rule of the far-field vortex and source, elementwise over the members; pure.  D, L = wind_axes(fx, fy, alpha), the
     drag and the lift in lattice units.  The targets are L/(2 pi u0) for the strength (Kutta-Joukowski with rho = 1) and D/(2 pi u0)
     for the source (0 when with_source is false); new = old + relax*(target - old).  Then both are scaled by one factor, where
     needed, so that the speed they induce together at the nearest far-field cell centre, hypot(strength, source)/bound, stays at
     most VORTEX_SPEED_MAX = 0.1: this keeps every profile inside set_far_profile's limits for u0 <= 0.25.
+    `norm`: "hypot", the default, forms that speed with np.hypot; "sqrt" with sqrt(s*s + q*q), one rounding per operation, which is the
+    rule of the device-side update (wt_polar.h "Device-side far-field vortex") as a NumPy function.  The two give the same bits whenever
+    both find the update unclipped, because the scale is then exactly 1.
     Returns (strength, source, clipped): float64, float64, bool."""
+    if norm not in VORTEX_NORMS:
+        raise ValueError(f"norm must be one of {VORTEX_NORMS}, got {norm!r}")
     old_s, old_q = np.asarray(strength, np.float64), np.asarray(source, np.float64)
     drag, lift = wind_axes(fx, fy, alpha)
     tgt_s = lift / (2 * math.pi * u0)
     tgt_q = drag / (2 * math.pi * u0) if with_source else np.zeros_like(tgt_s)
     new_s = old_s + relax * (tgt_s - old_s)
     new_q = old_q + relax * (tgt_q - old_q)
-    speed = np.hypot(new_s, new_q) / bound
+    speed = (np.hypot(new_s, new_q) if norm == "hypot" else np.sqrt(new_s * new_s + new_q * new_q)) / bound
     clipped = speed > VORTEX_SPEED_MAX
     scale = np.where(clipped, VORTEX_SPEED_MAX / np.where(clipped, speed, 1.0), 1.0)
     return new_s * scale, new_q * scale, clipped
@@ -790,7 +867,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               total_forces: bool = False, mean_fields: bool = False, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
               collision: str = "bgk", magic: float = MAGIC_DEFAULT,
               far_field: str = "uniform", vortex_every: int = 96, vortex_relax: float = 0.3, vortex_after: Optional[int] = None,
-              storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
+              vortex_on: str = "host", storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -858,7 +935,17 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     correction removes a part of the tunnel effect, not all of it, and a taller lattice (`ny`) removes more, at its cost in work
     (README, profiles/polar_profile_sweep.txt).  PolarResult.far_field says what ran, PolarResult.vortex_history holds every update
     and PolarPoint.vortex_strength / .vortex_source the last values.  storage="half" with a far field other than "uniform", an
-    unknown far_field, vortex_every < 1 or a vortex_relax outside (0, 1] raises ValueError before an engine is created."""
+    unknown far_field, vortex_every < 1 or a vortex_relax outside (0, 1] raises ValueError before an engine is created.
+    `vortex_on`: who updates the vortex.  "host", the default, is the loop above, with the code path and the bits it always had: every
+    update reads the forces back, which waits for the stream, forms the tables in NumPy and uploads them, which waits again.
+    "device" hands the updates to the library (PolarEngine.enable_far_vortex, wt_polar.h "Device-side far-field vortex"): the force
+    read-out, the relaxation, the clip and the tables are enqueued between two steps, so that the warm-up and the sampling are two
+    `step` calls as with the uniform far field, and a small `vortex_every` costs a few small launches per update and no wait.  The
+    updates fall on the same steps, a last one after a short last chunk included, and PolarResult.vortex_history, the points'
+    strengths and `state` are built from the device's log.  Device and host mode are the same run, bit for bit, unless an update clips
+    (vortex_history["clipped"]): the device forms the norm of (strength, source) as sqrt(s*s + q*q) where the host uses np.hypot
+    (vortex_update's `norm`), so a clipped update may differ in the last bit of its scale.  It is not read with the uniform far field.
+    An unknown vortex_on raises ValueError before an engine is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -884,6 +971,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             raise ValueError(f"magic must be a finite magic number in (0, 1], got {magic!r}")
     if not isinstance(far_field, str) or far_field not in FAR_FIELDS:
         raise ValueError(f"far_field must be one of {FAR_FIELDS}, got {far_field!r}")
+    if not isinstance(vortex_on, str) or vortex_on not in VORTEX_ON:
+        raise ValueError(f"vortex_on must be one of {VORTEX_ON}, got {vortex_on!r}")
     vortex = far_field != "uniform"
     if vortex:
         if storage == "half":
@@ -951,34 +1040,53 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             held = start.get("vortex") if start is not None else None
             strength = np.array(held["strength"], np.float64) if held else np.zeros(B)
             source = np.array(held["source"], np.float64) if held else np.zeros(B)
-            vh = {k: [] for k in ("step", "fx", "fy", "strength", "source", "clipped")}
-
-            def upload():
-                tabs = [far_profile(nx, ny, u_far[m], v_far[m], strength[m], source[m], xc, yc, eng.dtype) for m in range(B)]
-                eng.set_far_profile(*(np.stack([t[k] for t in tabs]) for k in range(3)))
-
+            total = warmup_steps + samples * sample_every
             eng.enable_far_profile()
-            upload()
-            total, done = warmup_steps + samples * sample_every, 0
-            while done < total:
-                n = min(int(vortex_every), total - done)
-                quiet = min(n, max(warmup_steps - done, 0))    # the chunk's steps that still belong to the warm-up take no sample
-                if quiet:
-                    eng.step(quiet, tau, ux0)
-                if n > quiet:
-                    eng.step(n - quiet, tau, ux0, sample_every=sample_every)
-                done += n
-                count = eng.step_count
-                if count >= after:
-                    fx, fy, _, _ = eng.forces()
-                    strength, source, clipped = vortex_update(strength, source, fx, fy, alpha_far, u0, vortex_relax, bound,
-                                                              with_source=far_field == "vortex+source")
-                    upload()
-                    for k, v in zip(vh, (count, fx, fy, strength, source, clipped)):
-                        vh[k].append(v)
-            U = len(vh["step"])
-            vortex_history = {"step": np.asarray(vh["step"], np.int64), **{k: np.asarray(vh[k], np.float64).reshape(U, B) for k in ("fx", "fy", "strength", "source")},
-                              "clipped": np.asarray(vh["clipped"], bool).reshape(U, B)}
+            if vortex_on == "device":
+                # the host loop below, enqueued: an update behind every vortex_every-th step of this call whose count lies at or beyond
+                # `after`, and one behind a short last chunk; the log holds exactly those
+                every, first = int(vortex_every), eng.step_count
+                updates = sum(1 for k in range(1, total // every + 1) if first + k * every >= after)
+                last = total % every != 0 and first + total >= after
+                eng.enable_far_vortex(every, after, vortex_relax, u0, far_field == "vortex+source", xc, yc, u_far, v_far, alpha_far,
+                                      log_cap=updates + int(last))
+                if held:
+                    eng.set_far_vortex(strength, source)
+                if warmup_steps:
+                    eng.step(warmup_steps, tau, ux0)
+                eng.step(samples * sample_every, tau, ux0, sample_every=sample_every)
+                if last:
+                    eng.far_vortex_update()
+                vortex_history = eng.far_vortex_log()
+                strength, source = eng.far_vortex()
+            else:
+                vh = {k: [] for k in ("step", "fx", "fy", "strength", "source", "clipped")}
+
+                def upload():
+                    tabs = [far_profile(nx, ny, u_far[m], v_far[m], strength[m], source[m], xc, yc, eng.dtype) for m in range(B)]
+                    eng.set_far_profile(*(np.stack([t[k] for t in tabs]) for k in range(3)))
+
+                upload()
+                done = 0
+                while done < total:
+                    n = min(int(vortex_every), total - done)
+                    quiet = min(n, max(warmup_steps - done, 0))    # the chunk's steps that still belong to the warm-up take no sample
+                    if quiet:
+                        eng.step(quiet, tau, ux0)
+                    if n > quiet:
+                        eng.step(n - quiet, tau, ux0, sample_every=sample_every)
+                    done += n
+                    count = eng.step_count
+                    if count >= after:
+                        fx, fy, _, _ = eng.forces()
+                        strength, source, clipped = vortex_update(strength, source, fx, fy, alpha_far, u0, vortex_relax, bound,
+                                                                  with_source=far_field == "vortex+source")
+                        upload()
+                        for k, v in zip(vh, (count, fx, fy, strength, source, clipped)):
+                            vh[k].append(v)
+                U = len(vh["step"])
+                vortex_history = {"step": np.asarray(vh["step"], np.int64), **{k: np.asarray(vh[k], np.float64).reshape(U, B) for k in ("fx", "fy", "strength", "source")},
+                                  "clipped": np.asarray(vh["clipped"], bool).reshape(U, B)}
         h = eng.history()
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), 0.0 if wind else a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)

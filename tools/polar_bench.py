@@ -298,7 +298,10 @@ def main():
     if a.repeats is None:
         a.repeats = 1 if plain else 7
     if a.lib:
-        unused = (("wtp_enable_trt", a.trt is None), ("wtp_enable_far_profile", not a.profile), ("wtp_set_far_profile", not a.profile))
+        unused = (("wtp_enable_trt", a.trt is None), ("wtp_enable_far_profile", not a.profile), ("wtp_set_far_profile", not a.profile),
+                  # the device-side far-field vortex and the tables' read-back: nothing here calls them
+                  ("wtp_read_far_profile", True), ("wtp_enable_far_vortex", True), ("wtp_set_far_vortex", True), ("wtp_far_vortex", True),
+                  ("wtp_far_vortex_update", True), ("wtp_far_vortex_log", True))
         pkg.polar.load_polar_library(a.lib, optional=tuple(name for name, free in unused if free))
     if a.storage == "half" and a.ibb:
         ap.error("--storage half does not combine with --ibb")
