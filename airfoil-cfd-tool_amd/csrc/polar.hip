@@ -21,6 +21,10 @@
 // Mean fields (wtp_enable_mean) are no reduction: k_mean_batch, launched behind the three, streams every member's emitted rho,
 // ux, uy once and adds them and their products to seven planes of running sums, one owner thread per entry.
 //
+// Probe points (wtp_enable_probes) are no reduction either: k_probe_batch, launched behind the four, samples every member's emitted rho,
+// ux, uy at the member's own points, bilinearly between cell centres, and adds the three values of each point to its running sums, one
+// owner lane per point.  A batch that never enables them launches the kernels it always launched.
+//
 // The step has one tiled kernel, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR>: step_tile (step_fast.hpp) of the wave's tile with
 // the collision, the wall rule and the far field as template arguments, and the values each of them reads per member in one argument
 // whose members exist only in the variants that read them (StepModel).  The models below select among its instantiations.
@@ -233,6 +237,14 @@ struct wtp_batch {
     long long *m_cnt = nullptr;          // [B]: samples added
     long m_stride = 0;
     int m_pitch = 0;                     // NY rounded up to WTP_MEAN_ROWS
+    // probe points (wtp_enable_probes); every pointer is null until then
+    bool probes = false;
+    int pb_n = 0;                        // P, the points of every member
+    long long *pb_off = nullptr;         // [B][P]: the offset of cell (i0, j0) in a macroscopic plane, i0 * pitch + j0; -1: the point is inactive
+    double *pb_w = nullptr;              // [B][4][P]: w00, w10, w01, w11
+    double *pb_sums = nullptr;           // [B][3][P]: sums of rho, ux, uy over the samples
+    long long *pb_cnt = nullptr;         // [B]: samples added
+    double *pb_row = nullptr;            // [3][P]: the scratch row of wtp_probe_sample
     bool inited = false;
     bool macro_stale = false;            // a member's populations were written (wtp_write_f / wtp_write_stored) and no step has emitted since
     long long steps_done = 0;
@@ -808,6 +820,50 @@ __global__ __launch_bounds__(256) void k_mean_batch(const T *__restrict__ macro,
     for (int k = 0; k < kMeanPlanes; k++) *reinterpret_cast<RowRun<double, R> *>(acc + k * ap) = s[k];
 }
 
+// Probe points of every member in one launch: grid (ceil(P / 256), members), blockIdx.y the member, one lane per point.  Definition
+// (include/wt_polar.h "Probe points"): member m holds P points; point p has a base cell (i0, j0), held as its offset off = i0 * pitch + j0
+// in a macroscopic plane ([NX][pitch], y fastest; -1 flags an inactive point), and four weights w00, w10, w01, w11 for the cells (i0, j0),
+// (i0+1, j0), (i0, j0+1), (i0+1, j0+1), all formed and checked on the host (probe_tables), so that every offset read here lies inside the
+// member's planes: i0 <= NX - 2 and j0 <= NY - 2.  For each of the three planes a in (rho, ux, uy), with the four values converted exactly
+// to double:
+//     v = ((w00*a00 + w10*a10) + w01*a01) + w11*a11
+// with no contraction (the file is built with -ffp-contract=off): seven roundings.  No cell is special-cased.
+// The tables are structure of arrays per member (off [P], w [4][P]), so that consecutive lanes read consecutive entries; the twelve gathers
+// of a lane fall into two neighbouring columns of each plane.  ACCUMULATE: the three values are added to the point's sums, out[a][p] += v,
+// and lane 0 of block 0 adds one to the member's count, as k_mean_batch does; every entry has one owner and launches are stream-ordered, so
+// these are plain read-modify-writes in sample order, with no atomics and no tickets, and an inactive point does nothing.  Without
+// ACCUMULATE the three values go to out[a][p] (the scratch row of wtp_probe_sample), NaN at an inactive point, and count is not touched.
+// macro, off, w, out and count are those of member blockIdx.y = 0: the on-demand call hands in one member's with a grid of one row.
+template <typename T, bool ACCUMULATE>
+__global__ __launch_bounds__(256) void k_probe_batch(const T *__restrict__ macro, Geom g, MemberStrides ms, int npoints,
+                                                     const long long *__restrict__ off, const double *__restrict__ w,
+                                                     double *__restrict__ out, long long *__restrict__ count)
+{
+    const long m = blockIdx.y;
+    const long P = npoints;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (ACCUMULATE && p == 0) count[m] += 1;
+    if (p >= P) return;
+    double *dst = out + m * 3 * P + p;
+    const long long o = off[m * P + p];
+    if (o < 0) {
+        if (!ACCUMULATE) { dst[0] = __builtin_nan(""); dst[P] = __builtin_nan(""); dst[2 * P] = __builtin_nan(""); }
+        return;
+    }
+    const double *wm = w + m * 4 * P + p;
+    const double w00 = wm[0], w10 = wm[P], w01 = wm[2 * P], w11 = wm[3 * P];
+    const long mp = (long)g.nxl * g.pitch;                          // elements of one field plane
+    const T *src = macro + m * ms.macro + o;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const T *s = src + a * mp;
+        const double a00 = (double)s[0], a10 = (double)s[g.pitch], a01 = (double)s[1], a11 = (double)s[g.pitch + 1];
+        const double v = ((w00 * a00 + w10 * a10) + w01 * a01) + w11 * a11;
+        if (ACCUMULATE) dst[a * P] += v;
+        else dst[a * P] = v;
+    }
+}
+
 // The device-side far-field vortex (include/wt_polar.h "Device-side far-field vortex") of every member in one launch, behind
 // k_forces_batch: grid (ceil((NY + 2 NX) / kVortexBlock), B), blockIdx.y the member, one lane per table entry, the entries in the order
 // left[0 .. NY), bottom[0 .. NX), top[0 .. NX), so that consecutive lanes write consecutive entries of a table plane.  Definition, all in
@@ -906,7 +962,8 @@ extern "C" int wtp_destroy(wtp_batch *b)
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
     void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->v_member, b->v_str, b->v_forces, b->v_log, b->v_clip, b->partials, b->tickets, b->stage,
-                    b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt};
+                    b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt,
+                    b->pb_off, b->pb_w, b->pb_sums, b->pb_cnt, b->pb_row};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (SampleTable *t : {&b->forces, &b->moment, &b->xforces}) t->release();
     if (b->st) (void)hipStreamDestroy(b->st);
@@ -994,7 +1051,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile, device-side far-field vortex)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile, device-side far-field vortex, probe points)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1072,11 +1129,21 @@ static int reset_wall_q(wtp_batch *b, int first, int count)
     return WT_OK;
 }
 
-// What restarts the time statistics of members [first, first+count): the surface sums and the mean fields, each if enabled.
+// Zero the probe sums and the sample counts of members [first, first+count), in stream order.  The points are kept.
+static int zero_probe_sums(wtp_batch *b, int first, int count)
+{
+    const size_t P = (size_t)b->pb_n;
+    HIP_TRY(hipMemsetAsync(b->pb_sums + (size_t)first * 3 * P, 0, (size_t)count * 3 * P * sizeof(double), b->st));
+    HIP_TRY(hipMemsetAsync(b->pb_cnt + first, 0, (size_t)count * sizeof(long long), b->st));
+    return WT_OK;
+}
+
+// What restarts the time statistics of members [first, first+count): the surface sums, the mean fields and the probe sums, each if enabled.
 static int clear_sums(wtp_batch *b, int first, int count)
 {
     WT_TRY(clear_surface_sums(b, first, count));
-    return b->mean ? zero_mean_sums(b, first, count) : WT_OK;
+    if (b->mean) WT_TRY(zero_mean_sums(b, first, count));
+    return b->probes ? zero_probe_sums(b, first, count) : WT_OK;
 }
 
 extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *masks)
@@ -1316,6 +1383,16 @@ static int launch_mean(wtp_batch *b)
     return WT_OK;
 }
 
+// The emitted fields of every member sampled at its probe points and added to the points' sums, and one sample to its count.
+template <typename T>
+static int launch_probes(wtp_batch *b)
+{
+    hipLaunchKernelGGL((k_probe_batch<T, true>), dim3((unsigned)((b->pb_n + 255) / 256), (unsigned)b->members), dim3(256), 0, b->st,
+                       (const T *)b->macro, b->g, b->ms, b->pb_n, (const long long *)b->pb_off, (const double *)b->pb_w, b->pb_sums, b->pb_cnt);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 // One sample of the state the last step left: every read-out that is enabled, into row `row` of its table.
 template <typename T>
 static int sample_into(wtp_batch *b, int row)
@@ -1324,6 +1401,7 @@ static int sample_into(wtp_batch *b, int row)
     if (b->loads) WT_TRY(launch_loads<T>(b, row, true));
     if (b->mex) WT_TRY(launch_mex<T>(b, row));
     if (b->mean) WT_TRY(launch_mean<T>(b));
+    if (b->probes) WT_TRY(launch_probes<T>(b));
     return WT_OK;
 }
 
@@ -1901,7 +1979,7 @@ extern "C" int wtp_clear_history(wtp_batch *b)
     WT_TRY(check_batch(b));
     b->h_step.clear();                           // (rows are only written by later, stream-ordered reductions)
     b->v_step.clear();                           // (so are the rows of the far-field vortex's log)
-    if (!b->loads && !b->mean) return WT_OK;
+    if (!b->loads && !b->mean && !b->probes) return WT_OK;
     HIP_TRY(hipSetDevice(b->device));
     return clear_sums(b, 0, b->members);
 }
@@ -2314,5 +2392,145 @@ extern "C" int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, 
         HIP_TRY(hipStreamSynchronize(b->st));
         HIP_TRY(hipMemcpy(n, b->m_cnt + member, sizeof(int64_t), hipMemcpyDeviceToHost));
     }
+    return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// probe points (include/wt_polar.h "Probe points")
+// ------------------------------------------------------------------------------------------
+static void free_probes(wtp_batch *b)
+{
+    for (void *p : {(void *)b->pb_off, (void *)b->pb_w, (void *)b->pb_sums, (void *)b->pb_cnt, (void *)b->pb_row}) if (p) (void)hipFree(p);
+    b->pb_off = nullptr; b->pb_w = nullptr; b->pb_sums = nullptr; b->pb_cnt = nullptr; b->pb_row = nullptr;
+    b->pb_n = 0;
+    b->probes = false;
+}
+
+extern "C" int wtp_enable_probes(wtp_batch *b, int npoints)
+{
+    WT_TRY(check_batch(b));
+    if (npoints < 0 || npoints > WTP_MAX_PROBES) return fail(WT_ERR_ARG, "npoints must be in [0, %d] (got %d)", WTP_MAX_PROBES, npoints);
+    HIP_TRY(hipSetDevice(b->device));
+    if (npoints == 0) {
+        HIP_TRY(hipStreamSynchronize(b->st));    // samples already enqueued still add to the sums
+        free_probes(b);
+        return WT_OK;
+    }
+    const size_t B = (size_t)b->members, P = (size_t)npoints;
+    if (npoints != b->pb_n) {                    // another count: new buffers first, so that a failure leaves the batch as it was
+        void *off = nullptr, *w = nullptr, *sums = nullptr, *cnt = nullptr, *row = nullptr;
+        hipError_t e = hipMalloc(&off, B * P * sizeof(long long));
+        if (e == hipSuccess) e = hipMalloc(&w, B * 4 * P * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&sums, B * 3 * P * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&cnt, B * sizeof(long long));
+        if (e == hipSuccess) e = hipMalloc(&row, 3 * P * sizeof(double));
+        if (e == hipSuccess) e = hipStreamSynchronize(b->st);      // samples already enqueued read and write the previous buffers
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // (the batch goes on as it was: later launches must not see this error)
+            for (void *p : {off, w, sums, cnt, row}) if (p) (void)hipFree(p);
+            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the probe tables and sums (%zu bytes) could not be allocated: %s",
+                        B * P * 64 + B * 8 + P * 24, hipGetErrorString(e));
+        }
+        free_probes(b);
+        b->pb_off = (long long *)off; b->pb_w = (double *)w; b->pb_sums = (double *)sums; b->pb_cnt = (long long *)cnt; b->pb_row = (double *)row;
+        b->pb_n = npoints;
+    }
+    HIP_TRY(hipMemsetAsync(b->pb_off, 0xFF, B * P * sizeof(long long), b->st));      // -1: every point inactive (behind the samples already enqueued)
+    HIP_TRY(hipMemsetAsync(b->pb_w, 0, B * 4 * P * sizeof(double), b->st));
+    b->probes = true;
+    return zero_probe_sums(b, 0, b->members);
+}
+
+// The tables of `n` points: off[n] and w[4][n] (k_probe_batch) from x[n], y[n] by the weight rule of include/wt_polar.h, in double, one
+// rounding per operation.  False where a point is neither valid nor inactive; *bad is then its index.
+static bool probe_tables(const wtp_batch *b, const double *x, const double *y, size_t n, long long *off, double *w, size_t *bad)
+{
+    const double xmax = (double)b->nx - 0.5, ymax = (double)b->ny - 0.5;
+    for (size_t p = 0; p < n; p++) {
+        if (std::isnan(x[p])) {                  // inactive: y is not read
+            off[p] = -1;
+            w[p] = 0.0; w[n + p] = 0.0; w[2 * n + p] = 0.0; w[3 * n + p] = 0.0;
+            continue;
+        }
+        if (!(x[p] >= 0.5 && x[p] <= xmax && y[p] >= 0.5 && y[p] <= ymax)) { *bad = p; return false; }       // (false for a NaN y)
+        const double gx = x[p] - 0.5, gy = y[p] - 0.5;
+        const int i0 = std::min(std::max((int)std::floor(gx), 0), b->nx - 2), j0 = std::min(std::max((int)std::floor(gy), 0), b->ny - 2);
+        const double tx = gx - (double)i0, sx = 1.0 - tx, ty = gy - (double)j0, sy = 1.0 - ty;
+        off[p] = (long long)i0 * b->g.pitch + j0;
+        w[p] = sx * sy; w[n + p] = tx * sy; w[2 * n + p] = sx * ty; w[3 * n + p] = tx * ty;
+    }
+    return true;
+}
+
+static int check_probes(const wtp_batch *b)
+{
+    if (!b->probes) return fail(WT_ERR_STATE, "the probe points are not enabled (wtp_enable_probes)");
+    return WT_OK;
+}
+
+extern "C" int wtp_set_probes(wtp_batch *b, int first, int count, const double *x, const double *y)
+{
+    WT_TRY(check_batch(b));
+    if (!x || !y) return fail(WT_ERR_ARG, "x or y is null");
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_probes(b));
+    const size_t P = (size_t)b->pb_n;
+    std::vector<long long> off((size_t)count * P);
+    std::vector<double> w((size_t)count * 4 * P);
+    for (size_t k = 0; k < (size_t)count; k++) {
+        size_t bad = 0;
+        if (!probe_tables(b, x + k * P, y + k * P, P, off.data() + k * P, w.data() + k * 4 * P, &bad))
+            return fail(WT_ERR_ARG, "point %zu of member %d, (%g, %g), lies outside [0.5, %g] x [0.5, %g] and is not inactive (x = NaN)", bad,
+                        first + (int)k, x[k * P + bad], y[k * P + bad], (double)b->nx - 0.5, (double)b->ny - 0.5);
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));        // samples already enqueued read the previous points
+    HIP_TRY(hipMemcpy(b->pb_off + (size_t)first * P, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->pb_w + (size_t)first * 4 * P, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    return zero_probe_sums(b, first, count);
+}
+
+extern "C" int wtp_probe_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy)
+{
+    WT_TRY(check_batch(b));
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_probes(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t P = (size_t)b->pb_n;
+    double *const dst[3] = {rho, ux, uy};
+    for (int a = 0; a < 3; a++)
+        if (dst[a]) HIP_TRY(hipMemcpy(dst[a], b->pb_sums + ((size_t)member * 3 + a) * P, P * sizeof(double), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(n, b->pb_cnt + member, sizeof(int64_t), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+// One member's points sampled on the last emitted state into the scratch row: a grid of one row with the member's planes and tables.
+template <typename T>
+static int launch_probe_sample(wtp_batch *b, int member)
+{
+    const size_t P = (size_t)b->pb_n;
+    hipLaunchKernelGGL((k_probe_batch<T, false>), dim3((unsigned)((b->pb_n + 255) / 256), 1u), dim3(256), 0, b->st,
+                       (const T *)macro_of<T>(b, member), b->g, b->ms, b->pb_n, (const long long *)(b->pb_off + (size_t)member * P),
+                       (const double *)(b->pb_w + (size_t)member * 4 * P), b->pb_row, (long long *)nullptr);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+extern "C" int wtp_probe_sample(wtp_batch *b, int member, double *rho, double *ux, double *uy)
+{
+    WT_TRY(check_batch(b));
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_probes(b));
+    WT_TRY(check_ready(b));
+    WT_TRY(check_macro(b));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(b->dtype == WT_F32 ? launch_probe_sample<float>(b, member) : launch_probe_sample<double>(b, member));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const size_t P = (size_t)b->pb_n;
+    double *const dst[3] = {rho, ux, uy};
+    for (int a = 0; a < 3; a++)
+        if (dst[a]) HIP_TRY(hipMemcpy(dst[a], b->pb_row + (size_t)a * P, P * sizeof(double), hipMemcpyDeviceToHost));
     return WT_OK;
 }

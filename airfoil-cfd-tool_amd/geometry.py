@@ -224,3 +224,45 @@ def wall_distances(xp: np.ndarray, yp: np.ndarray, mask: np.ndarray, nx: int, ny
         first = np.where(hit, t, np.inf).min(axis=1)
         q[k, jj, ii] = np.where(np.isfinite(first), first, 0.5)
     return q
+
+
+def to_lattice(x, y, nx: int, ny: int, y_half: Optional[float] = None):
+    """World coordinates in lattice units, as raster_mask maps them: X = (x - DX0) / (DX1 - DX0) * nx, Y = (y + y_half) / (2 y_half) * ny,
+    so that cell (i, j) covers [i, i+1) x [j, j+1)."""
+    if y_half is None:
+        y_half = domain_y_half(nx, ny)
+    return (np.asarray(x, np.float64) - DX0) / (DX1 - DX0) * nx, (np.asarray(y, np.float64) + y_half) / (2 * y_half) * ny
+
+
+def surface_stations(geom: Geometry, nx: int, ny: int, y_half: Optional[float] = None) -> Dict[str, object]:
+    """One station per panel of the member's panel polyline (geom.xp, geom.yp: NP = 160 panels), for read-outs along the wall (the
+    boundary-layer rakes of polar.boundary_layer_points).  All arrays are [NP] float64 in panel order unless said otherwise:
+      x, y          the panel's midpoint in lattice units, mapped as raster_mask maps it (to_lattice)
+      nrm_x, nrm_y  the unit outward normal in lattice units: the panel's direction turned by -90 degrees where the polyline runs
+                    counter-clockwise (its shoelace area is positive, as for Selig order: trailing edge, upper side, leading edge,
+                    lower side), by +90 degrees where it runs clockwise
+      tan_x, tan_y  the unit tangent pointing from the leading edge to the trailing edge on each side, so that attached flow has a
+                    positive tangential speed on both surfaces: against the panel's direction on the side the polyline walks first
+                    (trailing edge to leading edge), along it on the other
+      upper         bool: the panel lies on the upper side.  The leading edge is the polyline point of smallest x in the body's own
+                    axes; the panels before it are the first side, which is the upper one of a counter-clockwise polyline
+      x_over_c      x of the midpoint in the body's own axes, rotated back by the member's angle geom.a_deg about (0.25, 0)
+      lattice       (nx, ny), and chord_cells = nx / (DX1 - DX0), the cells of one chord
+    A panel of zero length has NaN normal and tangent."""
+    xp, yp = np.asarray(geom.xp, np.float64), np.asarray(geom.yp, np.float64)
+    X, Y = to_lattice(xp, yp, nx, ny, y_half)
+    dx, dy = np.diff(X), np.diff(Y)
+    length = np.hypot(dx, dy)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ux, uy = dx / length, dy / length
+    area = 0.5 * float(np.sum(X * np.roll(Y, -1) - np.roll(X, -1) * Y))     # shoelace, the closing segment included
+    ccw = area > 0
+    nrm_x, nrm_y = (uy, -ux) if ccw else (-uy, ux)
+    body = rotate(list(zip(xp.tolist(), yp.tolist())), -geom.a_deg)         # back into the body's own axes
+    bx = np.array([p[0] for p in body])
+    le = int(np.argmin(bx))
+    first = np.arange(xp.size - 1) < le                                     # the side walked from the trailing edge to the leading edge
+    sign = np.where(first, -1.0, 1.0)
+    return {"x": 0.5 * (X[:-1] + X[1:]), "y": 0.5 * (Y[:-1] + Y[1:]), "nrm_x": nrm_x, "nrm_y": nrm_y, "tan_x": sign * ux, "tan_y": sign * uy,
+            "upper": first if ccw else ~first, "x_over_c": 0.5 * (bx[:-1] + bx[1:]), "lattice": (int(nx), int(ny)),
+            "chord_cells": nx / (DX1 - DX0)}

@@ -26,6 +26,10 @@ With a prescribed far-field profile (``PolarEngine.enable_far_profile`` / ``set_
 equilibrium of its own (rho, ux, uy); ``run_polar(far_field="vortex")`` uses it for the textbook far-field correction of airfoil
 computations, the free stream plus a point vortex that follows the lift (:func:`far_profile`, :func:`vortex_update`);
 ``run_polar(vortex_on="device")`` leaves those updates to the device (``PolarEngine.enable_far_vortex``), in stream order and without a wait.
+With probe points (``PolarEngine.enable_probes`` / ``set_probes``) the device samples (rho, ux, uy) at caller-given points of every member
+and keeps their running sums; ``run_polar(boundary_layer=True)`` puts rakes along the wall normals (``geometry.surface_stations``,
+:func:`boundary_layer_points`) and attaches the boundary-layer read-out of every angle (:func:`boundary_layer`: x/c, Ue, delta*, theta, Cf,
+H per surface and where the skin friction changes sign).
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -63,6 +67,7 @@ EXPORTS = (
     "wtp_enable_trt",
     "wtp_enable_far_profile", "wtp_set_far_profile", "wtp_read_far_profile",
     "wtp_enable_far_vortex", "wtp_set_far_vortex", "wtp_far_vortex", "wtp_far_vortex_update", "wtp_far_vortex_log",
+    "wtp_enable_probes", "wtp_set_probes", "wtp_probe_sums", "wtp_probe_sample",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
@@ -77,6 +82,9 @@ VORTEX_NORMS = ("hypot", "sqrt")                                   # vortex_upda
 FRAMES = ("body", "wind")                                          # run_polar's ways to set the angle: turn the body, or the free stream
 WIND_ALPHA_MAX = 30.0                                              # degrees: the largest |angle| of a frame="wind" sweep
 MEAN_SUMS = ("rho", "ux", "uy", "rho2", "ux2", "uy2", "uxuy")      # wtp_mean_sums' planes, in its order
+WTP_MAX_PROBES = 1 << 20                                           # the most probe points a member holds (wt_polar.h)
+BL_HEIGHT_DEFAULT, BL_SPACING_DEFAULT = 0.15, 0.5                  # run_polar's boundary-layer rake: its height in chords and the spacing of its points in cells
+BL_EDGE = 0.99                                                     # the share of the rake's largest tangential speed that marks the boundary layer's edge
 
 _lib = None
 
@@ -140,6 +148,10 @@ def load_polar_library(path: str = POLAR_LIB_PATH, optional: Sequence[str] = ())
         "wtp_far_vortex": ([B, dp, dp], c_int),
         "wtp_far_vortex_update": ([B], c_int),
         "wtp_far_vortex_log": ([B, c_int, c_int, ip, dp, dp, dp, dp, POINTER(c_int32)], c_int),
+        "wtp_enable_probes": ([B, c_int], c_int),
+        "wtp_set_probes": ([B, c_int, c_int, dp, dp], c_int),
+        "wtp_probe_sums": ([B, c_int, ip, dp, dp, dp], c_int),
+        "wtp_probe_sample": ([B, c_int, dp, dp, dp], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         if name in optional and path != POLAR_LIB_PATH and not hasattr(lib, name):
@@ -221,6 +233,7 @@ class PolarEngine:
         self._far_profile = False
         self._far_vortex = False
         self._far_given = np.zeros(self.members, bool)      # which members have tables (set_far_profile, enable_far_vortex)
+        self._probes = 0                                    # probe points per member (0: the read-out is off)
         code = WT_F32 if self.dtype == np.float32 else WT_F64
         if storage == "half":
             _check(self._lib.wtp_create_stored(self.nx, self.ny, code, WTP_STORE_HALF, self.members, self.history_cap, int(device),
@@ -513,6 +526,46 @@ class PolarEngine:
         out["clipped"] = clipped != 0
         return out
 
+    def enable_probes(self, npoints: int) -> None:
+        """Sample (rho, ux, uy) at `npoints` points per member from the next sample on and keep the running sums (wt_polar.h "Probe
+        points"); set_probes gives the points, and until then every point is inactive.  Calling it again starts over: every point
+        inactive, the sums empty.  0 switches the read-out off and releases its buffers.  WTError (WT_ERR_ARG) for a count outside
+        [0, WTP_MAX_PROBES], (WT_ERR_OOM) where the buffers do not fit; the batch then goes on as it was.  Works with every dtype
+        and storage; independent of the other read-outs, and every other value keeps its bits."""
+        _check(self._lib.wtp_enable_probes(self._b, int(npoints)))
+        self._probes = int(npoints)
+
+    @property
+    def probes_enabled(self) -> bool:
+        return self._probes > 0
+
+    def set_probes(self, x, y, first: int = 0) -> None:
+        """The points of members first .. first+count-1: x, y [count][P] (or one member's [P]) float64, lattice units, the centre of
+        cell (i, j) at (i + 0.5, j + 0.5); valid inside [0.5, NX - 0.5] x [0.5, NY - 0.5].  A point whose x is NaN is inactive: never
+        sampled, its sums stay 0.  Any other point outside the rectangle raises WTError (WT_ERR_ARG) and the batch is left as it
+        was.  The sums and the counts of the members touched, and of no other, start again at zero.  After enable_probes."""
+        xs, ys = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, y))
+        if xs.ndim == 1:
+            xs, ys = xs[None], (ys[None] if ys.ndim == 1 else ys)
+        if xs.ndim != 2 or xs.shape != ys.shape or xs.shape[1] != self._probes:
+            raise ValueError(f"x and y must both have shape [count][P] = [count][{self._probes}], got {xs.shape} and {ys.shape}")
+        _check(self._lib.wtp_set_probes(self._b, int(first), int(xs.shape[0]), _dp(xs), _dp(ys)))
+
+    def probe_sums(self, member: int) -> Dict[str, object]:
+        """One member's sample count `n` and the sums of rho, ux, uy over the samples at its points, [P] float64 each (0 at inactive
+        points).  The time mean at a point is sum / n."""
+        n = np.zeros(1, np.int64)
+        out = {k: np.empty(self._probes) for k in ("rho", "ux", "uy")}
+        _check(self._lib.wtp_probe_sums(self._b, int(member), _ip(n), *(_dp(out[k]) for k in ("rho", "ux", "uy"))))
+        return {"n": int(n[0]), **out}
+
+    def probe_sample(self, member: int) -> Dict[str, np.ndarray]:
+        """rho, ux, uy of the last emitted state at one member's points, [P] float64 each, NaN at inactive points: the twin of
+        forces().  Adds nothing to the sums.  WTError (WT_ERR_STATE) after write_f until a step has run."""
+        out = {k: np.empty(self._probes) for k in ("rho", "ux", "uy")}
+        _check(self._lib.wtp_probe_sample(self._b, int(member), *(_dp(out[k]) for k in ("rho", "ux", "uy"))))
+        return out
+
     def clamp_events(self):
         """(density events, speed events), [B] each."""
         a, b = np.empty(self.members, np.int64), np.empty(self.members, np.int64)
@@ -641,6 +694,8 @@ class PolarPoint:
     # Plain attributes that run_polar sets: no fields and no constructor arguments, so that the constructor ends with `mean` as it did.
     vortex_strength = None
     vortex_source = None
+    # The boundary-layer read-out of a run_polar(boundary_layer=True) sweep, boundary_layer() of this angle (None: not sampled).  A plain attribute too.
+    boundary_layer = None
 
     def __post_init__(self, cl_total_mean, cl_total_std, cd_total_mean, cd_total_std, cm_total_mean, cm_total_std, cd_friction_mean,
                       mean):
@@ -806,6 +861,137 @@ def polar_point(alpha: float, step, fx, fy, surf, rev, u0: float, nx: int, clamp
                       surface=surface, **total)
 
 
+# ---- probe points and the boundary layer -------------------------------------------------------
+def probe_weights(x, y, nx: int, ny: int):
+    """The weight rule of the probe points (wt_polar.h "Probe points") in NumPy, elementwise over x, y (lattice units, the centre of
+    cell (i, j) at (i + 0.5, j + 0.5)): (i0, j0, w) with the base cell of each point, int64, and w [4][...] float64, the weights
+    w00, w10, w01, w11 of the cells (i0, j0), (i0+1, j0), (i0, j0+1), (i0+1, j0+1).  In float64, one rounding per operation:
+        gx = x - 0.5;  i0 = min(max(floor(gx), 0), NX - 2);  tx = gx - i0;  sx = 1.0 - tx        (and gy, j0, ty, sy from y)
+        w00 = sx*sy;  w10 = tx*sy;  w01 = sx*ty;  w11 = tx*ty
+    A point whose x is NaN is inactive: i0 = j0 = -1 and its weights are 0.  Any other point outside [0.5, NX - 0.5] x
+    [0.5, NY - 0.5] (a NaN y included) raises ValueError, as wtp_set_probes refuses it."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    if x.shape != y.shape:
+        raise ValueError(f"x and y must have one shape, got {x.shape} and {y.shape}")
+    off = np.isnan(x)
+    with np.errstate(invalid="ignore"):
+        ok = (x >= 0.5) & (x <= nx - 0.5) & (y >= 0.5) & (y <= ny - 0.5)
+    if not (ok | off).all():
+        k = np.argwhere(~(ok | off))[0]
+        raise ValueError(f"point {tuple(int(v) for v in k)}, ({x[tuple(k)]!r}, {y[tuple(k)]!r}), lies outside [0.5, {nx - 0.5}] x [0.5, {ny - 0.5}] "
+                         f"and is not inactive (x = NaN)")
+    gx, gy = np.where(off, 0.0, x) - 0.5, np.where(off, 0.0, y) - 0.5
+    i0 = np.minimum(np.maximum(np.floor(gx), 0.0), nx - 2.0)
+    j0 = np.minimum(np.maximum(np.floor(gy), 0.0), ny - 2.0)
+    tx, ty = gx - i0, gy - j0
+    sx, sy = 1.0 - tx, 1.0 - ty
+    w = np.where(off, 0.0, np.stack([sx * sy, tx * sy, sx * ty, tx * ty]))
+    return np.where(off, -1, i0.astype(np.int64)), np.where(off, -1, j0.astype(np.int64)), w
+
+
+def boundary_layer_points(stations: Dict[str, object], height: float, spacing: float):
+    """The rake points of geometry.surface_stations: (x, y, heights) with x, y [S * H] float64, station-major and height-minor, the
+    points station + h * n along the outward normal n for h = heights = spacing, 2 spacing, ... <= height (lattice units; H of them).
+    The macroscopic planes are column-major, y fastest, so that with this order the gathers of neighbouring points fall into a few
+    columns.  A point outside the valid rectangle [0.5, NX - 0.5] x [0.5, NY - 0.5] of the stations' lattice becomes NaN in x and y:
+    inactive as a probe point, and its station's boundary layer is NaN.  height >= spacing > 0, else ValueError."""
+    height, spacing = float(height), float(spacing)
+    if not (spacing > 0.0 and height >= spacing and math.isfinite(height)):
+        raise ValueError(f"a rake needs height >= spacing > 0, got height {height!r}, spacing {spacing!r}")
+    heights = spacing * np.arange(1, int(math.floor(height / spacing + 1e-9)) + 1)
+    nx, ny = stations["lattice"]
+    x = np.asarray(stations["x"])[:, None] + heights[None, :] * np.asarray(stations["nrm_x"])[:, None]
+    y = np.asarray(stations["y"])[:, None] + heights[None, :] * np.asarray(stations["nrm_y"])[:, None]
+    with np.errstate(invalid="ignore"):
+        ok = (x >= 0.5) & (x <= nx - 0.5) & (y >= 0.5) & (y <= ny - 0.5)
+    return np.where(ok, x, np.nan).ravel(), np.where(ok, y, np.nan).ravel(), heights
+
+
+def _sign_changes(xc, cf):
+    """(x_sep, x_reattach) of one side's Cf along x/c, both ordered from the leading edge: the first place where Cf turns from >= 0 to
+    < 0 and the next place where it turns back to >= 0, each linearly interpolated between the two stations; NaN where there is
+    none.  Stations whose Cf is NaN are skipped."""
+    keep = np.isfinite(cf) & np.isfinite(xc)
+    xc, cf = xc[keep], cf[keep]
+
+    def crossing(k):
+        return float(xc[k - 1] + (xc[k] - xc[k - 1]) * (cf[k - 1] / (cf[k - 1] - cf[k])))
+
+    sep = next((k for k in range(1, cf.size) if cf[k - 1] >= 0.0 and cf[k] < 0.0), None)
+    if sep is None:
+        return float("nan"), float("nan")
+    back = next((k for k in range(sep + 1, cf.size) if cf[k] >= 0.0), None)
+    return crossing(sep), (crossing(back) if back is not None else float("nan"))
+
+
+def boundary_layer(stations: Dict[str, object], means: Dict[str, np.ndarray], heights, u0: float, tau: float) -> Dict[str, object]:
+    """The boundary-layer read-out of one member from the time-mean velocity at its rake points: the columns of the reference's XFOIL
+    dump (x, Ue, delta*, theta, Cf, H per surface) as this lattice gives them.  `stations`: geometry.surface_stations; `means`: "ux",
+    "uy", the mean velocity at boundary_layer_points' points ([S * H] or [S][H]; PolarEngine.probe_sums over n); `heights`: that
+    function's, in cells.  Definitions, per station, with u_t(h) = mean u . t the speed along the station's tangent at height h:
+      Ue      = the u_t of largest magnitude over the rake's heights of one cell and more: the maximum of u_t wherever the outer flow
+                runs from the leading edge to the trailing edge, and negative on the stretch between the leading edge and the stagnation
+                point, where the layer runs towards the leading edge and the rake is read in its own direction.  The edge height h_e is
+                the lowest of those heights with u_t/Ue >= 0.99.
+      delta*  = integral from 0 to h_e of (1 - u_t/Ue) dh;  theta = integral from 0 to h_e of (u_t/Ue)(1 - u_t/Ue) dh;  H = delta*/theta.
+                Both by the trapezoid rule over the wall, where u_t(0) = 0, and the rake heights from one cell to h_e.  The samples
+                closer to the wall than one cell are left out: their stencils touch solid cells, whose stored velocity is 0 at the
+                cell centre and not at the wall.  NaN where Ue = 0 or theta = 0 (a layer thinner than one cell: every ratio 0 or 1).
+      Cf      = 2 nu (u_t(h_1)/h_1) / U0^2, with nu = (tau - 1/2)/3 and h_1 the first rake height >= 1 cell: a one-sided difference
+                from the wall.  nu is the molecular viscosity: with a Smagorinsky model on (run_polar's `les`) the eddy viscosity is
+                not in it.
+    A station whose rake holds an inactive point (NaN) is NaN throughout.  What this is not: there is no transition detection, the
+    wall is a staircase half a cell from the first fluid centre whatever the wall rule, and at a chord Reynolds number of a few
+    hundred the layer is a tenth of a chord thick.
+    Returns {"upper": side, "lower": side, "heights": heights}; a side holds, ordered from the leading edge by x/c: station (the
+    indices into `stations`), x_over_c, ue (Ue/U0), dstar and theta (in chords), cf, H, and the scalars x_sep, the x/c at which Cf
+    first turns negative going from the leading edge, linearly interpolated between the two stations, NaN if it never does, and
+    x_reattach, the next change of sign behind it, NaN if none.  Cf that is negative from the first station on (the stretch between
+    the leading edge and the stagnation point) is no separation."""
+    heights = np.asarray(heights, np.float64)
+    S, Hn = np.asarray(stations["x"]).size, heights.size
+    ux, uy = (np.asarray(means[k], np.float64).reshape(S, Hn) for k in ("ux", "uy"))
+    ut = ux * np.asarray(stations["tan_x"])[:, None] + uy * np.asarray(stations["tan_y"])[:, None]
+    kept = np.nonzero(heights >= 1.0)[0]
+    if kept.size == 0:
+        raise ValueError("the rake holds no height of one cell or more")
+    k1 = int(kept[0])
+    nu = (float(tau) - 0.5) / 3.0
+    chord = float(stations["chord_cells"])
+    ue, dstar, theta = (np.full(S, np.nan) for _ in range(3))
+    cf = 2.0 * nu * (ut[:, k1] / heights[k1]) / (u0 * u0)                   # (NaN where the rake's sample is)
+    for s in range(S):
+        u = ut[s]
+        if not np.isfinite(u).all():
+            cf[s] = np.nan
+            continue
+        top = float(u[kept][np.argmax(np.abs(u[kept]))])
+        ue[s] = top / u0
+        if top == 0.0:
+            continue
+        edge = next(k for k in kept if u[k] / top >= BL_EDGE)
+        h = np.concatenate([[0.0], heights[k1:edge + 1]])
+        r = np.concatenate([[0.0], u[k1:edge + 1]]) / top
+        f1, f2 = 1.0 - r, r * (1.0 - r)
+        dh = np.diff(h)
+        dstar[s] = float(np.sum(0.5 * (f1[1:] + f1[:-1]) * dh)) / chord
+        theta[s] = float(np.sum(0.5 * (f2[1:] + f2[:-1]) * dh)) / chord
+    with np.errstate(invalid="ignore", divide="ignore"):
+        shape = np.where(theta != 0.0, dstar / theta, np.nan)
+    out: Dict[str, object] = {"heights": heights}
+    upper, xc = np.asarray(stations["upper"], bool), np.asarray(stations["x_over_c"], np.float64)
+    for name, side in (("upper", upper), ("lower", ~upper)):
+        idx = np.nonzero(side)[0]
+        idx = idx[np.argsort(xc[idx], kind="stable")]
+        x_sep, x_re = _sign_changes(xc[idx], cf[idx])
+        out[name] = {"station": idx, "x_over_c": xc[idx], "ue": ue[idx], "dstar": dstar[idx], "theta": theta[idx], "cf": cf[idx], "H": shape[idx],
+                     "x_sep": x_sep, "x_reattach": x_re}
+    return out
+
+
+_boundary_layer_of = boundary_layer              # (run_polar has an argument of the function's name)
+
+
 # ---- the far-field correction ------------------------------------------------------------------
 def far_profile(nx: int, ny: int, u0: float, v0: float, strength: float, source: float, xc: float, yc: float, dtype="float32"):
     """The tables (left [3][NY], bottom [3][NX], top [3][NX]; planes rho, ux, uy) of PolarEngine.set_far_profile for the free stream
@@ -864,7 +1050,8 @@ def vortex_update(strength, source, fx, fy, alpha, u0: float, relax: float, boun
 def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", nx: int = 320, ny: int = 160, dtype="float32",
               u0: float = U0_DEFAULT, tau: Optional[float] = None, re: Optional[float] = None, warmup_steps: Optional[int] = None,
               samples: int = 256, sample_every: int = 12, device: int = 0, loads: bool = True,
-              total_forces: bool = False, mean_fields: bool = False, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
+              total_forces: bool = False, mean_fields: bool = False,
+              boundary_layer: bool = False, bl_height: float = BL_HEIGHT_DEFAULT, bl_spacing: float = BL_SPACING_DEFAULT, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
               collision: str = "bgk", magic: float = MAGIC_DEFAULT,
               far_field: str = "uniform", vortex_every: int = 96, vortex_relax: float = 0.3, vortex_after: Optional[int] = None,
               vortex_on: str = "host", storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
@@ -945,7 +1132,18 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     strengths and `state` are built from the device's log.  Device and host mode are the same run, bit for bit, unless an update clips
     (vortex_history["clipped"]): the device forms the norm of (strength, source) as sqrt(s*s + q*q) where the host uses np.hypot
     (vortex_update's `norm`), so a clipped update may differ in the last bit of its scale.  It is not read with the uniform far field.
-    An unknown vortex_on raises ValueError before an engine is created."""
+    An unknown vortex_on raises ValueError before an engine is created.
+    `boundary_layer`: also sample the flow along rakes normal to the wall, one rake per panel of the body (geometry.surface_stations,
+    boundary_layer_points: 160 stations, points every `bl_spacing` cells up to `bl_height` chords from the wall), as probe points on the
+    device (PolarEngine.enable_probes, wt_polar.h "Probe points"), and attach boundary_layer() of the time means as
+    PolarPoint.boundary_layer: x/c, Ue, delta*, theta, Cf and H per surface, the columns of the reference's XFOIL boundary-layer dump, and
+    x_sep / x_reattach, where the skin friction changes sign.  With frame="body" the rakes stand on each angle's rotated body, with
+    frame="wind" one set serves every angle.  The probes are on before the warm-up, which takes no sample, and a continued sweep
+    (`start`) starts with empty sums, like the other running sums.  Cf uses the molecular viscosity (tau - 1/2)/3, also with `les`.
+    polar_rows then carries x_sep_upper and x_sep_lower.  Off by default: the sweep then launches the kernels, and returns the rows,
+    results and bits, it always did; with it on every other value is the same bits.  bl_height and bl_spacing must be finite and
+    positive, with the rake reaching at least one cell (bl_height * chord_cells(nx) >= max(bl_spacing, 1)) and at most WTP_MAX_PROBES
+    points per angle, else ValueError before an engine is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -982,6 +1180,15 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         vortex_relax = float(vortex_relax)
         if not 0.0 < vortex_relax <= 1.0:                      # (false for a NaN)
             raise ValueError(f"vortex_relax must be in (0, 1], got {vortex_relax!r}")
+    if boundary_layer:
+        bl_height, bl_spacing = float(bl_height), float(bl_spacing)
+        if not (math.isfinite(bl_height) and math.isfinite(bl_spacing) and bl_height > 0.0 and bl_spacing > 0.0):
+            raise ValueError(f"bl_height and bl_spacing must be finite and positive, got {bl_height!r} and {bl_spacing!r}")
+        rake_cells = bl_height * chord_cells(int(nx))
+        if rake_cells < max(bl_spacing, 1.0):
+            raise ValueError(f"the boundary-layer rake must reach at least one cell and one spacing: bl_height {bl_height!r} is {rake_cells:.3g} cells")
+        if geo.NP * math.floor(rake_cells / bl_spacing + 1e-9) > WTP_MAX_PROBES:
+            raise ValueError(f"the boundary-layer rakes would hold more than {WTP_MAX_PROBES} points per angle")
     wind = frame == "wind"
     if wind and any(not abs(a) <= WIND_ALPHA_MAX for a in alphas):
         raise ValueError(f'frame="wind" takes angles within +-{WIND_ALPHA_MAX:g} degrees, got {alphas!r}')
@@ -1003,6 +1210,11 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         geoms = [geo.build_geometry(nx, ny, a, user, shape) for a in alphas]
         ux0 = u0
     masks = np.stack([g.mask for g in geoms])
+    if boundary_layer:                                         # one set of stations and rake points per geometry (one in all with frame="wind")
+        stations = [geo.surface_stations(g, nx, ny) for g in (geoms[:1] if wind else geoms)]
+        rakes = [boundary_layer_points(s, bl_height * chord_cells(nx), bl_spacing) for s in stations]
+        if wind:
+            stations, rakes = stations * len(alphas), rakes * len(alphas)
     with PolarEngine(nx, ny, len(alphas), dtype=dtype, history_cap=samples, device=device, storage=storage) as eng:
         eng.set_masks(masks)
         if walls == "interpolated":
@@ -1019,6 +1231,9 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_momentum_exchange(*quarter_chord(nx, ny))
         if mean_fields:
             eng.enable_mean_fields()
+        if boundary_layer:
+            eng.enable_probes(rakes[0][0].size)
+            eng.set_probes(np.stack([r[0] for r in rakes]), np.stack([r[1] for r in rakes]))
         if les is not None:
             eng.enable_les(les)
         if trt:
@@ -1091,6 +1306,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
         rho_ev, u_ev = eng.clamp_events()
         surfaces = [surface_cp(eng.surface(m), 0.0 if wind else a, u0) for m, a in enumerate(alphas)] if loads else [None] * len(alphas)
         means = [mean_flow(eng.mean_sums(m), u0) for m in range(len(alphas))] if mean_fields else [None] * len(alphas)
+        probe_sums = [eng.probe_sums(m) for m in range(len(alphas))] if boundary_layer else None
         state = eng.state() if keep_state else None
         if vortex and state is not None:
             state["vortex"] = {"strength": strength.copy(), "source": source.copy()}
@@ -1107,6 +1323,12 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     if vortex:
         for m, p in enumerate(points):
             p.vortex_strength, p.vortex_source = float(strength[m]), float(source[m])
+    if boundary_layer:
+        for m, p in enumerate(points):
+            n = probe_sums[m]["n"]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                means = {k: probe_sums[m][k] / n for k in ("rho", "ux", "uy")}
+            p.boundary_layer = _boundary_layer_of(stations[m], means, rakes[m][2], u0, tau)
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
                        walls=walls, frame=frame, storage=storage, state=state, collision=collision, magic=magic if trt else None,
                        far_field=far_field, vortex_history=vortex_history if vortex else None)
@@ -1119,13 +1341,32 @@ def sweep_alphas(start: float, end: float, step: float) -> List[float]:
             if round(start + i * step, 2) <= end + 1e-9]
 
 
+def _with_separation(result: PolarResult, rows: List[dict]) -> List[dict]:
+    """polar_rows' rows with x_sep_upper and x_sep_lower in front of Status where every point carries a boundary layer
+    (run_polar(boundary_layer=True)); the rows as they are otherwise.  "—" where the flow stays attached or the point failed."""
+    if any(getattr(p, "boundary_layer", None) is None for p in result.points):
+        return rows
+    out = []
+    for p, row in zip(result.points, rows):
+        row = dict(row)
+        status = row.pop("Status")
+        for side in ("upper", "lower"):
+            x = p.boundary_layer[side]["x_sep"]
+            row["x_sep_" + side] = round(x, 3) if p.converged and math.isfinite(x) else "—"
+        row["Status"] = status
+        out.append(row)
+    return out
+
+
 def polar_rows(result: PolarResult, forces: str = "pressure") -> List[dict]:
     """The page's sweep table (pages/Airfoil_Analysis.py:950-966), one row per angle.  Cm is the mean moment coefficient of a
     point that carries one (run_polar(loads=True)), "—" otherwise.
     A point converged when every sample is finite and the stability net held no site at a bound; a failed one shows "—"
     throughout, as the page's failed rows do.
     forces="total" (every point must carry the momentum exchange, run_polar(total_forces=True), else ValueError): CL, CD, L/D
-    and Cm from the totals, and between CD and L/D the pressure drag CDp and the friction drag CDf = CD - CDp."""
+    and Cm from the totals, and between CD and L/D the pressure drag CDp and the friction drag CDf = CD - CDp.
+    Where every point carries a boundary layer (run_polar(boundary_layer=True)) the rows also hold x_sep_upper and x_sep_lower, the
+    x/c at which the skin friction of that surface first turns negative ("—": attached); without it the rows are what they always were."""
     if forces not in ("pressure", "total"):
         raise ValueError(f'forces must be "pressure" or "total", got {forces!r}')
     rows = []
@@ -1141,7 +1382,7 @@ def polar_rows(result: PolarResult, forces: str = "pressure") -> List[dict]:
             else:
                 rows.append({"α (°)": p.alpha, "CL": "—", "CD": "—", "CDp": "—", "CDf": "—", "L/D": "—", "Cm": "—",
                              "Status": "❌ Failed"})
-        return rows
+        return _with_separation(result, rows)
     for p in result.points:
         if p.converged:
             ld = p.cl_mean / p.cd_mean if p.cd_mean != 0 else None
@@ -1150,4 +1391,4 @@ def polar_rows(result: PolarResult, forces: str = "pressure") -> List[dict]:
                          "Cm": round(p.cm_mean, 4) if p.cm_mean is not None else "—", "Status": "✅ Converged"})
         else:
             rows.append({"α (°)": p.alpha, "CL": "—", "CD": "—", "L/D": "—", "Cm": "—", "Status": "❌ Failed"})
-    return rows
+    return _with_separation(result, rows)

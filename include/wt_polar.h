@@ -477,6 +477,58 @@ WTP_API int wtp_far_vortex(wtp_batch *b, double *strength, double *source);
 WTP_API int wtp_far_vortex_update(wtp_batch *b);
 WTP_API int wtp_far_vortex_log(wtp_batch *b, int first, int count, int64_t *step, double *fx, double *fy, double *strength, double *source,
                                int32_t *clipped);
+/*
+ * Probe points: (rho, ux, uy) sampled at caller-given points of every member, bilinearly between cell centres, and the running sums
+ * of the samples, added on the device behind the force reduction of a sampled step.  A boundary-layer rake along the wall normals, a
+ * wake rake, a velocity profile at a station and a probe behind the trailing edge are all sets of such points; what is made of the
+ * sums is host arithmetic (airfoil_cfd_tool_amd.polar.boundary_layer).  The mean fields give the same numbers at 56 bytes per site;
+ * this read-out holds 64 bytes per point.  It is a read-out, per batch and opt-in.  Definition:
+ *   Points.  Member m holds P points (x, y) in lattice units.  Cell (i, j) covers [i, i+1) x [j, j+1) and its centre is
+ *   (i + 0.5, j + 0.5), as in the loads.  A point is valid when 0.5 <= x <= NX - 0.5 and 0.5 <= y <= NY - 0.5.  A point whose x is
+ *   NaN is inactive: its y is not read, it is never sampled, and its sums stay +0.  Any other point outside the rectangle (a NaN y
+ *   included) is WT_ERR_ARG, before any device call.
+ *   Weights.  Formed on the host in double, one rounding per operation, left to right as written:
+ *     gx = x - 0.5;  i0 = min(max((int)floor(gx), 0), NX - 2);  tx = gx - i0;  sx = 1.0 - tx
+ *     gy = y - 0.5;  j0 = min(max((int)floor(gy), 0), NY - 2);  ty = gy - j0;  sy = 1.0 - ty
+ *     w00 = sx*sy   (cell (i0,   j0))      w10 = tx*sy   (cell (i0+1, j0))
+ *     w01 = sx*ty   (cell (i0,   j0+1))    w11 = tx*ty   (cell (i0+1, j0+1))
+ *   A point on a cell centre has weight 1 on that cell; at x = NX - 0.5 the base cell is NX - 2 and tx = 1.
+ *   Sample.  For each of the three planes a in (rho, ux, uy) that wtp_read_macro would return, with a00, a10, a01, a11 the values of
+ *   the four cells converted exactly to double:
+ *     v = ((w00*a00 + w10*a10) + w01*a01) + w11*a11
+ *   with no contraction: seven roundings.  No cell is special-cased.  Solid cells hold (1, 0, 0), as the step stores them, and a
+ *   far-field cell holds what it stored; what the caller makes of a stencil that touches the body is the caller's business.
+ *   Running sums.  The device keeps three doubles per member and point, sum rho, sum ux, sum uy, added in sample order, one addition
+ *   per sample, and one sample count n per member (int64), which counts every sampled step whatever the member's points are.  The
+ *   sums are bit-identical to a NumPy loop that applies the formula above to wtp_read_macro at the sampled steps.
+ * On the device a member's points take 40 bytes each (the offset of the base cell in a macroscopic plane, -1 for an inactive point,
+ * and the four weights, structure of arrays) and its sums 24; the batch holds one scratch row of 24 bytes per point.
+ *
+ * wtp_enable_probes switches the sampling on with npoints = P points per member, 1 <= P <= WTP_MAX_PROBES: it allocates the tables,
+ * the sums and the scratch row; every point of every member starts inactive and the sums and the counts start at zero; from the next
+ * sample on, every sampled step adds to the sums.  Calling it again, with the same count or another, starts over in the same way
+ * (another count reallocates).  Where the allocation fails it returns WT_ERR_OOM, holds nothing new, and the batch goes on working as
+ * it was.  npoints == 0 switches the read-out off and releases the buffers.  A count outside [0, WTP_MAX_PROBES] is WT_ERR_ARG.  It
+ * works on fp32, fp64 and half batches alike, because the planes it reads are the macroscopic ones.
+ * wtp_set_probes gives members [first, first+count) their points: x, y are [count][P] doubles.  A null pointer, a member range
+ * outside the batch or a point that is neither valid nor inactive is WT_ERR_ARG, before any device call, and the batch, its points and
+ * its sums are left as they were; WT_ERR_STATE while the read-out is off.  It uploads the tables and zeroes the sums and the counts of
+ * the members it touches, and of no other.  Samples already enqueued see the old points.
+ * wtp_probe_sums reads one member's count *n and its three sums, [P] doubles each; any output may be NULL.
+ * wtp_probe_sample returns the sample of the last emitted state at one member's points, [P] doubles each, NaN at inactive points; any
+ * output may be NULL.  It adds nothing to the sums or the count, like wtp_forces.  WT_ERR_STATE while the macroscopic planes are stale
+ * (after wtp_write_f, until a step has run).  Both are WT_ERR_ARG for a member outside the batch and WT_ERR_STATE while the read-out
+ * is off.
+ * wtp_init_equilibrium and wtp_clear_history zero the sums and the counts of all members; wtp_set_masks, wtp_write_f and
+ * wtp_write_stored zero those of the members they touch.  The points themselves survive all of these.  It is independent of
+ * wtp_enable_loads, wtp_enable_mex and wtp_enable_mean; with it on, every other value is the same bits.  A batch that never calls
+ * wtp_enable_probes launches the kernels it always launched and returns the bits it always returned.
+ */
+#define WTP_MAX_PROBES (1 << 20)
+WTP_API int wtp_enable_probes(wtp_batch *b, int npoints);
+WTP_API int wtp_set_probes(wtp_batch *b, int first, int count, const double *x, const double *y);
+WTP_API int wtp_probe_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy);
+WTP_API int wtp_probe_sample(wtp_batch *b, int member, double *rho, double *ux, double *uy);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -65,6 +65,13 @@ point vortex at the quarter chord that induces 0.01 at the nearest far-field cel
 switches select.  The line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --profile,
 --lib may name a build from before the entry points existed.
 
+    python tools/polar_bench.py --probes [--loads] [--mex] [--mean] [--lib PATH] [the same options as --loads]
+
+The same protocol for the probe points (wtp_enable_probes: one k_probe_batch behind the other read-outs) with run_polar's default
+boundary-layer rake on every member's airfoil (160 stations, a point every 0.5 cells up to 0.15 chords: 8320 points per member at
+320x160); with --loads / --mex / --mean those read-outs are on in both variants.  With --lib naming a build from before the entry points
+existed only the variant without probes is timed, so that a parent commit's library gives its figure by the same script and protocol.
+
 Tracing: run under `rocprofv3 --kernel-trace --stats -- python tools/polar_bench.py ...`.
 """
 import argparse
@@ -150,8 +157,18 @@ STORAGE = "native"      # --storage: the sampled protocols run on a batch of thi
 TRT = None      # --trt: the magic number the sampled protocols run the two-relaxation-time collision with (None: off)
 
 
-def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False):
-    """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats."""
+def _default_rakes(nx, ny, b):
+    """(x, y) [b][P]: run_polar's default boundary-layer rake on every member's airfoil (_masks' geometries)."""
+    pts = []
+    for a in _alphas(b):
+        st = pkg.geometry.surface_stations(pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412"), nx, ny)
+        pts.append(pkg.polar.boundary_layer_points(st, pkg.polar.BL_HEIGHT_DEFAULT * st["chord_cells"], pkg.polar.BL_SPACING_DEFAULT)[:2])
+    return np.stack([p[0] for p in pts]), np.stack([p[1] for p in pts])
+
+
+def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=False, mean=False, probes=None):
+    """Seconds of `steps` sampled steps, one figure per repeat; the history is emptied between repeats.  probes: (x, y) [b][P], the
+    probe points of every member (None: off)."""
     out = []
     with pkg.PolarEngine(nx, ny, b, history_cap=steps // every + 1, storage=STORAGE) as eng:
         eng.set_masks(masks)
@@ -164,6 +181,9 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.enable_momentum_exchange(*pkg.polar.quarter_chord(nx, ny))
         if mean:
             eng.enable_mean_fields()
+        if probes is not None:
+            eng.enable_probes(probes[0].shape[1])
+            eng.set_probes(*probes)
         if LES is not None:
             eng.enable_les(LES)
         if IBB:
@@ -251,6 +271,32 @@ def mean_cost(a):
             print(json.dumps(line), flush=True)
 
 
+def probes_cost(a):
+    variants = (False, True) if hasattr(pkg.polar.load_polar_library(), "wtp_enable_probes") else (False,)
+    for size in a.sizes.split(","):
+        nx, ny = (int(v) for v in size.split("x"))
+        for b in (int(v) for v in a.members.split(",")):
+            masks = _masks(nx, ny, b)
+            rakes = _default_rakes(nx, ny, b) if True in variants else None
+            t = {v: [] for v in variants}
+            for r in range(a.repeats):                 # in turn, so that a drift of the clocks lands on both
+                for on in variants:
+                    t[on] += bench_sampled(nx, ny, b, a.steps, a.warmup, masks, a.sample_every, a.loads, 1, mex=a.mex, mean=a.mean,
+                                           probes=rakes if on else None)
+            us = {k: np.array(v) / a.steps * 1e6 for k, v in t.items()}
+            med = {k: float(np.median(v)) for k, v in us.items()}
+            samples = a.steps // a.sample_every
+            line = {"tool": "polar_bench --probes", "lib": a.lib or "default", "storage": a.storage, "loads": bool(a.loads), "mex": bool(a.mex),
+                    "mean": bool(a.mean), "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps, "sample_every": a.sample_every,
+                    "repeats": a.repeats, "us_per_step_plain": [round(float(v), 3) for v in us[False]], "us_per_step_plain_median": round(med[False], 3)}
+            if True in variants:
+                per_sample = (med[True] - med[False]) * a.steps / samples
+                line.update({"points_per_member": int(rakes[0].shape[1]), "us_per_step_probes": [round(float(v), 3) for v in us[True]],
+                             "us_per_step_probes_median": round(med[True], 3), "probes_us_per_sample": round(per_sample, 3),
+                             "probes_fraction_of_step": round(med[True] / med[False] - 1.0, 5)})
+            print(json.dumps(line), flush=True)
+
+
 def bench_sequential(nx, ny, b, steps, warmup, masks):
     hs = []
     try:
@@ -284,6 +330,7 @@ def main():
     ap.add_argument("--loads", action="store_true", help="the sampled step with and without surface loads")
     ap.add_argument("--mex", action="store_true", help="the sampled step with and without the momentum-exchange readout")
     ap.add_argument("--mean", action="store_true", help="the sampled step with and without the mean fields")
+    ap.add_argument("--probes", action="store_true", help="the sampled step with and without probe points (run_polar's default boundary-layer rake)")
     ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
     ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
     ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
@@ -294,14 +341,16 @@ def main():
     ap.add_argument("--sample-every", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=None, help="timed windows per variant (default 7; 1 for the first form)")
     a = ap.parse_args()
-    plain = not (a.mean or a.mex or a.loads)
+    plain = not (a.mean or a.mex or a.loads or a.probes)
     if a.repeats is None:
         a.repeats = 1 if plain else 7
     if a.lib:
         unused = (("wtp_enable_trt", a.trt is None), ("wtp_enable_far_profile", not a.profile), ("wtp_set_far_profile", not a.profile),
                   # the device-side far-field vortex and the tables' read-back: nothing here calls them
                   ("wtp_read_far_profile", True), ("wtp_enable_far_vortex", True), ("wtp_set_far_vortex", True), ("wtp_far_vortex", True),
-                  ("wtp_far_vortex_update", True), ("wtp_far_vortex_log", True))
+                  ("wtp_far_vortex_update", True), ("wtp_far_vortex_log", True),
+                  # the probe points: only --probes calls them, and with an older build it times the variant without them alone
+                  ("wtp_enable_probes", True), ("wtp_set_probes", True), ("wtp_probe_sums", True), ("wtp_probe_sample", True))
         pkg.polar.load_polar_library(a.lib, optional=tuple(name for name, free in unused if free))
     if a.storage == "half" and a.ibb:
         ap.error("--storage half does not combine with --ibb")
@@ -312,6 +361,8 @@ def main():
         ap.error("--profile times the plain stepping form only")
     global LES, IBB, WIND, STORAGE, TRT
     LES, IBB, WIND, STORAGE, TRT = a.les, a.ibb, a.wind, a.storage, a.trt
+    if a.probes:
+        return probes_cost(a)
     if a.mean:
         return mean_cost(a)
     if a.mex:
