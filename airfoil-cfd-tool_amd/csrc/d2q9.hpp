@@ -434,8 +434,10 @@ __device__ __forceinline__ void collide_trt(const T (&fin)[9], T tau, T lam, T c
 }
 
 // What a step kernel does with a population whose source cell is solid: half-way bounce-back (the page's), or linear interpolated
-// bounce-back with a wall distance per link (wall_incoming).
-enum : int { WALL_HALFWAY = 0, WALL_INTERP = 1 };
+// bounce-back with a wall distance per link (wall_incoming), or the same with a wall velocity per link on top (its second overload).
+enum : int { WALL_HALFWAY = 0, WALL_INTERP = 1, WALL_MOVING = 2 };
+// The wall rule reads the wall distances: both interpolating rules.
+__host__ __device__ constexpr bool wall_has_links(int wall) { return wall != WALL_HALFWAY; }
 
 // Linear interpolated bounce-back (Bouzidi, Firdaouss and Lallemand 2001; include/wt_polar.h "Interpolated bounce-back").  A link is an
 // interior fluid cell x and a direction k whose neighbour x + e_k is solid; q in (0, 1] is the fraction of the link at which it crosses
@@ -457,6 +459,28 @@ __device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bo
     const T inv = T(1.0) / two;
     return inv * a + (T(1.0) - inv) * *h;
 }
+
+// The same link with a moving wall (Ladd's term carried through the interpolation; include/wt_polar.h "Wall velocity"): un = e_k . u_w
+// at the link's wall point, the wall density taken as 1, w the link's lattice weight as feq_all forms it (T(1)/T(9) or T(1)/T(36)),
+//   d = (T(6)*w) * un
+//   q <  0.5:  fin = (two*a + (1 - two)*g) - d     if x - e_k is not solid, else fin = a - d
+//   q >= 0.5:  fin = (inv*a + (1 - inv)*h) - inv*d
+// in the same contract.  With un = +0, d = +0 and fin has the bits of the overload above.
+template <typename T>
+__device__ __forceinline__ T wall_incoming(T q, T a, const T *__restrict__ g, bool g_solid, const T *__restrict__ h, T w, T un)
+{
+    const T d = (T(6.0) * w) * un;
+    const T two = T(2.0) * q;
+    if (q < T(0.5)) {
+        if (g_solid) return a - d;
+        return (two * a + (T(1.0) - two) * *g) - d;
+    }
+    const T inv = T(1.0) / two;
+    return (inv * a + (T(1.0) - inv) * *h) - inv * d;
+}
+// The lattice weight of direction k = 1..8 as feq_all forms it.
+template <typename T>
+__device__ __forceinline__ constexpr T link_weight(int k) { return k <= 4 ? T(1.0) / T(9.0) : T(1.0) / T(36.0); }
 
 // What a step kernel writes into a far-field cell (inlet column, top and bottom rows): the equilibrium of the axial free stream (U0, 0)
 // (the page's), that of an inclined one (U0, V0) (include/wt_polar.h "Inclined free stream"), or that of a prescribed (rho, ux, uy) per

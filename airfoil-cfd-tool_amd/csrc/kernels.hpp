@@ -40,6 +40,8 @@ enum : uint8_t { TILE_GENERAL = 0, TILE_FAST = 1, TILE_SOLID = 2, TILE_INLET = 3
 // WALL selects what the interior branch does with a population whose source cell is solid: WALL_HALFWAY, or WALL_INTERP with the wall
 // distances `wq` (wall_incoming, d2q9.hpp): eight planes laid out like population planes 1..8, plane k - 1 holding q of direction k
 // at the link's fluid cell; `wq` points at column 0 of plane 0, as `s` does.  q is read only on lanes whose source cell is solid.
+// WALL_MOVING is WALL_INTERP with the wall-normal velocities `wu` on top (wall_incoming's second overload): eight planes laid out and
+// pointed at like `wq`, read on the lanes that read q and on no others.
 // FAR selects what the far-field branch writes: FAR_AXIAL, feq(1, U0, 0), FAR_INCLINED, feq(1, U0, V0) with the member's cross-flow `V0`, or
 // FAR_PROFILE, feq(rho, ux, uy) of the cell's entry in the member's tables `prof` (FarProfile, d2q9.hpp), which also become the stored moments.
 // S is the stored element of the lattices `s` and `d`: every population read goes through lat_load and every one written through
@@ -50,7 +52,7 @@ template <typename T, int COLL = COLLIDE_BGK, int WALL = WALL_HALFWAY, int FAR =
 __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restrict__ d, T *__restrict__ macro,
                                              const uint8_t *__restrict__ m, const Geom &g, int i, int j,
                                              T tau, T U0, bool emit, T cles = T(0.0), const T *__restrict__ wq = nullptr, T V0 = T(0.0),
-                                             T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>())
+                                             T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>(), const T *__restrict__ wu = nullptr)
 {
     const long c = (long)i * g.pitch + j;
     const int gi = i + g.gi0;
@@ -78,14 +80,14 @@ __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restr
         feq_all(rho, ux, uy, out);
     } else {                                                       // html:324-359 interior fluid
         T fin[9];
-        [[maybe_unused]] unsigned wall = 0;                        // WALL_INTERP: bit k, fin[k]'s source cell is solid
+        [[maybe_unused]] unsigned wall = 0;                        // WALL_INTERP, WALL_MOVING: bit k, fin[k]'s source cell is solid
 #pragma unroll
         for (int k = 0; k < 9; k++) {
             const long src = c - (long)ex_of(k) * g.pitch - ey_of(k);
-            if constexpr (WALL == WALL_INTERP) wall |= k > 0 && m[src] ? 1u << k : 0u;
+            if constexpr (wall_has_links(WALL)) wall |= k > 0 && m[src] ? 1u << k : 0u;
             fin[k] = m[src] ? lat_load<T>(s + opp_of(k) * g.plane + c, opp_of(k)) : lat_load<T>(s + k * g.plane + src, k);
         }
-        if constexpr (WALL == WALL_INTERP) {
+        if constexpr (wall_has_links(WALL)) {
             static_assert(std::is_same<S, T>::value, "interpolated bounce-back reads its neighbours from a native lattice: not available with half storage");
             // The gather above is the half-way one, nine loads in flight together, and on a link it has fetched a = s[o](x), o = opp(k),
             // the link's direction: x + e_o = src is solid and x - e_o = `behind` is the cell the link comes from.  Waves that touch
@@ -97,8 +99,12 @@ __device__ __forceinline__ void site_general(const S *__restrict__ s, S *__restr
                     if (!(wall >> k & 1u)) continue;
                     const int o = opp_of(k);
                     const long behind = c + (long)ex_of(k) * g.pitch + ey_of(k);
-                    fin[k] = wall_incoming<T>(wq[(o - 1) * g.plane + c], fin[k], s + o * g.plane + behind, m[behind] != 0,
-                                              s + k * g.plane + c);
+                    if constexpr (WALL == WALL_MOVING)
+                        fin[k] = wall_incoming<T>(wq[(o - 1) * g.plane + c], fin[k], s + o * g.plane + behind, m[behind] != 0,
+                                                  s + k * g.plane + c, link_weight<T>(o), wu[(o - 1) * g.plane + c]);
+                    else
+                        fin[k] = wall_incoming<T>(wq[(o - 1) * g.plane + c], fin[k], s + o * g.plane + behind, m[behind] != 0,
+                                                  s + k * g.plane + c);
                 }
             }
         }

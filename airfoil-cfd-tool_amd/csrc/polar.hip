@@ -25,7 +25,8 @@
 // ux, uy at the member's own points, bilinearly between cell centres, and adds the three values of each point to its running sums, one
 // owner lane per point.  A batch that never enables them launches the kernels it always launched.
 //
-// The step has one tiled kernel, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR>: step_tile (step_fast.hpp) of the wave's tile with
+// The step has one tiled kernel body, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR> (and k_wallvel_batch around the same body):
+// step_tile (step_fast.hpp) of the wave's tile with
 // the collision, the wall rule and the far field as template arguments, and the values each of them reads per member in one argument
 // whose members exist only in the variants that read them (StepModel).  The models below select among its instantiations.
 //
@@ -37,6 +38,13 @@
 // step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
 // collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction (mex_member) with the interpolated link
 // rule.  A batch that has it off launches the kernels it always launched, with the arguments they always had.
+//
+// Wall velocity (wtp_enable_wall_velocity) is a third wall rule on top of the second: while it is on, wtp_step launches k_wallvel_batch,
+// k_step_batch's body (step_member) with WALL_MOVING under a name of its own: the same step_tile with the moving-wall overload of
+// wall_incoming at the links of its general tiles and eight more planes per
+// member, the wall-normal velocities, read on the lanes that read a wall distance, with every collision and every far field, and a sample's
+// momentum exchange comes from k_mex_wallvel_batch (mex_member with LinkMoving).  Native storage only.  A batch that has it off launches the
+// kernels it always launched, with the arguments they always had.
 //
 // The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_batch with FAR_INCLINED, the same
 // step_tile with feq(1, U0, V0) in its far-field cells and one more value per member, with either collision and either wall rule,
@@ -178,6 +186,9 @@ struct wtp_batch {
     bool ibb = false;
     void *wq = nullptr;                  // [B][8] planes of T laid out like population planes 1..8, members q_stride elements apart
     long q_stride = 0;
+    // wall velocity (wtp_enable_wall_velocity), on top of interpolated bounce-back; the pointer is null until then
+    bool wallvel = false;
+    void *wu = nullptr;                  // [B][8] planes of T laid out like wq, members q_stride elements apart
     // inclined free stream (wtp_enable_wind); the pointer is null until then
     bool wind = false;
     void *wind_v = nullptr;              // [B] of T: the cross-flow V0 of every member
@@ -270,24 +281,27 @@ struct MemberTile {
 // that read it, so that a variant's kernel arguments are the ones it uses and no other.  (One unused pointer argument costs the
 // fp32 kernels about 30 VGPRs and two waves; see step_waves.)  In argument order:
 //   cles     [B]: c = (T)(18 sqrt(2) Cs^2) of every member                                        the Smagorinsky collisions
-//   wq       the members' wall distances, eight planes each, qstride elements apart               WALL_INTERP
+//   wq       the members' wall distances, eight planes each, qstride elements apart               WALL_INTERP, WALL_MOVING
+//   wu       the members' wall-normal velocities, eight planes each, ustride elements apart       WALL_MOVING
 //   vwind    [B]: the cross-flow V0 of every member                                               FAR_INCLINED
 //   lam      [B]: the magic number of every member                                                the two-relaxation-time collisions
 //   prof     the members' tables (FarProfile, d2q9.hpp), pstride elements apart, nxp elements per plane of `bottom` and `top`   FAR_PROFILE
 //   rev      walk members and tiles backwards (MemberTile)                                        every variant
 template <typename T, bool ON> struct ArgLes { const T *__restrict__ cles; };
 template <typename T, bool ON> struct ArgWallQ { const T *__restrict__ wq; long qstride; };
+template <typename T, bool ON> struct ArgWallU { const T *__restrict__ wu; long ustride; };
 template <typename T, bool ON> struct ArgWind { const T *__restrict__ vwind; };
 template <typename T, bool ON> struct ArgTrt { const T *__restrict__ lam; };
 template <typename T, bool ON> struct ArgProfile { const T *__restrict__ prof; long pstride; int nxp; };
 template <typename T> struct ArgLes<T, false> {};
 template <typename T> struct ArgWallQ<T, false> {};
+template <typename T> struct ArgWallU<T, false> {};
 template <typename T> struct ArgWind<T, false> {};
 template <typename T> struct ArgTrt<T, false> {};
 template <typename T> struct ArgProfile<T, false> {};
 template <typename T, int COLL, int WALL, int FAR>
-struct StepModel : ArgLes<T, coll_has_les(COLL)>, ArgWallQ<T, WALL == WALL_INTERP>, ArgWind<T, FAR == FAR_INCLINED>, ArgTrt<T, coll_is_trt(COLL)>,
-                   ArgProfile<T, FAR == FAR_PROFILE> {
+struct StepModel : ArgLes<T, coll_has_les(COLL)>, ArgWallQ<T, wall_has_links(WALL)>, ArgWallU<T, WALL == WALL_MOVING>, ArgWind<T, FAR == FAR_INCLINED>,
+                   ArgTrt<T, coll_is_trt(COLL)>, ArgProfile<T, FAR == FAR_PROFILE> {
     int rev;
 };
 
@@ -304,13 +318,17 @@ struct StepModel : ArgLes<T, coll_has_les(COLL)>, ArgWallQ<T, WALL == WALL_INTER
 //    scratch (the entry of a FAST tile's far row is loaded behind the collision, so it adds no live register to it).  One exception: the
 //    plain non-emitting fp32 kernel with interpolated walls, asked for its twin's 6 waves, got 79 VGPRs and 12 bytes of scratch per lane
 //    where the twin has none, so it asks for 5.
+//  * moving walls: every kernel asks for what its interpolating twin asks for and allocates 79 to 95 VGPRs in fp32 and 83 to 119 in fp64
+//    without scratch (profiles/polar_wallvel_isa.txt): the velocity is loaded on a link's lanes, behind the ballot, and dies in
+//    wall_incoming.  The same exception holds: asked for 6 waves, the plain non-emitting fp32 profile kernel got 79 VGPRs and 12 bytes of
+//    scratch per lane, so it asks for 5 like its twin.
 template <typename T, bool EMIT, int COLL, int WALL, int FAR>
 constexpr int step_waves()
 {
     if (FAR == FAR_AXIAL) return 0;
     if (sizeof(T) == 8) return 4;
     if (EMIT || COLL != COLLIDE_BGK) return 5;
-    return FAR == FAR_PROFILE && WALL == WALL_INTERP ? 5 : 6;
+    return FAR == FAR_PROFILE && wall_has_links(WALL) ? 5 : 6;
 }
 
 // One step of every member: step_tile (step_fast.hpp) of the wave's tile (MemberTile) with the member's tau and U0, on the member's
@@ -325,11 +343,12 @@ constexpr int step_waves()
 // The two-relaxation-time collisions are not built with FAR_AXIAL: a batch without wtp_enable_wind hands them an array of zeros as
 // vwind, and V0 = 0 gives the axial far field's bits because ex*U0 + ey*0 and U0*U0 + 0*0 are exact, so that the collision costs
 // eight instantiations per dtype and not sixteen.
+// step_member is the body; it has two entry points, so that the kernels of the half-way and the interpolating rule keep their name and
+// their number: k_step_batch (WALL_HALFWAY, WALL_INTERP) and k_wallvel_batch (WALL_MOVING, "wall velocity" below).
 template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL, int FAR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL, FAR>())))
-void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
-                  const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                  StepModel<T, COLL, WALL, FAR> a)
+__device__ __forceinline__ void step_member(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
+                                            const uint8_t *__restrict__ tiles, int tiles_per_col, const Geom &g, const MemberStrides &ms,
+                                            const T *__restrict__ params, const StepModel<T, COLL, WALL, FAR> &a)
 {
     const int lane = threadIdx.x & 63;
     const MemberTile w(g, tiles_per_col, a.rev);
@@ -337,16 +356,38 @@ void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ 
     const long m = w.member();
     const T tau = params[2 * m], U0 = params[2 * m + 1];
     T c = T(0.0), V0 = T(0.0), magic = T(0.0);
-    const T *q = nullptr;
+    const T *q = nullptr, *u = nullptr;
     FarProfile<T> fp;
     if constexpr (coll_has_les(COLL)) c = a.cles[m];
-    if constexpr (WALL == WALL_INTERP) q = a.wq + m * a.qstride;
+    if constexpr (wall_has_links(WALL)) q = a.wq + m * a.qstride;
+    if constexpr (WALL == WALL_MOVING) u = a.wu + m * a.ustride;
     if constexpr (FAR == FAR_INCLINED) V0 = a.vwind[m];
     if constexpr (coll_is_trt(COLL)) magic = a.lam[m];
     if constexpr (FAR == FAR_PROFILE) { fp.tab = a.prof + m * a.pstride; fp.pitch = g.pitch; fp.nxp = a.nxp; }
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
                                                          tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
-                                                         c, q, V0, magic, fp);
+                                                         c, q, V0, magic, fp, u);
+}
+
+template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL, int FAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL, FAR>())))
+void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
+                  const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                  StepModel<T, COLL, WALL, FAR> a)
+{
+    static_assert(WALL != WALL_MOVING, "the moving-wall variants are k_wallvel_batch's");
+    step_member<T, EMIT, LOADMODE, COLL, WALL, FAR>(fs, fd, macro, mask, tiles, tiles_per_col, g, ms, params, a);
+}
+
+// One step of every member with moving walls (include/wt_polar.h "Wall velocity"): step_member with WALL_MOVING, k_step_batch's arguments,
+// grid and waves; every collision and every far field that k_step_batch has.
+template <typename T, bool EMIT, int LOADMODE, int COLL, int FAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL_MOVING, FAR>())))
+void k_wallvel_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
+                     const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                     StepModel<T, COLL, WALL_MOVING, FAR> a)
+{
+    step_member<T, EMIT, LOADMODE, COLL, WALL_MOVING, FAR>(fs, fd, macro, mask, tiles, tiles_per_col, g, ms, params, a);
 }
 
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
@@ -603,7 +644,7 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
     if (threadIdx.x == 0) { mz[m] = s; tickets[m * kTicketStride] = 0; }
 }
 
-// The body of k_mex_batch, k_mex_ibb_batch and k_mex_half_batch.
+// The body of k_mex_batch, k_mex_ibb_batch, k_mex_wallvel_batch and k_mex_half_batch.
 // Momentum exchange of every member in one launch: grid (ceil(W / kLoadsWaves), B), one wave per (member, column), W the widest
 // member's window.  Definition (include/wt_polar.h): directions e_k, k = 1..8, as d2q9.hpp / html:238-248; cell (i, j) covers
 // [i, i+1) x [j, j+1).  After step n the current lattice holds, in every interior fluid cell x (not solid, 1 <= i <= NX-2,
@@ -736,7 +777,28 @@ struct LinkInterp {
     }
 };
 
-// The three kernels of the momentum exchange: one body (mex_member), each a kernel of its own name and code object, so that a batch runs
+// The moving-wall link (include/wt_polar.h "Wall velocity"): LinkInterp with b from the moving-wall overload of wall_incoming and the link's
+// wall-normal velocity, read from wu (laid out like wq, ustride elements between members) on the lanes that own the link.  With +0 in every
+// entry it is LinkInterp's.
+template <typename T>
+struct LinkMoving {
+    const T *__restrict__ wq;
+    long qstride;
+    const T *__restrict__ wu;
+    long ustride;
+    __device__ __forceinline__ void operator()(const T *__restrict__ fc, const uint8_t *__restrict__ mk, const Geom &g, long m, long coloff, int j,
+                                               int k, double &t, double &q) const
+    {
+        const long back = j - ey_of(k) - (long)ex_of(k) * g.pitch;      // x - e_k, from column i
+        const long e = coloff + (k - 1) * g.plane + j;
+        const T qk = wq[m * qstride + e], un = wu[m * ustride + e], fa = fc[k * g.plane + j];
+        const T fb = wall_incoming<T>(qk, fa, fc + k * g.plane + back, mk[back] != 0, fc + opp_of(k) * g.plane + j, link_weight<T>(k), un);
+        t = (double)fa + (double)fb;
+        q = (double)qk;
+    }
+};
+
+// The four kernels of the momentum exchange: one body (mex_member), each a kernel of its own name and code object, so that a batch runs
 // the one its storage and wall rule select (launch_mex) and no other.  ms.lat counts the lattice's elements: T, or halves.
 template <typename T>
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
@@ -756,6 +818,17 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__r
                                                    long long *__restrict__ links, const T *__restrict__ wq, long qstride)
 {
     mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkInterp<T>{wq, qstride});
+}
+
+template <typename T>
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_wallvel_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
+                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
+                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
+                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
+                                                   long long *__restrict__ links, const T *__restrict__ wq, long qstride,
+                                                   const T *__restrict__ wu, long ustride)
+{
+    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkMoving<T>{wq, qstride, wu, ustride});
 }
 
 __global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_half_batch(const half_t *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
@@ -961,7 +1034,7 @@ extern "C" int wtp_destroy(wtp_batch *b)
     if (!b) return WT_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->v_member, b->v_str, b->v_forces, b->v_log, b->v_clip, b->partials, b->tickets, b->stage,
+    void *bufs[] = {b->f[0], b->f[1], b->macro, b->mask, b->tiles, b->params, b->les_c, b->wq, b->wu, b->wind_v, b->trt_lam, b->zero_v, b->prof, b->v_member, b->v_str, b->v_forces, b->v_log, b->v_clip, b->partials, b->tickets, b->stage,
                     b->l_ref, b->l_col, b->l_tickets, b->s_rho, b->s_cnt, b->x_win, b->x_ref, b->x_col, b->x_tickets, b->m_sums, b->m_cnt,
                     b->pb_off, b->pb_w, b->pb_sums, b->pb_cnt, b->pb_row};
     for (void *p : bufs) if (p) (void)hipFree(p);
@@ -1051,7 +1124,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
 
 extern "C" const char *wtp_last_error(void) { return g_err; }
 
-extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile, device-side far-field vortex, probe points)"; }
+extern "C" const char *wtp_version(void) { return "libwtpolar 0.4 (gfx950, batched D2Q9 members, column-major SoA, surface loads, momentum exchange, mean fields, Smagorinsky subgrid viscosity, interpolated bounce-back, inclined free stream, half-precision population storage, state upload and restart, two-relaxation-time collision, prescribed far-field profile, device-side far-field vortex, probe points, wall velocity)"; }
 
 extern "C" int wtp_sync(wtp_batch *b)
 {
@@ -1129,6 +1202,14 @@ static int reset_wall_q(wtp_batch *b, int first, int count)
     return WT_OK;
 }
 
+// The wall velocities of members [first, first+count) back to +0 (walls at rest), in stream order.  Nothing to do while they are not held.
+static int reset_wall_u(wtp_batch *b, int first, int count)
+{
+    if (!b->wu) return WT_OK;
+    HIP_TRY(hipMemsetAsync((char *)b->wu + (size_t)first * b->q_stride * b->esz, 0, (size_t)count * b->q_stride * b->esz, b->st));
+    return WT_OK;
+}
+
 // Zero the probe sums and the sample counts of members [first, first+count), in stream order.  The points are kept.
 static int zero_probe_sums(wtp_batch *b, int first, int count)
 {
@@ -1165,6 +1246,7 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
         mex_window(b, first + k, m01.data());
         WT_TRY(clear_sums(b, first + k, 1));                    // the member's surface cells moved; a mean across two bodies means nothing
         WT_TRY(reset_wall_q(b, first + k, 1));                  // a wall distance belongs to a mask
+        WT_TRY(reset_wall_u(b, first + k, 1));                  // ... and so does a wall velocity
         HIP_TRY(hipMemcpy(b->stage, m01.data(), n, hipMemcpyHostToDevice));
         uint8_t *mm = b->mask + (long)(first + k) * b->ms.mask;
         dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
@@ -1360,6 +1442,11 @@ static int launch_mex(wtp_batch *b, int row)
         hipLaunchKernelGGL(k_mex_half_batch, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), (const uint8_t *)b->mask, b->g,
                            b->ms, (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
                            t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row));
+    else if (b->wallvel)
+        hipLaunchKernelGGL(k_mex_wallvel_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
+                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
+                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), (const T *)b->wq, b->q_stride,
+                           (const T *)b->wu, b->q_stride);
     else if (b->ibb)
         hipLaunchKernelGGL(k_mex_ibb_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
                            (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
@@ -1421,9 +1508,9 @@ template <typename Launch>
 static void with_step_variant(const wtp_batch *b, bool emit, Launch launch)
 {
     const int coll = b->trt ? (b->les ? COLLIDE_TRT_LES : COLLIDE_TRT) : (b->les ? COLLIDE_LES : COLLIDE_BGK);
-    const int wall = b->ibb ? WALL_INTERP : WALL_HALFWAY;
+    const int wall = b->wallvel ? WALL_MOVING : (b->ibb ? WALL_INTERP : WALL_HALFWAY);
     const int far = b->profile ? FAR_PROFILE : (b->wind || b->trt ? FAR_INCLINED : FAR_AXIAL);
-    with_constant<2>(emit, [&](auto EMIT) { with_constant<4>(coll, [&](auto COLL) { with_constant<2>(wall, [&](auto WALL) {
+    with_constant<2>(emit, [&](auto EMIT) { with_constant<4>(coll, [&](auto COLL) { with_constant<3>(wall, [&](auto WALL) {
         with_constant<3>(far, [&](auto FAR) {
             if constexpr (!coll_is_trt(COLL) || FAR != FAR_AXIAL) launch(EMIT, COLL, WALL, FAR);
         }); }); }); });
@@ -1436,7 +1523,8 @@ static StepModel<T, COLL, WALL, FAR> step_model(const wtp_batch *b, int rev)
 {
     StepModel<T, COLL, WALL, FAR> a;
     if constexpr (coll_has_les(COLL)) a.cles = (const T *)b->les_c;
-    if constexpr (WALL == WALL_INTERP) { a.wq = (const T *)b->wq; a.qstride = b->q_stride; }
+    if constexpr (wall_has_links(WALL)) { a.wq = (const T *)b->wq; a.qstride = b->q_stride; }
+    if constexpr (WALL == WALL_MOVING) { a.wu = (const T *)b->wu; a.ustride = b->q_stride; }
     if constexpr (FAR == FAR_INCLINED) a.vwind = (const T *)(b->wind ? b->wind_v : b->zero_v);
     if constexpr (coll_is_trt(COLL)) a.lam = (const T *)b->trt_lam;
     if constexpr (FAR == FAR_PROFILE) { a.prof = (const T *)b->prof; a.pstride = b->p_stride; a.nxp = b->p_nxp; }
@@ -1504,9 +1592,14 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
     const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)b->members), block(256);
     return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
         with_step_variant(b, emit, [&](auto EMIT, auto COLL, auto WALL, auto FAR) {
-            hipLaunchKernelGGL((k_step_batch<T, EMIT != 0, WT_LOADMODE, COLL, WALL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
-                               fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
-                               b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
+            if constexpr (WALL == WALL_MOVING)
+                hipLaunchKernelGGL((k_wallvel_batch<T, EMIT != 0, WT_LOADMODE, COLL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
+                                   fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
+                                   b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
+            else
+                hipLaunchKernelGGL((k_step_batch<T, EMIT != 0, WT_LOADMODE, COLL, WALL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
+                                   fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
+                                   b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
         });
     });
 }
@@ -1890,7 +1983,7 @@ extern "C" int wtp_enable_ibb(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
     if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "interpolated bounce-back is not available in a half batch");
-    if (!on) { b->ibb = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
+    if (!on) { b->ibb = false; b->wallvel = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
     HIP_TRY(hipSetDevice(b->device));
     if (!b->wq) {
         const long stride = member_stride((size_t)8 * b->g.plane * b->esz, b->esz);
@@ -1944,6 +2037,70 @@ extern "C" int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q)
         return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
     if (!b->wq) return fail(WT_ERR_STATE, "interpolated bounce-back has never been enabled (wtp_enable_ibb)");
     return b->dtype == WT_F32 ? set_wall_q_impl<float>(b, first, count, (const float *)q) : set_wall_q_impl<double>(b, first, count, (const double *)q);
+}
+
+// ------------------------------------------------------------------------------------------
+// wall velocity
+// ------------------------------------------------------------------------------------------
+extern "C" int wtp_enable_wall_velocity(wtp_batch *b, int on)
+{
+    WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a wall velocity is not available in a half batch");
+    if (!on) { b->wallvel = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
+    if (!b->ibb) return fail(WT_ERR_STATE, "interpolated bounce-back is not enabled (wtp_enable_ibb)");
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->wu) {
+        const size_t bytes = (size_t)b->members * b->q_stride * b->esz;       // the wall distances' layout and stride
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();             // (the batch goes on with walls at rest: later launches must not see this error)
+            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the wall velocities (%zu bytes) could not be allocated: %s", bytes,
+                        hipGetErrorString(e));
+        }
+        b->wu = p;
+        WT_TRY(reset_wall_u(b, 0, b->members));
+    }
+    b->wallvel = true;
+    return WT_OK;
+}
+
+template <typename T>
+static int set_wall_velocity_impl(wtp_batch *b, int first, int count, const T *un)
+{
+    const size_t n = (size_t)b->nx * b->ny;
+    for (size_t e = 0; e < (size_t)count * 8 * n; e++)
+        if (!(un[e] >= T(-0.5) && un[e] <= T(0.5)))       // (false for a NaN)
+            return fail(WT_ERR_ARG, "wall velocity %zu of member %d is not in [-0.5, 0.5]", e % (8 * n), first + (int)(e / (8 * n)));
+    HIP_TRY(hipSetDevice(b->device));
+    WT_TRY(ensure_stage(b, 8 * n * sizeof(T)));
+    const Geom &g = b->g;
+    for (int k = 0; k < count; k++) {
+        HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old velocities
+        HIP_TRY(hipMemcpy(b->stage, un + (size_t)k * 8 * n, 8 * n * sizeof(T), hipMemcpyHostToDevice));
+        T *dst = reinterpret_cast<T *>(b->wu) + (long)(first + k) * b->q_stride;
+        dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
+        for (int p = 0; p < 8; p++) {
+            // [NY][NX] rows -> column i at row i + 1 of the padded plane (pad columns and rows past NY keep +0; nothing reads them)
+            hipLaunchKernelGGL(k_rows_to_cols<T>, grd, blk, 0, b->st, reinterpret_cast<const T *>(b->stage) + (size_t)p * n,
+                               dst + p * g.plane + g.pitch, 0, b->nx, b->ny, g.pitch, (long)b->nx);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(b->st));
+    return WT_OK;
+}
+
+extern "C" int wtp_set_wall_velocity(wtp_batch *b, int first, int count, const void *un)
+{
+    WT_TRY(check_batch(b));
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a wall velocity is not available in a half batch");
+    if (!un) return fail(WT_ERR_ARG, "un is null");
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    if (!b->wu) return fail(WT_ERR_STATE, "wall velocity has never been enabled (wtp_enable_wall_velocity)");
+    return b->dtype == WT_F32 ? set_wall_velocity_impl<float>(b, first, count, (const float *)un)
+                              : set_wall_velocity_impl<double>(b, first, count, (const double *)un);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -157,7 +157,8 @@ __device__ __forceinline__ Vec<T> shift_from_above(const Vec<T> &r, const T *p, 
 // COLL: the collision of interior fluid cells, COLLIDE_BGK, COLLIDE_LES with the constant `cles` (collide_les, d2q9.hpp), or COLLIDE_TRT /
 // COLLIDE_TRT_LES with the magic number `lam` (collide_trt); the two-relaxation-time kernels never come with FAR_AXIAL.
 // WALL: the wall rule of interior fluid cells, WALL_HALFWAY or WALL_INTERP with the wall distances `wq`, eight planes laid out like
-// population planes 1..8, pad column included (wall_incoming, d2q9.hpp).  Only TILE_GENERAL tiles can own a link: no other path reads them.
+// population planes 1..8, pad column included (wall_incoming, d2q9.hpp), or WALL_MOVING with the wall-normal velocities `wu` on top, laid
+// out like `wq`.  Only TILE_GENERAL tiles can own a link: no other path reads them.
 // FAR: what a far-field cell holds, FAR_AXIAL (feq(1, U0, 0)), FAR_INCLINED with the cross-flow `V0` (feq(1, U0, V0)) or FAR_PROFILE with
 // the member's tables `prof` (feq(rho, ux, uy) of the cell's entry); the three places that form the far field take it: site_general,
 // the top and bottom rows of a TILE_FAST tile, and TILE_INLET.  With FAR_PROFILE a TILE_FAST tile collides all its rows and then, on the
@@ -169,7 +170,8 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
                                           const uint8_t *__restrict__ mask, const uint8_t *__restrict__ tiles,
                                           int tiles_per_col, const Geom &g, int i_begin, T tau, T U0, long tile_local, int lane,
                                           int stride = 0, int st_lo = 0, int st_hi = 0, T cles = T(0.0), const T *__restrict__ wq = nullptr,
-                                          T V0 = T(0.0), T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>())
+                                          T V0 = T(0.0), T lam = T(0.0), const FarProfile<T> &prof = FarProfile<T>(),
+                                          const T *__restrict__ wu = nullptr)
 {
     constexpr int N = VecOf<T>::N;
     constexpr int TJ = 64 * N;
@@ -191,7 +193,9 @@ __device__ __forceinline__ void step_tile(const T *__restrict__ fs, T *__restric
         for (int v = 0; v < N; v++) {
             const int j = row0 + v * 64 + lane;
             if (j < g.ny && (!WIN || (j >= st_lo && j < st_hi))) {
-                if constexpr (FAR == FAR_PROFILE)
+                if constexpr (WALL == WALL_MOVING)
+                    site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, wq + g.pitch, V0, lam, prof, wu + g.pitch);
+                else if constexpr (FAR == FAR_PROFILE)
                     site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0, lam, prof);
                 else if constexpr (FAR == FAR_INCLINED)
                     site_general<T, COLL, WALL, FAR>(s, d, macro, m, g, i, j, tau, U0, EMIT, cles, WALL == WALL_INTERP ? wq + g.pitch : wq, V0, lam);

@@ -266,3 +266,68 @@ def surface_stations(geom: Geometry, nx: int, ny: int, y_half: Optional[float] =
     return {"x": 0.5 * (X[:-1] + X[1:]), "y": 0.5 * (Y[:-1] + Y[1:]), "nrm_x": nrm_x, "nrm_y": nrm_y, "tan_x": sign * ux, "tan_y": sign * uy,
             "upper": first if ccw else ~first, "x_over_c": 0.5 * (bx[:-1] + bx[1:]), "lattice": (int(nx), int(ny)),
             "chord_cells": nx / (DX1 - DX0)}
+
+
+def _links(solid: np.ndarray):
+    """(k, jj, ii) for every direction k = 0..7 (direction k + 1 of _LINK_DIRS): the interior fluid cells (1 <= i <= NX-2, 1 <= j <= NY-2,
+    not solid) whose neighbour (i, j) + e_k is solid, the links of interpolated bounce-back."""
+    ny, nx = solid.shape
+    interior = np.zeros_like(solid)
+    interior[1:ny - 1, 1:nx - 1] = True
+    for k, (ex, ey) in enumerate(_LINK_DIRS):
+        nb = np.zeros_like(solid)
+        nb[1:ny - 1, 1:nx - 1] = solid[1 + ey:ny - 1 + ey, 1 + ex:nx - 1 + ex]
+        jj, ii = np.nonzero(interior & ~solid & nb)
+        yield k, jj, ii
+
+
+def _check_link_planes(mask, q):
+    solid = np.asarray(mask) != 0
+    q = np.asarray(q, np.float64)
+    if solid.ndim != 2 or q.shape != (8,) + solid.shape:
+        raise ValueError(f"mask must be [NY][NX] and q [8][NY][NX], got {solid.shape} and {q.shape}")
+    return solid, q
+
+
+def rigid_wall_velocity(mask: np.ndarray, q: np.ndarray, ux: float, uy: float, omega: float, px: float, py: float) -> np.ndarray:
+    """The wall-normal velocities (include/wt_polar.h "Wall velocity") of a body that moves rigidly: float64 [8][NY][NX], plane k - 1 for
+    direction k.  The body translates with (ux, uy) and turns counter-clockwise with `omega` (radians per step) about (px, py), all in
+    lattice units, so that the wall's velocity at a point r is u_w = (ux - omega (r_y - py), uy + omega (r_x - px)).  On every link of
+    `mask` (wall_distances' links) with wall distance q = q[k - 1][j][i],
+        un_k = e_kx (ux - omega (r_y - py)) + e_ky (uy + omega (r_x - px))   at the wall point   r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky);
+    every other entry is +0.  The mask itself does not move: a spinning circle, or a small-amplitude motion applied by transpiration."""
+    solid, q = _check_link_planes(mask, q)
+    un = np.zeros(q.shape)
+    for k, jj, ii in _links(solid):
+        ex, ey = _LINK_DIRS[k]
+        rx, ry = ii + 0.5 + q[k, jj, ii] * ex, jj + 0.5 + q[k, jj, ii] * ey
+        un[k, jj, ii] = ex * (ux - omega * (ry - py)) + ey * (uy + omega * (rx - px))
+    return un
+
+
+def slot_wall_velocity(geom: Geometry, mask: np.ndarray, q: np.ndarray, nx: int, ny: int, surface: str, x0: float, x1: float, vn: float,
+                       y_half: Optional[float] = None) -> np.ndarray:
+    """The wall-normal velocities of blowing (vn > 0, into the fluid) or suction (vn < 0) through a slot of the surface: float64
+    [8][NY][NX], plane k - 1 for direction k.  A link of `mask` belongs to the slot when the station of surface_stations(geom, nx, ny)
+    nearest to its wall point r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky) lies on `surface` ("upper" or "lower") with x0 <= x_over_c <= x1;
+    there u_w = vn (nrm_x, nrm_y) of that station, in lattice units, and un_k = e_k . u_w.  Every other entry is +0.  Stations of
+    zero-length panels are not candidates."""
+    if surface not in ("upper", "lower"):
+        raise ValueError(f'surface must be "upper" or "lower", got {surface!r}')
+    solid, q = _check_link_planes(mask, q)
+    if solid.shape != (ny, nx):
+        raise ValueError(f"mask must have shape [NY][NX] = {(ny, nx)}, got {solid.shape}")
+    st = surface_stations(geom, nx, ny, y_half)
+    ok = np.isfinite(st["nrm_x"]) & np.isfinite(st["nrm_y"])
+    sx, sy, nrx, nry = st["x"][ok], st["y"][ok], st["nrm_x"][ok], st["nrm_y"][ok]
+    side = st["upper"][ok] if surface == "upper" else ~st["upper"][ok]
+    slot = side & (st["x_over_c"][ok] >= x0) & (st["x_over_c"][ok] <= x1)
+    un = np.zeros(q.shape)
+    for k, jj, ii in _links(solid):
+        if jj.size == 0:
+            continue
+        ex, ey = _LINK_DIRS[k]
+        rx, ry = ii + 0.5 + q[k, jj, ii] * ex, jj + 0.5 + q[k, jj, ii] * ey
+        near = np.argmin((rx[:, None] - sx[None, :]) ** 2 + (ry[:, None] - sy[None, :]) ** 2, axis=1)
+        un[k, jj, ii] = np.where(slot[near], vn * (ex * nrx[near] + ey * nry[near]), 0.0)
+    return un

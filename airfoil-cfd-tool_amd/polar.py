@@ -30,6 +30,9 @@ With probe points (``PolarEngine.enable_probes`` / ``set_probes``) the device sa
 and keeps their running sums; ``run_polar(boundary_layer=True)`` puts rakes along the wall normals (``geometry.surface_stations``,
 :func:`boundary_layer_points`) and attaches the boundary-layer read-out of every angle (:func:`boundary_layer`: x/c, Ue, delta*, theta, Cf,
 H per surface and where the skin friction changes sign).
+With a wall velocity (``PolarEngine.enable_wall_velocity`` / ``set_wall_velocity``, on top of interpolated bounce-back) the walls of a
+member move or transpire: a velocity per wall link (``geometry.rigid_wall_velocity``, ``geometry.slot_wall_velocity``) enters the
+reflected population as Ladd's moving-wall term; ``run_polar(walls="interpolated", slot={...})`` blows or sucks through a slot.
 
 * :class:`PolarEngine` — ctypes binding of libwtpolar.so (loaded lazily, after torch, like ``_capi.load_library``).
 * :func:`run_polar` — masks from ``geometry.build_geometry`` per angle, warm-up, sampled run, statistics per angle.
@@ -68,6 +71,7 @@ EXPORTS = (
     "wtp_enable_far_profile", "wtp_set_far_profile", "wtp_read_far_profile",
     "wtp_enable_far_vortex", "wtp_set_far_vortex", "wtp_far_vortex", "wtp_far_vortex_update", "wtp_far_vortex_log",
     "wtp_enable_probes", "wtp_set_probes", "wtp_probe_sums", "wtp_probe_sample",
+    "wtp_enable_wall_velocity", "wtp_set_wall_velocity",
 )
 
 WTP_STORE_NATIVE, WTP_STORE_HALF = 0, 1
@@ -152,6 +156,8 @@ def load_polar_library(path: str = POLAR_LIB_PATH, optional: Sequence[str] = ())
         "wtp_set_probes": ([B, c_int, c_int, dp, dp], c_int),
         "wtp_probe_sums": ([B, c_int, ip, dp, dp, dp], c_int),
         "wtp_probe_sample": ([B, c_int, dp, dp, dp], c_int),
+        "wtp_enable_wall_velocity": ([B, c_int], c_int),
+        "wtp_set_wall_velocity": ([B, c_int, c_int, c_void_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         if name in optional and path != POLAR_LIB_PATH and not hasattr(lib, name):
@@ -228,6 +234,7 @@ class PolarEngine:
         self.mean_enabled = False
         self.les_enabled = False
         self.interpolated_walls = False
+        self.wall_velocity_enabled = False
         self._wind = False
         self._trt = False
         self._far_profile = False
@@ -379,6 +386,8 @@ class PolarEngine:
         enable_les, independent of the read-outs."""
         _check(self._lib.wtp_enable_ibb(self._b, 1 if on else 0))
         self.interpolated_walls = bool(on)
+        if not on:
+            self.wall_velocity_enabled = False
 
     def set_wall_distances(self, q, first: int = 0) -> None:
         """q [count][8][NY][NX] (or one [8][NY][NX]) for members first .. first+count-1, each value in (0, 1], plane k - 1 for
@@ -390,6 +399,28 @@ class PolarEngine:
         if a.ndim != 4 or a.shape[1:] != (8, self.ny, self.nx):
             raise ValueError(f"wall distances must have shape [count][8][NY][NX] = [count]{(8, self.ny, self.nx)}, got {a.shape}")
         _check(self._lib.wtp_set_wall_q(self._b, int(first), int(a.shape[0]), a.ctypes.data_as(c_void_p)))
+
+    def enable_wall_velocity(self, on: bool = True) -> None:
+        """Let the walls move or transpire from the next step on (wt_polar.h "Wall velocity"): every link carries Ladd's moving-wall term
+        with its wall-normal velocity, +0 (a wall at rest) until set_wall_velocity gives others.  Needs enable_interpolated_walls;
+        on=False switches back to the interpolating kernels and keeps the velocities, and so does enable_interpolated_walls(False).
+        The flow state, the history, every running sum and every other setting are kept."""
+        if not hasattr(self._lib, "wtp_enable_wall_velocity"):
+            raise WTError(-1, "this libwtpolar.so has no wall velocity (wtp_enable_wall_velocity)")
+        _check(self._lib.wtp_enable_wall_velocity(self._b, 1 if on else 0))
+        self.wall_velocity_enabled = bool(on)
+
+    def set_wall_velocity(self, un, first: int = 0) -> None:
+        """un [count][8][NY][NX] (or one [8][NY][NX]) for members first .. first+count-1: e_k . u_w at the wall point of every link,
+        plane k - 1 for direction k (geometry.rigid_wall_velocity, geometry.slot_wall_velocity), each finite with |un| <= 0.5;
+        converted to the batch's dtype.  After set_masks, which resets the velocities of the members it touches to +0, and after
+        set_wall_distances.  The values hold until they are replaced; steps already enqueued see the old ones."""
+        a = np.ascontiguousarray(un, dtype=self.dtype)
+        if a.ndim == 3:
+            a = a[None]
+        if a.ndim != 4 or a.shape[1:] != (8, self.ny, self.nx):
+            raise ValueError(f"wall velocities must have shape [count][8][NY][NX] = [count]{(8, self.ny, self.nx)}, got {a.shape}")
+        _check(self._lib.wtp_set_wall_velocity(self._b, int(first), int(a.shape[0]), a.ctypes.data_as(c_void_p)))
 
     def enable_wind(self, v0) -> None:
         """Incline the free stream (wt_polar.h): v0 is the cross-flow of the far field, one value or [B], each finite with
@@ -736,8 +767,12 @@ class PolarResult:
     # (lattice axes), strength, source [U][B] float64 and clipped [U][B] bool (None for "uniform").  Init-only too.
     far_field: InitVar[str] = "uniform"
     vortex_history: InitVar[Optional[Dict[str, np.ndarray]]] = None
+    # The blowing or suction slot of the sweep: {"surface", "x0", "x1", "vn", "links"}, links [B] the links that carry a velocity per angle
+    # (None without a slot).  Init-only too.
+    slot: InitVar[Optional[Dict[str, object]]] = None
 
-    def __post_init__(self, walls, frame, storage, state, collision, magic, far_field="uniform", vortex_history=None):
+    def __post_init__(self, walls, frame, storage, state, collision, magic, far_field="uniform", vortex_history=None, slot=None):
+        self.slot = slot
         self.far_field = far_field
         self.vortex_history = vortex_history
         self.walls = walls
@@ -1054,7 +1089,7 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
               boundary_layer: bool = False, bl_height: float = BL_HEIGHT_DEFAULT, bl_spacing: float = BL_SPACING_DEFAULT, start: Optional[Dict[str, object]] = None, keep_state: bool = False,
               collision: str = "bgk", magic: float = MAGIC_DEFAULT,
               far_field: str = "uniform", vortex_every: int = 96, vortex_relax: float = 0.3, vortex_after: Optional[int] = None,
-              vortex_on: str = "host", storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
+              vortex_on: str = "host", slot: Optional[Dict[str, object]] = None, storage: str = "native", walls: str = "staircase", frame: str = "body", les: Optional[float] = None) -> PolarResult:
     """One batch member per angle: warm-up of `warmup_steps` (default two flow-throughs, 2*nx/u0 steps), then `samples` force
     samples every `sample_every` steps (12: the page's cadence, 4 steps per frame and forces every 3rd frame).  User `coords`
     win over `shape`, as in WindTunnel; tau from `re` when given (tau_from_reynolds), else `tau` or the page's 0.58.
@@ -1143,7 +1178,17 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     polar_rows then carries x_sep_upper and x_sep_lower.  Off by default: the sweep then launches the kernels, and returns the rows,
     results and bits, it always did; with it on every other value is the same bits.  bl_height and bl_spacing must be finite and
     positive, with the rake reaching at least one cell (bl_height * chord_cells(nx) >= max(bl_spacing, 1)) and at most WTP_MAX_PROBES
-    points per angle, else ValueError before an engine is created."""
+    points per angle, else ValueError before an engine is created.
+    `slot`: blowing or suction through a slot of the surface, a dict with the keys "surface" ("upper" or "lower"), "x0" and "x1" (the
+    slot's extent in x/c of the body's own axes, x0 <= x1) and "vn" (the normal velocity in units of `u0`; positive blows into the
+    fluid).  Every wall link whose wall point lies nearest to a panel of the slot carries Ladd's moving-wall term with u_w = vn u0 times
+    the panel's outward normal (geometry.slot_wall_velocity, PolarEngine.enable_wall_velocity, wt_polar.h "Wall velocity"), from the
+    first warm-up step on.  It needs walls="interpolated" and is refused with storage="half"; it works in both frames: with
+    frame="body" each angle's own panels are used, with frame="wind" one set serves every angle.  PolarResult.slot records what ran,
+    and how many links of each angle carry a velocity.  The momentum exchange (`total_forces`) uses the moving-wall link term, without
+    a Galilean-invariant correction.  None, the default, launches the kernels, and returns the bits, that the sweep always did.  A slot
+    with other keys, an unknown surface, x0 > x1, a vn that is not finite or |vn| u0 sqrt(2) > 0.5 raises ValueError before an engine
+    is created."""
     alphas = [float(a) for a in alphas]
     if not alphas:
         raise ValueError("no angles")
@@ -1160,6 +1205,20 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
     if frame not in FRAMES:
         raise ValueError(f"frame must be one of {FRAMES}, got {frame!r}")
     _check_storage(storage, dtype, walls)
+    if slot is not None:
+        if storage == "half":
+            raise ValueError('storage="half" does not combine with a slot')
+        if walls != "interpolated":
+            raise ValueError('a slot needs walls="interpolated"')
+        if not isinstance(slot, dict) or set(slot) != {"surface", "x0", "x1", "vn"}:
+            raise ValueError(f'slot must be a dict with the keys "surface", "x0", "x1" and "vn", got {slot!r}')
+        if slot["surface"] not in ("upper", "lower"):
+            raise ValueError(f'slot["surface"] must be "upper" or "lower", got {slot["surface"]!r}')
+        slot = {"surface": slot["surface"], "x0": float(slot["x0"]), "x1": float(slot["x1"]), "vn": float(slot["vn"])}
+        if not (math.isfinite(slot["x0"]) and math.isfinite(slot["x1"]) and slot["x0"] <= slot["x1"]):
+            raise ValueError(f'slot needs finite x0 <= x1, got {slot["x0"]!r} and {slot["x1"]!r}')
+        if not (math.isfinite(slot["vn"]) and abs(slot["vn"]) * abs(float(u0)) * math.sqrt(2.0) <= 0.5):
+            raise ValueError(f'slot["vn"] must be finite with |vn| u0 sqrt(2) <= 0.5, got {slot["vn"]!r}')
     if not isinstance(collision, str) or collision not in COLLISIONS:
         raise ValueError(f"collision must be one of {COLLISIONS}, got {collision!r}")
     trt = collision == "trt"
@@ -1221,7 +1280,16 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             eng.enable_interpolated_walls()
             q = geo.wall_distances(geoms[0].xp, geoms[0].yp, geoms[0].mask, nx, ny) if wind else None
             for m, g in enumerate(geoms):                      # (one member at a time: eight float64 planes each on the host)
-                eng.set_wall_distances(q if wind else geo.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
+                qm = q if wind else geo.wall_distances(g.xp, g.yp, g.mask, nx, ny)
+                eng.set_wall_distances(qm, first=m)
+                if slot is not None and (m == 0 or not wind):  # (one set of velocities serves every angle of the wind frame)
+                    un = geo.slot_wall_velocity(g, g.mask, qm, nx, ny, slot["surface"], slot["x0"], slot["x1"], slot["vn"] * u0)
+                if slot is not None:
+                    if m == 0:
+                        eng.enable_wall_velocity()
+                        slot["links"] = []
+                    eng.set_wall_velocity(un, first=m)
+                    slot["links"].append(int(np.count_nonzero(un)))
         if wind:
             eng.enable_wind(vy0)
         eng.init_equilibrium(ux0)
@@ -1331,7 +1399,8 @@ def run_polar(alphas: Sequence[float], *, coords=None, shape: str = "naca2412", 
             p.boundary_layer = _boundary_layer_of(stations[m], means, rakes[m][2], u0, tau)
     return PolarResult(points=points, nx=nx, ny=ny, tau=tau, u0=u0, warmup_steps=warmup_steps, sample_every=int(sample_every), les=les,
                        walls=walls, frame=frame, storage=storage, state=state, collision=collision, magic=magic if trt else None,
-                       far_field=far_field, vortex_history=vortex_history if vortex else None)
+                       far_field=far_field, vortex_history=vortex_history if vortex else None,
+                       slot=dict(slot, links=np.array(slot["links"], np.int64)) if slot is not None else None)
 
 
 def sweep_alphas(start: float, end: float, step: float) -> List[float]:

@@ -529,6 +529,54 @@ WTP_API int wtp_enable_probes(wtp_batch *b, int npoints);
 WTP_API int wtp_set_probes(wtp_batch *b, int first, int count, const double *x, const double *y);
 WTP_API int wtp_probe_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy);
 WTP_API int wtp_probe_sample(wtp_batch *b, int member, double *rho, double *ux, double *uy);
+/*
+ * Wall velocity: moving and transpiring walls.  Every wall above is at rest.  With a velocity per wall link a member can blow or suck
+ * through a slot of its surface, spin (the raster mask of a circle does not change as it turns, so the wall velocity is the only thing
+ * that turns), or move rigidly at small amplitude by transpiration: the pitch or plunge velocity applied on the fixed mask.  It is a
+ * third wall rule, defined only on top of interpolated bounce-back (half-way walls are the case q = 0.5), per batch and opt-in.
+ * Definition:
+ *   The wall-normal velocity.  Member m holds, per cell (i, j) and direction k = 1..8, the number un_k(i, j) = e_k . u_w, where u_w is
+ *   the wall's velocity at the link's wall point r = (i + 0.5 + q e_kx, j + 0.5 + q e_ky), in lattice units.  The caller forms it in
+ *   double; it is stored in the batch's dtype T after one rounding.  The values are stored as eight planes per member, laid out
+ *   exactly like the wall distances, and are read only on links: an interior fluid cell x whose neighbour x + e_k is solid, exactly
+ *   as in interpolated bounce-back.
+ *   The incoming population.  a, g, h, two and inv are those of "Interpolated bounce-back" above.  c_k = T(6) * w_k is one
+ *   multiplication in T, w_k being the step's weight as feq_all forms it (T(1)/T(9) for k = 1..4, T(1)/T(36) for k = 5..8).  The wall
+ *   density is taken as 1.  Every operation rounds once in T.  Evaluation is left to right as written, with no contraction.
+ *     d = c_k * un
+ *     q <  0.5:  fin = (two*a + (1 - two)*g) - d      if x - e_k is not solid, else fin = a - d
+ *     q >= 0.5:  fin = (inv*a + (1 - inv)*h) - inv*d
+ *   fin is the incoming population fin[opp(k)] of x.  This is Ladd's moving-wall term,
+ *   f_opp(k)(x, t+1) = f*_k(x, t) - 2 w_k rho_w (e_k . u_w) / c_s^2, carried through Bouzidi's linear interpolation.  At q = 0.5 both
+ *   branches give a - d.  With un = +0 everywhere d = +0, and every population has the bits of a batch with interpolated walls alone.
+ *   Nothing else in the step changes: the gather, the moments, the stability net, every collision, the stored (rho, ux, uy), and the
+ *   solid, outlet and far-field branches all stay as they are.
+ *   The momentum exchange needs no new definition: b is the value the next step will reflect, computed from the current lattice by
+ *   the formulas above.  The link's term stays ((double)a + (double)b) e_k and the link's point stays the wall point.  links is
+ *   unchanged.
+ * The device holds the velocities as the wall distances are held: 8 * (NX + 2) * pitch * sizeof(T) bytes per member more.
+ * Out of scope: half storage, because interpolated walls have none.  Out of scope: a wall density other than 1.  Out of scope: a
+ * Galilean-invariant correction of the momentum exchange.  Out of scope: masks that move, meaning no refill of uncovered cells.
+ * Out of scope: a per-step schedule on the device, because values hold until the caller replaces them.  Out of scope: libwindtunnel
+ * handles; a member with a moving wall has no libwindtunnel twin.
+ *
+ * wtp_enable_wall_velocity with on != 0 switches the model on.  It needs interpolated bounce-back switched on (wtp_enable_ibb), else
+ * WT_ERR_STATE; on a half batch it returns WT_ERR_STATE and leaves the batch working.  On first use it allocates the planes of all
+ * members, filled with +0; where the allocation fails it returns WT_ERR_OOM, holds nothing, and the batch goes on as before.  From the
+ * next wtp_step the moving-wall kernels run.  on == 0 switches back to the interpolating kernels, with the same bits as in a batch that
+ * never enabled it; the planes are kept.  wtp_enable_ibb(b, 0) switches the wall velocity off too.  The flow state, the step count, the
+ * history, every running sum and every other wtp_enable_* setting are kept.  It combines with every collision and every far field.  A
+ * batch that never calls it launches the kernels it always launched.
+ */
+WTP_API int wtp_enable_wall_velocity(wtp_batch *b, int on);
+/* The wall-normal velocities of members [first, first+count): un is [count][8][NY][NX] of the batch's dtype, plane k - 1 holds
+ * direction k.  Every value must be finite with |un| <= 0.5 (this bound holds 0.35 sqrt(2), the stability net's speed along a
+ * diagonal).  A null pointer, a bad value or a member range outside the batch is WT_ERR_ARG before any device call, and the batch is
+ * left as it was.  WT_ERR_STATE while the model has never been enabled.  Entries that are no link are never read.  Steps already
+ * enqueued see the old values, later steps the new ones; the values hold until the caller replaces them.  wtp_set_masks resets the
+ * velocities of the members it touches to +0, as it resets their distances to 0.5: upload the velocities after the masks and the
+ * distances. */
+WTP_API int wtp_set_wall_velocity(wtp_batch *b, int first, int count, const void *un);
 /* Wait for the enqueued work. */
 WTP_API int wtp_sync(wtp_batch *b);
 

@@ -38,6 +38,13 @@ The batched step with interpolated bounce-back (wtp_enable_ibb, every member wit
 the WALL_INTERP instantiation of k_step_batch with the collision the other switches select.  The line has the shape of --les's; no
 sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
 
+    python tools/polar_bench.py --wall-velocity [--les CS] [--wind] [--trt MAGIC] [--profile] [--repeats 5] [the options of the first form]
+
+The batched step with moving walls (wtp_enable_wall_velocity on top of --ibb's wall distances; every member's body turns rigidly about the
+lattice's centre, so that every link carries a term): k_wallvel_batch with the collision and the far field the other switches select.  The
+line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --wall-velocity, --lib may name a build from
+before the entry points existed.
+
     python tools/polar_bench.py --wind [--les CS] [--ibb] [--repeats 5] [the options of the first form]
 
 The batched step with an inclined free stream (wtp_enable_wind): the FAR_INCLINED instantiation of the kernel the other switches select.
@@ -107,6 +114,17 @@ def _interpolated_walls(eng, nx, ny, b):
         eng.set_wall_distances(pkg.geometry.wall_distances(g.xp, g.yp, g.mask, nx, ny), first=m)
 
 
+def _wall_velocity(eng, nx, ny, b):
+    """Switch the wall velocity on and turn every member's body rigidly about the lattice's centre, so that every link carries a term:
+    a rim speed of 0.02 at half a chord's distance."""
+    eng.enable_wall_velocity()
+    omega = 0.02 / (0.5 * pkg.windtunnel.chord_cells(nx))
+    for m, a in enumerate(_alphas(b)):
+        g = pkg.geometry.build_geometry(nx, ny, float(a), None, "naca2412")
+        q = pkg.geometry.wall_distances(g.xp, g.yp, g.mask, nx, ny)
+        eng.set_wall_velocity(pkg.geometry.rigid_wall_velocity(g.mask, q, 0.0, 0.0, omega, 0.5 * nx, 0.5 * ny), first=m)
+
+
 def _cross_flow(b):
     return U0 * np.sin(np.radians(_alphas(b)))
 
@@ -121,11 +139,13 @@ def _far_profile(eng, nx, ny, b, wind):
     eng.set_far_profile(*(np.stack([t[k] for t in tabs]) for k in range(3)))
 
 
-def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native", trt=None, profile=False):
+def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False, wind=False, storage="native", trt=None, profile=False,
+                wall_velocity=False):
     """Seconds of `steps` steps after a warm-up, one figure per repeat; les: the Smagorinsky constant of every member (None: BGK);
     ibb: interpolated bounce-back with every airfoil's wall distances; wind: an inclined free stream, U0 sin(alpha) across;
     trt: the magic number of the two-relaxation-time collision in every member (None: one relaxation time); profile: a prescribed
-    far-field profile, the free stream plus a weak vortex."""
+    far-field profile, the free stream plus a weak vortex; wall_velocity: interpolated bounce-back with a rigid rotation of every body
+    as its wall velocity."""
     out = []
     with pkg.PolarEngine(nx, ny, b, storage=storage) as eng:
         eng.set_masks(masks)
@@ -134,8 +154,10 @@ def bench_batch(nx, ny, b, steps, warmup, masks, les=None, repeats=1, ibb=False,
         eng.init_equilibrium(U0)
         if les is not None:
             eng.enable_les(les)
-        if ibb:
+        if ibb or wall_velocity:
             _interpolated_walls(eng, nx, ny, b)
+        if wall_velocity:
+            _wall_velocity(eng, nx, ny, b)
         if trt is not None:
             eng.enable_trt(trt)
         if profile:
@@ -333,6 +355,7 @@ def main():
     ap.add_argument("--probes", action="store_true", help="the sampled step with and without probe points (run_polar's default boundary-layer rake)")
     ap.add_argument("--les", type=float, default=None, metavar="CS", help="step with the Smagorinsky subgrid viscosity, constant CS in every member")
     ap.add_argument("--ibb", action="store_true", help="step with interpolated bounce-back, every member with its airfoil's wall distances")
+    ap.add_argument("--wall-velocity", action="store_true", help="step with interpolated bounce-back and a wall velocity, a rigid rotation of every member's body")
     ap.add_argument("--wind", action="store_true", help="step with an inclined free stream, U0 sin(alpha) across in every member")
     ap.add_argument("--storage", default="native", choices=pkg.polar.STORAGES, help="how the batch stores its populations (half: binary16 deviations)")
     ap.add_argument("--trt", type=float, default=None, metavar="MAGIC", help="step with the two-relaxation-time collision, magic number MAGIC in every member")
@@ -350,10 +373,13 @@ def main():
                   ("wtp_read_far_profile", True), ("wtp_enable_far_vortex", True), ("wtp_set_far_vortex", True), ("wtp_far_vortex", True),
                   ("wtp_far_vortex_update", True), ("wtp_far_vortex_log", True),
                   # the probe points: only --probes calls them, and with an older build it times the variant without them alone
-                  ("wtp_enable_probes", True), ("wtp_set_probes", True), ("wtp_probe_sums", True), ("wtp_probe_sample", True))
+                  ("wtp_enable_probes", True), ("wtp_set_probes", True), ("wtp_probe_sums", True), ("wtp_probe_sample", True),
+                  ("wtp_enable_wall_velocity", not a.wall_velocity), ("wtp_set_wall_velocity", not a.wall_velocity))
         pkg.polar.load_polar_library(a.lib, optional=tuple(name for name, free in unused if free))
-    if a.storage == "half" and a.ibb:
-        ap.error("--storage half does not combine with --ibb")
+    if a.storage == "half" and (a.ibb or a.wall_velocity):
+        ap.error("--storage half does not combine with --ibb or --wall-velocity")
+    if a.wall_velocity and not plain:
+        ap.error("--wall-velocity times the plain stepping form only")
     half = a.storage == "half"
     if half and a.profile:
         ap.error("--storage half does not combine with --profile")
@@ -375,7 +401,7 @@ def main():
             masks = _masks(nx, ny, b)
             sites = nx * ny
             ts = bench_batch(nx, ny, b, a.steps, a.warmup, masks, les=a.les, repeats=a.repeats, ibb=a.ibb, wind=a.wind, storage=a.storage, trt=a.trt,
-                             profile=a.profile)
+                             profile=a.profile, wall_velocity=a.wall_velocity)
             t = float(np.median(ts))
             us = t / a.steps * 1e6
             ms_per_s = b * a.steps / t
@@ -383,7 +409,7 @@ def main():
             line = {"tool": "polar_bench", "nx": nx, "ny": ny, "dtype": "float32", "members": b, "steps": a.steps,
                     "us_per_batched_step": round(us, 2), "member_steps_per_s": round(ms_per_s, 1),
                     "glups": round(ms_per_s * sites / 1e9, 3), "hbm_fraction_of_8TBps": round(bytes_step / (t / a.steps) / PEAK_BPS, 4)}
-            if a.les is not None or a.ibb or a.wind or half or a.trt is not None or a.profile or a.repeats > 1:
+            if a.les is not None or a.ibb or a.wall_velocity or a.wind or half or a.trt is not None or a.profile or a.repeats > 1:
                 line["les"] = a.les
                 if a.trt is not None:
                     line["trt"] = a.trt
@@ -393,12 +419,14 @@ def main():
                     line["storage"] = "half"
                 if a.ibb:
                     line["ibb"] = True
+                if a.wall_velocity:
+                    line["wall_velocity"] = True
                 if a.wind:
                     line["wind"] = True
                 if a.profile:
                     line["profile"] = True
                 line["us_per_batched_step_repeats"] = [round(v / a.steps * 1e6, 2) for v in ts]
-            if not a.no_sequential and a.les is None and not a.ibb and not a.wind and not half and a.trt is None and not a.profile:
+            if not a.no_sequential and a.les is None and not a.ibb and not a.wall_velocity and not a.wind and not half and a.trt is None and not a.profile:
                 ts = bench_sequential(nx, ny, b, a.steps, a.warmup, masks)
                 line["sequential_us_per_member_step"] = round(ts / (b * a.steps) * 1e6, 2)
                 line["sequential_member_steps_per_s"] = round(b * a.steps / ts, 1)
