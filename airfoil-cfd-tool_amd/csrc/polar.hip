@@ -25,8 +25,7 @@
 // ux, uy at the member's own points, bilinearly between cell centres, and adds the three values of each point to its running sums, one
 // owner lane per point.  A batch that never enables them launches the kernels it always launched.
 //
-// The step has one tiled kernel body, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR> (and k_wallvel_batch around the same body):
-// step_tile (step_fast.hpp) of the wave's tile with
+// The step has one tiled kernel, k_step_batch<T, EMIT, LOADMODE, COLL, WALL, FAR>: step_tile (step_fast.hpp) of the wave's tile with
 // the collision, the wall rule and the far field as template arguments, and the values each of them reads per member in one argument
 // whose members exist only in the variants that read them (StepModel).  The models below select among its instantiations.
 //
@@ -36,14 +35,13 @@
 //
 // Interpolated bounce-back (wtp_enable_ibb) is another wall rule: while it is on, wtp_step launches k_step_batch with WALL_INTERP, the same
 // step_tile with wall_incoming at the links of its general tiles and eight planes of wall distances per member, with either
-// collision, and a sample's momentum exchange comes from k_mex_ibb_batch, the same reduction (mex_member) with the interpolated link
+// collision, and a sample's momentum exchange comes from k_mex_batch with LinkInterp, the same reduction with the interpolated link
 // rule.  A batch that has it off launches the kernels it always launched, with the arguments they always had.
 //
-// Wall velocity (wtp_enable_wall_velocity) is a third wall rule on top of the second: while it is on, wtp_step launches k_wallvel_batch,
-// k_step_batch's body (step_member) with WALL_MOVING under a name of its own: the same step_tile with the moving-wall overload of
-// wall_incoming at the links of its general tiles and eight more planes per
+// Wall velocity (wtp_enable_wall_velocity) is a third wall rule on top of the second: while it is on, wtp_step launches k_step_batch with
+// WALL_MOVING: the same step_tile with the moving-wall overload of wall_incoming at the links of its general tiles and eight more planes per
 // member, the wall-normal velocities, read on the lanes that read a wall distance, with every collision and every far field, and a sample's
-// momentum exchange comes from k_mex_wallvel_batch (mex_member with LinkMoving).  Native storage only.  A batch that has it off launches the
+// momentum exchange comes from k_mex_batch with LinkMoving.  Native storage only.  A batch that has it off launches the
 // kernels it always launched, with the arguments they always had.
 //
 // The inclined free stream (wtp_enable_wind) is another far field: while it is on, wtp_step launches k_step_batch with FAR_INCLINED, the same
@@ -54,7 +52,7 @@
 // Half-precision population storage (wtp_create_stored with WTP_STORE_HALF) is another storage of an fp32 batch: its lattices hold
 // each population as the binary16 deviation from its lattice weight, in wt_create's layout with 2-byte elements.  wtp_step launches
 // k_step_half_batch<EMIT, COLL, FAR>, site_general with half_t as its stored element: a Load in front of its branches and a Store behind,
-// fp32 between, with every collision and either far field, and k_step_batch's model argument; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_half_batch.  The other
+// fp32 between, with every collision and either far field, and k_step_batch's model argument; wtp_init_equilibrium fills by k_fill_half and a sample's momentum exchange comes from k_mex_batch with half_t elements.  The other
 // read-outs read the fp32 macroscopic planes and run unchanged.  A native batch launches the kernels it always launched, with the
 // arguments they always had.
 //
@@ -83,7 +81,7 @@
 //
 // Every variant above is an instantiation of its own, so a batch runs the code object its switches select and no other.  What the
 // variants share is source text: one site (site_general, kernels.hpp, for every storage), one tiled step kernel and one half step kernel
-// with one selection and one launch on the host (with_step_variant, step_model), one momentum-exchange body (mex_member, with a link
+// with one selection and one launch on the host (with_step_variant, step_model), one momentum-exchange kernel (k_mex_batch, with a link
 // rule per wall rule), one stepping loop on the host.
 #include <hip/hip_runtime.h>
 
@@ -122,6 +120,33 @@ struct MemberStrides { long lat, macro, mask, tiles; };
 
 static long member_stride(size_t bytes, size_t esz) { return (long)(((bytes + 4095) / 4096 * 4096 + 17408) / esz); }
 
+// A feature's optional device buffers, all or none: every *p of `want` that is still null is allocated with its bytes (one that is held,
+// from an earlier call, is kept), and only when all of them succeeded are they assigned.  On a failure what was got is freed, nothing is
+// assigned and HIP's last error is cleared, so that the batch goes on as it was and later launches do not see the error.
+struct DevBuf { void **p; size_t bytes; };
+
+static int alloc_all(const std::vector<DevBuf> &want, const char *what)
+{
+    std::vector<void *> got;
+    size_t total = 0;
+    hipError_t e = hipSuccess;
+    for (const DevBuf &w : want) if (!*w.p) total += w.bytes;
+    for (const DevBuf &w : want) {
+        void *p = nullptr;
+        if (*w.p) continue;
+        if ((e = hipMalloc(&p, w.bytes)) != hipSuccess) break;
+        got.push_back(p);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void *p : got) (void)hipFree(p);
+        return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the %s (%zu bytes) could not be allocated: %s", what, total, hipGetErrorString(e));
+    }
+    size_t k = 0;
+    for (const DevBuf &w : want) if (!*w.p) *w.p = got[k++];
+    return WT_OK;
+}
+
 // The samples of one read-out: up to four columns of 8-byte values (double or long long), [cap + 1][B] each, one value per
 // member and row.  Rows [0, cap) are the history, in step order; row cap is the scratch row of the on-demand call.
 struct SampleTable {
@@ -131,11 +156,12 @@ struct SampleTable {
 
     size_t bytes() const { return rows * members * 8; }
     bool allocated() const { return ncols > 0 && col[ncols - 1]; }
-    int alloc(int n, size_t cap, size_t B)       // (columns already held are kept)
+    int alloc(int n, size_t cap, size_t B, const char *what)      // (columns already held are kept)
     {
         ncols = n; rows = cap + 1; members = B;
-        for (int c = 0; c < n; c++) if (!col[c]) HIP_TRY(hipMalloc(&col[c], bytes()));
-        return WT_OK;
+        std::vector<DevBuf> want;
+        for (int c = 0; c < n; c++) want.push_back({&col[c], bytes()});
+        return alloc_all(want, what);
     }
     // "Never sampled" in every row of the columns of `mask` (bit c: column c): bytes 0xFF, a NaN as a double, -1 as a long long.
     int fill(unsigned mask, hipStream_t st)
@@ -343,12 +369,11 @@ constexpr int step_waves()
 // The two-relaxation-time collisions are not built with FAR_AXIAL: a batch without wtp_enable_wind hands them an array of zeros as
 // vwind, and V0 = 0 gives the axial far field's bits because ex*U0 + ey*0 and U0*U0 + 0*0 are exact, so that the collision costs
 // eight instantiations per dtype and not sixteen.
-// step_member is the body; it has two entry points, so that the kernels of the half-way and the interpolating rule keep their name and
-// their number: k_step_batch (WALL_HALFWAY, WALL_INTERP) and k_wallvel_batch (WALL_MOVING, "wall velocity" below).
 template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL, int FAR>
-__device__ __forceinline__ void step_member(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
-                                            const uint8_t *__restrict__ tiles, int tiles_per_col, const Geom &g, const MemberStrides &ms,
-                                            const T *__restrict__ params, const StepModel<T, COLL, WALL, FAR> &a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL, FAR>())))
+void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
+                  const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
+                  StepModel<T, COLL, WALL, FAR> a)
 {
     const int lane = threadIdx.x & 63;
     const MemberTile w(g, tiles_per_col, a.rev);
@@ -367,27 +392,6 @@ __device__ __forceinline__ void step_member(const T *__restrict__ fs, T *__restr
     step_tile<T, EMIT, LOADMODE, false, COLL, WALL, FAR>(fs + m * ms.lat, fd + m * ms.lat, macro + m * ms.macro, mask + m * ms.mask,
                                                          tiles + m * ms.tiles, tiles_per_col, g, 0, tau, U0, w.tile(), lane, 0, 0, 0,
                                                          c, q, V0, magic, fp, u);
-}
-
-template <typename T, bool EMIT, int LOADMODE, int COLL, int WALL, int FAR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL, FAR>())))
-void k_step_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
-                  const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                  StepModel<T, COLL, WALL, FAR> a)
-{
-    static_assert(WALL != WALL_MOVING, "the moving-wall variants are k_wallvel_batch's");
-    step_member<T, EMIT, LOADMODE, COLL, WALL, FAR>(fs, fd, macro, mask, tiles, tiles_per_col, g, ms, params, a);
-}
-
-// One step of every member with moving walls (include/wt_polar.h "Wall velocity"): step_member with WALL_MOVING, k_step_batch's arguments,
-// grid and waves; every collision and every far field that k_step_batch has.
-template <typename T, bool EMIT, int LOADMODE, int COLL, int FAR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(step_waves<T, EMIT, COLL, WALL_MOVING, FAR>())))
-void k_wallvel_batch(const T *__restrict__ fs, T *__restrict__ fd, T *__restrict__ macro, const uint8_t *__restrict__ mask,
-                     const uint8_t *__restrict__ tiles, int tiles_per_col, Geom g, MemberStrides ms, const T *__restrict__ params,
-                     StepModel<T, COLL, WALL_MOVING, FAR> a)
-{
-    step_member<T, EMIT, LOADMODE, COLL, WALL_MOVING, FAR>(fs, fd, macro, mask, tiles, tiles_per_col, g, ms, params, a);
 }
 
 // The start state of a member with an inclined free stream: k_fill_equilibrium's walk and stores (both lattices, pad columns included), with
@@ -644,7 +648,6 @@ __global__ __launch_bounds__(kLoadsWaves * 64) void k_loads_batch(const T *__res
     if (threadIdx.x == 0) { mz[m] = s; tickets[m * kTicketStride] = 0; }
 }
 
-// The body of k_mex_batch, k_mex_ibb_batch, k_mex_wallvel_batch and k_mex_half_batch.
 // Momentum exchange of every member in one launch: grid (ceil(W / kLoadsWaves), B), one wave per (member, column), W the widest
 // member's window.  Definition (include/wt_polar.h): directions e_k, k = 1..8, as d2q9.hpp / html:238-248; cell (i, j) covers
 // [i, i+1) x [j, j+1).  After step n the current lattice holds, in every interior fluid cell x (not solid, 1 <= i <= NX-2,
@@ -798,46 +801,17 @@ struct LinkMoving {
     }
 };
 
-// The four kernels of the momentum exchange: one body (mex_member), each a kernel of its own name and code object, so that a batch runs
-// the one its storage and wall rule select (launch_mex) and no other.  ms.lat counts the lattice's elements: T, or halves.
-template <typename T>
-__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
+// The kernel of the momentum exchange: mex_member with the link rule as an argument, by value, with what the rule reads per member.  Every
+// (E, Link) is a kernel of its own, so that a batch runs the one its storage and wall rule select (launch_mex) and no other.  ms.lat counts
+// the lattice's elements: T, or halves.
+template <typename E, typename Link>
+__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_batch(const E *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
                                                    MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
                                                    MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
                                                    double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
-                                                   long long *__restrict__ links)
+                                                   long long *__restrict__ links, Link link)
 {
-    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkHalfway<T>{});
-}
-
-template <typename T>
-__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_ibb_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
-                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
-                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
-                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
-                                                   long long *__restrict__ links, const T *__restrict__ wq, long qstride)
-{
-    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkInterp<T>{wq, qstride});
-}
-
-template <typename T>
-__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_wallvel_batch(const T *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
-                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
-                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
-                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
-                                                   long long *__restrict__ links, const T *__restrict__ wq, long qstride,
-                                                   const T *__restrict__ wu, long ustride)
-{
-    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkMoving<T>{wq, qstride, wu, ustride});
-}
-
-__global__ __launch_bounds__(kLoadsWaves * 64) void k_mex_half_batch(const half_t *__restrict__ f, const uint8_t *__restrict__ mask, Geom g,
-                                                   MemberStrides ms, const double *__restrict__ ref, const int32_t *__restrict__ win,
-                                                   MexPartial *__restrict__ col, unsigned int *__restrict__ tickets,
-                                                   double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ mz,
-                                                   long long *__restrict__ links)
-{
-    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, LinkHalfway<float>{});
+    mex_member(f, mask, g, ms, ref, win, col, tickets, fx, fy, mz, links, link);
 }
 
 // Every element of p[0, n) set to v: the wall distances' default.
@@ -1020,11 +994,38 @@ static int check_batch(const wtp_batch *b)
     return WT_OK;
 }
 
+static int check_members(const wtp_batch *b, int first, int count)
+{
+    if (first < 0 || count < 1 || first + count > b->members)
+        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    return WT_OK;
+}
+
+static int check_member(const wtp_batch *b, int member)
+{
+    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    return WT_OK;
+}
+
+// What a half batch does not have: `what` names it.
+static int check_native(const wtp_batch *b, const char *what)
+{
+    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "%s is not available in a half batch", what);
+    return WT_OK;
+}
+
+// f(T()) with T the batch's dtype, float or double: the run-time dtype handed on as a type (decltype of f's argument).
+template <typename F>
+static auto with_dtype(const wtp_batch *b, F f)
+{
+    return b->dtype == WT_F32 ? f(float()) : f(double());
+}
+
 static int ensure_stage(wtp_batch *b, size_t bytes)
 {
     if (b->stage_bytes >= bytes) return WT_OK;
     if (b->stage) { HIP_TRY(hipFree(b->stage)); b->stage = nullptr; b->stage_bytes = 0; }
-    HIP_TRY(hipMalloc(&b->stage, bytes));
+    WT_TRY(alloc_all({{&b->stage, bytes}}, "stage"));
     b->stage_bytes = bytes;
     return WT_OK;
 }
@@ -1109,7 +1110,7 @@ extern "C" int wtp_create_stored(int nx, int ny, int dtype, int storage, int mem
     CREATE_TRY(hipMalloc(&b->params, B * 2 * b->esz));
     CREATE_TRY(hipMalloc((void **)&b->partials, B * b->nb * sizeof(ForcePartial)));
     CREATE_TRY(hipMalloc((void **)&b->tickets, B * sizeof(unsigned int)));
-    if (int rc = b->forces.alloc(4, (size_t)history_cap, B)) return cleanup(rc);
+    if (int rc = b->forces.alloc(4, (size_t)history_cap, B, "force history")) return cleanup(rc);
     CREATE_TRY(hipMemsetAsync(b->f[0], 0, lat_bytes, b->st));
     CREATE_TRY(hipMemsetAsync(b->f[1], 0, lat_bytes, b->st));
     CREATE_TRY(hipMemsetAsync(b->macro, 0, macro_bytes, b->st));
@@ -1194,10 +1195,10 @@ static int reset_wall_q(wtp_batch *b, int first, int count)
     if (!b->wq) return WT_OK;
     const long n = (long)count * b->q_stride;
     const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
-    if (b->dtype == WT_F32)
-        hipLaunchKernelGGL(k_fill_value<float>, dim3(blocks), dim3(256), 0, b->st, (float *)b->wq + (long)first * b->q_stride, n, 0.5f);
-    else
-        hipLaunchKernelGGL(k_fill_value<double>, dim3(blocks), dim3(256), 0, b->st, (double *)b->wq + (long)first * b->q_stride, n, 0.5);
+    with_dtype(b, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_fill_value<T>, dim3(blocks), dim3(256), 0, b->st, (T *)b->wq + (long)first * b->q_stride, n, T(0.5));
+    });
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -1231,8 +1232,7 @@ extern "C" int wtp_set_masks(wtp_batch *b, int first, int count, const uint8_t *
 {
     WT_TRY(check_batch(b));
     if (!masks) return fail(WT_ERR_ARG, "masks is null");
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     HIP_TRY(hipSetDevice(b->device));
     const Geom &g = b->g;
     const size_t n = (size_t)b->nx * b->ny;
@@ -1325,7 +1325,7 @@ extern "C" int wtp_init_equilibrium(wtp_batch *b, const double *u0)
         if (!std::isfinite(u0[m])) return fail(WT_ERR_ARG, "u0[%d] must be finite", m);
     HIP_TRY(hipSetDevice(b->device));
     if (b->storage == WTP_STORE_HALF) WT_TRY(init_half(b, u0));
-    else WT_TRY(b->dtype == WT_F32 ? init_impl<float>(b, u0) : init_impl<double>(b, u0));
+    else WT_TRY(with_dtype(b, [&](auto t) { return init_impl<decltype(t)>(b, u0); }));
     b->cur = 0;
     b->inited = true;
     b->macro_stale = false;
@@ -1438,23 +1438,17 @@ static int launch_mex(wtp_batch *b, int row)
     for (int m = 0; m < b->members; m++) widest = std::max(widest, (int)b->mex_win[2 * (size_t)m + 1]);
     const SampleTable &t = b->xforces;
     const dim3 grid((unsigned)((widest + kLoadsWaves - 1) / kLoadsWaves), (unsigned)b->members), block(kLoadsWaves * 64);
-    if (b->storage == WTP_STORE_HALF)
-        hipLaunchKernelGGL(k_mex_half_batch, grid, block, 0, b->st, (const half_t *)fptr<half_t>(b, b->cur, 0), (const uint8_t *)b->mask, b->g,
+    const auto launch = [&](auto e, auto link) {             // e: the lattice's stored element
+        using E = decltype(e);
+        hipLaunchKernelGGL((k_mex_batch<E, decltype(link)>), grid, block, 0, b->st, (const E *)fptr<E>(b, b->cur, 0), (const uint8_t *)b->mask, b->g,
                            b->ms, (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
-                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row));
-    else if (b->wallvel)
-        hipLaunchKernelGGL(k_mex_wallvel_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
-                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
-                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), (const T *)b->wq, b->q_stride,
-                           (const T *)b->wu, b->q_stride);
-    else if (b->ibb)
-        hipLaunchKernelGGL(k_mex_ibb_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
-                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
-                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), (const T *)b->wq, b->q_stride);
-    else
-        hipLaunchKernelGGL(k_mex_batch<T>, grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0), (const uint8_t *)b->mask, b->g, b->ms,
-                           (const double *)b->x_ref, (const int32_t *)b->x_win, b->x_col, b->x_tickets, t.at<double>(0, row),
-                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row));
+                           t.at<double>(1, row), t.at<double>(2, row), t.at<long long>(3, row), link);
+    };
+    const T *wq = (const T *)b->wq, *wu = (const T *)b->wu;
+    if (b->storage == WTP_STORE_HALF) launch(half_t(), LinkHalfway<float>{});
+    else if (b->wallvel) launch(T(), LinkMoving<T>{wq, b->q_stride, wu, b->q_stride});
+    else if (b->ibb) launch(T(), LinkInterp<T>{wq, b->q_stride});
+    else launch(T(), LinkHalfway<T>{});
     HIP_TRY(hipGetLastError());
     return WT_OK;
 }
@@ -1592,14 +1586,9 @@ static int step_impl(wtp_batch *b, int nsteps, int sample_every)
     const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)b->members), block(256);
     return step_loop<T>(b, nsteps, sample_every, [&](bool emit, int rev) {
         with_step_variant(b, emit, [&](auto EMIT, auto COLL, auto WALL, auto FAR) {
-            if constexpr (WALL == WALL_MOVING)
-                hipLaunchKernelGGL((k_wallvel_batch<T, EMIT != 0, WT_LOADMODE, COLL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
-                                   fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
-                                   b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
-            else
-                hipLaunchKernelGGL((k_step_batch<T, EMIT != 0, WT_LOADMODE, COLL, WALL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
-                                   fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
-                                   b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
+            hipLaunchKernelGGL((k_step_batch<T, EMIT != 0, WT_LOADMODE, COLL, WALL, FAR>), grid, block, 0, b->st, (const T *)fptr<T>(b, b->cur, 0),
+                               fptr<T>(b, 1 - b->cur, 0), macro_of<T>(b, 0), (const uint8_t *)b->mask, (const uint8_t *)b->tiles, b->tiles_per_col,
+                               b->g, b->ms, (const T *)b->params, step_model<T, COLL, WALL, FAR>(b, rev));
         });
     });
 }
@@ -1616,7 +1605,7 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
     }
     if (b->trt)                                  // tm = 0.5 + lam / (tp - 0.5) needs tp > 0.5 in the batch's dtype
         for (int m = 0; m < b->members; m++)
-            if (!(b->dtype == WT_F32 ? (float)tau[m] > 0.5f : tau[m] > 0.5))
+            if (!with_dtype(b, [&](auto t) { return (decltype(t))tau[m] > decltype(t)(0.5); }))
                 return fail(WT_ERR_ARG, "tau[%d] must be above 0.5 in the batch's dtype while the two-relaxation-time collision is on", m);
     WT_TRY(check_ready(b));
     if (b->profile)
@@ -1632,13 +1621,10 @@ extern "C" int wtp_step(wtp_batch *b, int nsteps, const double *tau, const doubl
         return fail(WT_ERR_STATE, "%lld updates would overflow the far-field vortex's log (%zu of %d rows held): read it and wtp_clear_history",
                     updates, b->v_step.size(), b->v_cap);
     HIP_TRY(hipSetDevice(b->device));
-    if (b->dtype == WT_F32) {
-        WT_TRY(upload_params<float>(b, tau, u0));
-        WT_TRY(b->storage == WTP_STORE_HALF ? step_half(b, nsteps, sample_every) : step_impl<float>(b, nsteps, sample_every));
-    } else {
-        WT_TRY(upload_params<double>(b, tau, u0));
-        WT_TRY(step_impl<double>(b, nsteps, sample_every));
-    }
+    WT_TRY(with_dtype(b, [&](auto t) {
+        WT_TRY(upload_params<decltype(t)>(b, tau, u0));
+        return b->storage == WTP_STORE_HALF ? step_half(b, nsteps, sample_every) : step_impl<decltype(t)>(b, nsteps, sample_every);
+    }));
     if (nsteps > 0) b->macro_stale = false;      // the call's last step emitted
     return WT_OK;
 }
@@ -1653,7 +1639,7 @@ static int upload_per_member(wtp_batch *b, void **dev, Value value_of)
 {
     std::vector<T> v((size_t)b->members);
     for (size_t m = 0; m < v.size(); m++) v[m] = (T)value_of(m);
-    if (!*dev) HIP_TRY(hipMalloc(dev, v.size() * sizeof(T)));
+    WT_TRY(alloc_all({{dev, v.size() * sizeof(T)}}, "per-member values"));
     HIP_TRY(hipStreamSynchronize(b->st));
     HIP_TRY(hipMemcpy(*dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return WT_OK;
@@ -1667,7 +1653,7 @@ extern "C" int wtp_enable_les(wtp_batch *b, const double *cs)
         if (!std::isfinite(cs[m]) || cs[m] < 0.0 || cs[m] > 0.5) return fail(WT_ERR_ARG, "cs[%d] must be finite and in [0, 0.5]", m);
     HIP_TRY(hipSetDevice(b->device));
     const auto c = [&](size_t m) { return 18.0 * std::sqrt(2.0) * cs[m] * cs[m]; };      // c = 18 sqrt(2) Cs^2: formed left to right in double
-    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->les_c, c) : upload_per_member<double>(b, &b->les_c, c));
+    WT_TRY(with_dtype(b, [&](auto t) { return upload_per_member<decltype(t)>(b, &b->les_c, c); }));
     b->les = true;
     return WT_OK;
 }
@@ -1683,11 +1669,11 @@ extern "C" int wtp_enable_trt(wtp_batch *b, const double *magic)
         if (!std::isfinite(magic[m]) || !(magic[m] > 0.0) || magic[m] > 1.0) return fail(WT_ERR_ARG, "magic[%d] must be finite and in (0, 1]", m);
     HIP_TRY(hipSetDevice(b->device));
     if (!b->zero_v) {
-        HIP_TRY(hipMalloc(&b->zero_v, (size_t)b->members * b->esz));
+        WT_TRY(alloc_all({{&b->zero_v, (size_t)b->members * b->esz}}, "per-member values"));
         HIP_TRY(hipMemsetAsync(b->zero_v, 0, (size_t)b->members * b->esz, b->st));      // (+0 in either dtype)
     }
     const auto lam = [&](size_t m) { return magic[m]; };
-    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->trt_lam, lam) : upload_per_member<double>(b, &b->trt_lam, lam));
+    WT_TRY(with_dtype(b, [&](auto t) { return upload_per_member<decltype(t)>(b, &b->trt_lam, lam); }));
     b->trt = true;
     return WT_OK;
 }
@@ -1703,7 +1689,7 @@ extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
         if (!std::isfinite(v0[m]) || std::fabs(v0[m]) > 0.35) return fail(WT_ERR_ARG, "v0[%d] must be finite and in [-0.35, 0.35]", m);
     HIP_TRY(hipSetDevice(b->device));
     const auto v = [&](size_t m) { return v0[m]; };
-    WT_TRY(b->dtype == WT_F32 ? upload_per_member<float>(b, &b->wind_v, v) : upload_per_member<double>(b, &b->wind_v, v));
+    WT_TRY(with_dtype(b, [&](auto t) { return upload_per_member<decltype(t)>(b, &b->wind_v, v); }));
     b->wind_host.assign(v0, v0 + b->members);
     b->wind = true;
     return WT_OK;
@@ -1715,24 +1701,17 @@ extern "C" int wtp_enable_wind(wtp_batch *b, const double *v0)
 extern "C" int wtp_enable_far_profile(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    WT_TRY(check_native(b, "a prescribed far-field profile"));
     if (!on) { b->profile = false; b->vortex = false; return WT_OK; }       // (steps already enqueued were launched with the model on: stream order)
     HIP_TRY(hipSetDevice(b->device));
     if (!b->prof) {
         const int nxp = (b->nx + 63) / 64 * 64;
         const long stride = member_stride((size_t)far_profile_elems(b->g.pitch, nxp) * b->esz, b->esz);
         const size_t bytes = (size_t)b->members * stride * b->esz;
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();             // (the batch goes on with its uniform far field: later launches must not see this error)
-            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the far-field tables (%zu bytes) could not be allocated: %s", bytes,
-                        hipGetErrorString(e));
-        }
-        e = hipMemsetAsync(p, 0, bytes, b->st);  // (the entries no cell reads, rows past NY and columns past NX, hold +0)
-        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
-        b->prof = p; b->p_stride = stride; b->p_nxp = nxp;
+        WT_TRY(alloc_all({{&b->prof, bytes}}, "far-field tables"));       // (on a failure the batch goes on with its uniform far field)
+        b->p_stride = stride; b->p_nxp = nxp;
         b->prof_set.assign((size_t)b->members, 0);
+        HIP_TRY(hipMemsetAsync(b->prof, 0, bytes, b->st));      // (the entries no cell reads, rows past NY and columns past NX, hold +0)
     }
     b->profile = true;
     return WT_OK;
@@ -1780,14 +1759,15 @@ static int set_far_profile_impl(wtp_batch *b, int first, int count, const T *lef
 extern "C" int wtp_set_far_profile(wtp_batch *b, int first, int count, const void *left, const void *bottom, const void *top)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    WT_TRY(check_native(b, "a prescribed far-field profile"));
     if (!left || !bottom || !top) return fail(WT_ERR_ARG, "left, bottom or top is null");
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     if (!b->prof) return fail(WT_ERR_STATE, "the far-field profile has never been enabled (wtp_enable_far_profile)");
     if (b->vortex) return fail(WT_ERR_STATE, "the device-side far-field vortex owns the tables (wtp_enable_far_vortex with every = 0 hands them back)");
-    return b->dtype == WT_F32 ? set_far_profile_impl<float>(b, first, count, (const float *)left, (const float *)bottom, (const float *)top)
-                              : set_far_profile_impl<double>(b, first, count, (const double *)left, (const double *)bottom, (const double *)top);
+    return with_dtype(b, [&](auto t) {
+        using T = decltype(t);
+        return set_far_profile_impl(b, first, count, (const T *)left, (const T *)bottom, (const T *)top);
+    });
 }
 
 // The device layout of FarProfile of members [first, first + count) unpacked into wtp_set_far_profile's host layouts.
@@ -1814,13 +1794,14 @@ static int read_far_profile_impl(wtp_batch *b, int first, int count, T *left, T 
 extern "C" int wtp_read_far_profile(wtp_batch *b, int first, int count, void *left, void *bottom, void *top)
 {
     WT_TRY(check_batch(b));
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     if (!b->prof) return fail(WT_ERR_STATE, "the far-field profile has never been enabled (wtp_enable_far_profile)");
     for (int m = first; m < first + count; m++)
         if (!b->prof_set[(size_t)m]) return fail(WT_ERR_STATE, "member %d has no far-field profile (wtp_set_far_profile)", m);
-    return b->dtype == WT_F32 ? read_far_profile_impl<float>(b, first, count, (float *)left, (float *)bottom, (float *)top)
-                              : read_far_profile_impl<double>(b, first, count, (double *)left, (double *)bottom, (double *)top);
+    return with_dtype(b, [&](auto t) {
+        using T = decltype(t);
+        return read_far_profile_impl(b, first, count, (T *)left, (T *)bottom, (T *)top);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1835,7 +1816,7 @@ static bool far_vortex_pair_ok(double s, double q, double bound)
 // All tables from the current strengths, behind whatever is enqueued.
 static int far_vortex_tables(wtp_batch *b)
 {
-    return b->dtype == WT_F32 ? launch_far_vortex<float, false>(b, 0) : launch_far_vortex<double, false>(b, 0);
+    return with_dtype(b, [&](auto t) { return launch_far_vortex<decltype(t), false>(b, 0); });
 }
 
 extern "C" int wtp_enable_far_vortex(wtp_batch *b, int every, int64_t after, double relax, double u_ref, int with_source, double xc, double yc,
@@ -1843,7 +1824,7 @@ extern "C" int wtp_enable_far_vortex(wtp_batch *b, int every, int64_t after, dou
 {
     WT_TRY(check_batch(b));
     if (every == 0) { b->vortex = false; return WT_OK; }      // (updates already enqueued were launched with the model on: stream order)
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a prescribed far-field profile is not available in a half batch");
+    WT_TRY(check_native(b, "a prescribed far-field profile"));
     if (!b->profile) return fail(WT_ERR_STATE, "the far-field profile is not enabled (wtp_enable_far_profile)");
     if (every < 0) return fail(WT_ERR_ARG, "every must be >= 0 (got %d)", every);
     if (after < 0) return fail(WT_ERR_ARG, "after must be >= 0 (got %lld)", (long long)after);
@@ -1872,26 +1853,20 @@ extern "C" int wtp_enable_far_vortex(wtp_batch *b, int every, int64_t after, dou
                 return fail(WT_ERR_ARG, "the strengths held by member %d induce more than 0.1 at the new bound %g", (int)m, bound);
     }
     // the buffers: everything of the first enable at once, a log of another size on a later one
-    void *member = b->v_member, *str = b->v_str, *forces = b->v_forces, *log = nullptr, *clip = nullptr;
+    const bool relog = !b->v_log || log_cap != b->v_cap;
+    void *member = b->v_member, *str = b->v_str, *forces = b->v_forces, *log = relog ? nullptr : b->v_log, *clip = relog ? nullptr : b->v_clip;
     const size_t rows = (size_t)std::max(log_cap, 1);
-    hipError_t e = hipSuccess;
-    if (!member && e == hipSuccess) e = hipMalloc(&member, 4 * B * sizeof(double));
-    if (!str && e == hipSuccess) e = hipMalloc(&str, 4 * B * sizeof(double));
-    if (!forces && e == hipSuccess) e = hipMalloc(&forces, 4 * B * 8);
-    if ((!b->v_log || log_cap != b->v_cap) && e == hipSuccess) {
-        e = hipMalloc(&log, 4 * rows * B * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&clip, rows * B * sizeof(int32_t));
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(b->st);      // updates already enqueued read the previous settings and write the previous log
-    if (e == hipSuccess && !b->v_str) e = hipMemcpy(str, held.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice);      // (zeros, into half 0)
-    if (e != hipSuccess) {
+    HIP_TRY(hipStreamSynchronize(b->st));        // updates already enqueued read the previous settings and write the previous log
+    WT_TRY(alloc_all({{&member, 4 * B * sizeof(double)}, {&str, 4 * B * sizeof(double)}, {&forces, 4 * B * 8},
+                      {&log, 4 * rows * B * sizeof(double)}, {&clip, rows * B * sizeof(int32_t)}}, "far-field vortex's buffers"));
+    if (hipError_t e = b->v_str ? hipSuccess : hipMemcpy(str, held.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice)) {      // (zeros, into half 0)
         (void)hipGetLastError();                 // (the batch goes on as it was: later launches must not see this error)
-        for (void *p : {b->v_member ? nullptr : member, b->v_str ? nullptr : str, b->v_forces ? nullptr : forces, log, clip}) if (p) (void)hipFree(p);
+        for (void *p : {b->v_member ? nullptr : member, str, b->v_forces ? nullptr : forces, relog ? log : nullptr, relog ? clip : nullptr}) if (p) (void)hipFree(p);
         return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the far-field vortex's buffers could not be set up: %s", hipGetErrorString(e));
     }
     if (!b->v_str) b->v_par = 0;
     b->v_member = (double *)member; b->v_str = (double *)str; b->v_forces = forces;
-    if (log) {
+    if (relog) {
         if (b->v_log) (void)hipFree(b->v_log);
         if (b->v_clip) (void)hipFree(b->v_clip);
         b->v_log = (double *)log; b->v_clip = (int32_t *)clip;
@@ -1954,7 +1929,7 @@ extern "C" int wtp_far_vortex_update(wtp_batch *b)
     if ((int)b->v_step.size() >= b->v_cap)
         return fail(WT_ERR_STATE, "the far-field vortex's log is full (%d rows): read it and wtp_clear_history", b->v_cap);
     HIP_TRY(hipSetDevice(b->device));
-    return b->dtype == WT_F32 ? far_vortex_update_now<float>(b) : far_vortex_update_now<double>(b);
+    return with_dtype(b, [&](auto t) { return far_vortex_update_now<decltype(t)>(b); });
 }
 
 extern "C" int wtp_far_vortex_log(wtp_batch *b, int first, int count, int64_t *step, double *fx, double *fy, double *strength, double *source,
@@ -1982,43 +1957,38 @@ extern "C" int wtp_far_vortex_log(wtp_batch *b, int first, int count, int64_t *s
 extern "C" int wtp_enable_ibb(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "interpolated bounce-back is not available in a half batch");
+    WT_TRY(check_native(b, "interpolated bounce-back"));
     if (!on) { b->ibb = false; b->wallvel = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
     HIP_TRY(hipSetDevice(b->device));
     if (!b->wq) {
         const long stride = member_stride((size_t)8 * b->g.plane * b->esz, b->esz);
-        const size_t bytes = (size_t)b->members * stride * b->esz;
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();             // (the batch goes on with half-way walls: later launches must not see this error)
-            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the wall distances (%zu bytes) could not be allocated: %s", bytes,
-                        hipGetErrorString(e));
-        }
-        b->wq = p; b->q_stride = stride;
+        WT_TRY(alloc_all({{&b->wq, (size_t)b->members * stride * b->esz}}, "wall distances"));      // (on a failure the batch goes on with half-way walls)
+        b->q_stride = stride;
         WT_TRY(reset_wall_q(b, 0, b->members));
     }
     b->ibb = true;
     return WT_OK;
 }
 
-template <typename T>
-static int set_wall_q_impl(wtp_batch *b, int first, int count, const T *q)
+// Eight [NY][NX] planes per member of members [first, first + count), from the host into the padded link-plane layout of `dev` (wq or wu:
+// planes laid out like population planes 1..8, members q_stride elements apart), through the stage.  Every value has to pass `ok` (false
+// for a NaN); the refusal names the value by `noun` and the interval by `bound`.
+template <typename T, typename Ok>
+static int upload_link_planes(wtp_batch *b, void *dev, int first, int count, const T *v, Ok ok, const char *noun, const char *bound)
 {
     const size_t n = (size_t)b->nx * b->ny;
     for (size_t e = 0; e < (size_t)count * 8 * n; e++)
-        if (!(q[e] > T(0.0) && q[e] <= T(1.0)))       // (false for a NaN)
-            return fail(WT_ERR_ARG, "wall distance %zu of member %d is not in (0, 1]", e % (8 * n), first + (int)(e / (8 * n)));
+        if (!ok(v[e])) return fail(WT_ERR_ARG, "%s %zu of member %d is not in %s", noun, e % (8 * n), first + (int)(e / (8 * n)), bound);
     HIP_TRY(hipSetDevice(b->device));
     WT_TRY(ensure_stage(b, 8 * n * sizeof(T)));
     const Geom &g = b->g;
     for (int k = 0; k < count; k++) {
-        HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old distances
-        HIP_TRY(hipMemcpy(b->stage, q + (size_t)k * 8 * n, 8 * n * sizeof(T), hipMemcpyHostToDevice));
-        T *dst = reinterpret_cast<T *>(b->wq) + (long)(first + k) * b->q_stride;
+        HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old values
+        HIP_TRY(hipMemcpy(b->stage, v + (size_t)k * 8 * n, 8 * n * sizeof(T), hipMemcpyHostToDevice));
+        T *dst = reinterpret_cast<T *>(dev) + (long)(first + k) * b->q_stride;
         dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
         for (int p = 0; p < 8; p++) {
-            // [NY][NX] rows -> column i at row i + 1 of the padded plane (pad columns and rows past NY keep 0.5; nothing reads them)
+            // [NY][NX] rows -> column i at row i + 1 of the padded plane (pad columns and rows past NY keep their default; nothing reads them)
             hipLaunchKernelGGL(k_rows_to_cols<T>, grd, blk, 0, b->st, reinterpret_cast<const T *>(b->stage) + (size_t)p * n,
                                dst + p * g.plane + g.pitch, 0, b->nx, b->ny, g.pitch, (long)b->nx);
             HIP_TRY(hipGetLastError());
@@ -2031,12 +2001,14 @@ static int set_wall_q_impl(wtp_batch *b, int first, int count, const T *q)
 extern "C" int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "interpolated bounce-back is not available in a half batch");
+    WT_TRY(check_native(b, "interpolated bounce-back"));
     if (!q) return fail(WT_ERR_ARG, "q is null");
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     if (!b->wq) return fail(WT_ERR_STATE, "interpolated bounce-back has never been enabled (wtp_enable_ibb)");
-    return b->dtype == WT_F32 ? set_wall_q_impl<float>(b, first, count, (const float *)q) : set_wall_q_impl<double>(b, first, count, (const double *)q);
+    return with_dtype(b, [&](auto t) {
+        using T = decltype(t);
+        return upload_link_planes(b, b->wq, first, count, (const T *)q, [](T x) { return x > T(0.0) && x <= T(1.0); }, "wall distance", "(0, 1]");
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2045,62 +2017,30 @@ extern "C" int wtp_set_wall_q(wtp_batch *b, int first, int count, const void *q)
 extern "C" int wtp_enable_wall_velocity(wtp_batch *b, int on)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a wall velocity is not available in a half batch");
+    WT_TRY(check_native(b, "a wall velocity"));
     if (!on) { b->wallvel = false; return WT_OK; }   // (steps already enqueued were launched with the model on: stream order)
     if (!b->ibb) return fail(WT_ERR_STATE, "interpolated bounce-back is not enabled (wtp_enable_ibb)");
     HIP_TRY(hipSetDevice(b->device));
     if (!b->wu) {
-        const size_t bytes = (size_t)b->members * b->q_stride * b->esz;       // the wall distances' layout and stride
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();             // (the batch goes on with walls at rest: later launches must not see this error)
-            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the wall velocities (%zu bytes) could not be allocated: %s", bytes,
-                        hipGetErrorString(e));
-        }
-        b->wu = p;
+        // the wall distances' layout and stride (on a failure the batch goes on with walls at rest)
+        WT_TRY(alloc_all({{&b->wu, (size_t)b->members * b->q_stride * b->esz}}, "wall velocities"));
         WT_TRY(reset_wall_u(b, 0, b->members));
     }
     b->wallvel = true;
     return WT_OK;
 }
 
-template <typename T>
-static int set_wall_velocity_impl(wtp_batch *b, int first, int count, const T *un)
-{
-    const size_t n = (size_t)b->nx * b->ny;
-    for (size_t e = 0; e < (size_t)count * 8 * n; e++)
-        if (!(un[e] >= T(-0.5) && un[e] <= T(0.5)))       // (false for a NaN)
-            return fail(WT_ERR_ARG, "wall velocity %zu of member %d is not in [-0.5, 0.5]", e % (8 * n), first + (int)(e / (8 * n)));
-    HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(ensure_stage(b, 8 * n * sizeof(T)));
-    const Geom &g = b->g;
-    for (int k = 0; k < count; k++) {
-        HIP_TRY(hipStreamSynchronize(b->st));        // the stage may still feed an earlier conversion; steps before this call see the old velocities
-        HIP_TRY(hipMemcpy(b->stage, un + (size_t)k * 8 * n, 8 * n * sizeof(T), hipMemcpyHostToDevice));
-        T *dst = reinterpret_cast<T *>(b->wu) + (long)(first + k) * b->q_stride;
-        dim3 blk(32, 8), grd((b->nx + 31) / 32, (b->ny + 31) / 32);
-        for (int p = 0; p < 8; p++) {
-            // [NY][NX] rows -> column i at row i + 1 of the padded plane (pad columns and rows past NY keep +0; nothing reads them)
-            hipLaunchKernelGGL(k_rows_to_cols<T>, grd, blk, 0, b->st, reinterpret_cast<const T *>(b->stage) + (size_t)p * n,
-                               dst + p * g.plane + g.pitch, 0, b->nx, b->ny, g.pitch, (long)b->nx);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(b->st));
-    return WT_OK;
-}
-
 extern "C" int wtp_set_wall_velocity(wtp_batch *b, int first, int count, const void *un)
 {
     WT_TRY(check_batch(b));
-    if (b->storage == WTP_STORE_HALF) return fail(WT_ERR_STATE, "a wall velocity is not available in a half batch");
+    WT_TRY(check_native(b, "a wall velocity"));
     if (!un) return fail(WT_ERR_ARG, "un is null");
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     if (!b->wu) return fail(WT_ERR_STATE, "wall velocity has never been enabled (wtp_enable_wall_velocity)");
-    return b->dtype == WT_F32 ? set_wall_velocity_impl<float>(b, first, count, (const float *)un)
-                              : set_wall_velocity_impl<double>(b, first, count, (const double *)un);
+    return with_dtype(b, [&](auto t) {
+        using T = decltype(t);
+        return upload_link_planes(b, b->wu, first, count, (const T *)un, [](T x) { return x >= T(-0.5) && x <= T(0.5); }, "wall velocity", "[-0.5, 0.5]");
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2148,7 +2088,7 @@ extern "C" int wtp_forces(wtp_batch *b, double *fx, double *fy, int64_t *surf, i
     WT_TRY(check_ready(b));
     WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? launch_forces<float>(b, b->cap) : launch_forces<double>(b, b->cap));     // the scratch row
+    WT_TRY(with_dtype(b, [&](auto t) { return launch_forces<decltype(t)>(b, b->cap); }));     // the scratch row
     return read_rows(b, b->forces, b->cap, 1, {fx, fy, surf, rev});
 }
 
@@ -2163,7 +2103,7 @@ static int set_ref_points(wtp_batch *b, const double *xref, const double *yref, 
     for (size_t m = 0; m < B; m++)
         if (!std::isfinite(xref[m]) || !std::isfinite(yref[m])) return fail(WT_ERR_ARG, "reference point of member %d must be finite", (int)m);
     HIP_TRY(hipSetDevice(b->device));
-    if (!*dev) HIP_TRY(hipMalloc((void **)dev, B * 2 * sizeof(double)));
+    WT_TRY(alloc_all({{(void **)dev, B * 2 * sizeof(double)}}, "reference points"));
     std::vector<double> ref(B * 2);
     for (size_t m = 0; m < B; m++) { ref[2 * m] = xref[m]; ref[2 * m + 1] = yref[m]; }
     HIP_TRY(hipStreamSynchronize(b->st));
@@ -2177,11 +2117,9 @@ extern "C" int wtp_enable_loads(wtp_batch *b, const double *xref, const double *
     if (!xref || !yref) return fail(WT_ERR_ARG, "xref or yref is null");
     WT_TRY(set_ref_points(b, xref, yref, &b->l_ref));
     const size_t B = (size_t)b->members, cols = B * b->nx;
-    if (!b->l_col) HIP_TRY(hipMalloc((void **)&b->l_col, cols * sizeof(double)));
-    if (!b->l_tickets) HIP_TRY(hipMalloc((void **)&b->l_tickets, B * kTicketStride * sizeof(unsigned int)));
-    if (!b->s_rho) HIP_TRY(hipMalloc((void **)&b->s_rho, 2 * cols * sizeof(double)));
-    if (!b->s_cnt) HIP_TRY(hipMalloc((void **)&b->s_cnt, 2 * cols * sizeof(long long)));
-    WT_TRY(b->moment.alloc(1, (size_t)b->cap, B));
+    WT_TRY(alloc_all({{(void **)&b->l_col, cols * sizeof(double)}, {(void **)&b->l_tickets, B * kTicketStride * sizeof(unsigned int)},
+                      {(void **)&b->s_rho, 2 * cols * sizeof(double)}, {(void **)&b->s_cnt, 2 * cols * sizeof(long long)}}, "surface-load buffers"));
+    WT_TRY(b->moment.alloc(1, (size_t)b->cap, B, "moment history"));
     HIP_TRY(hipMemsetAsync(b->l_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
     WT_TRY(b->moment.fill(1u, b->st));           // rows sampled before this call hold no Mz about these points
     b->loads = true;
@@ -2211,7 +2149,7 @@ extern "C" int wtp_moment(wtp_batch *b, double *mz)
     WT_TRY(check_ready(b));
     WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? launch_loads<float>(b, b->cap, false) : launch_loads<double>(b, b->cap, false));     // the scratch row
+    WT_TRY(with_dtype(b, [&](auto t) { return launch_loads<decltype(t)>(b, b->cap, false); }));     // the scratch row
     return read_rows(b, b->moment, b->cap, 1, {mz});
 }
 
@@ -2220,7 +2158,7 @@ extern "C" int wtp_surface(wtp_batch *b, int member, double *rho_upper, double *
 {
     WT_TRY(check_batch(b));
     if (!rho_upper || !rho_lower || !n_upper || !n_lower || !j_upper || !j_lower) return fail(WT_ERR_ARG, "null output");
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_member(b, member));
     WT_TRY(check_loads(b));
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->st));
@@ -2244,10 +2182,9 @@ extern "C" int wtp_enable_mex(wtp_batch *b, const double *xref, const double *yr
     const bool first = !b->xforces.allocated();
     WT_TRY(set_ref_points(b, xref, yref, &b->x_ref));
     const size_t B = (size_t)b->members;
-    if (!b->x_win) HIP_TRY(hipMalloc((void **)&b->x_win, B * 2 * sizeof(int32_t)));
-    if (!b->x_col) HIP_TRY(hipMalloc((void **)&b->x_col, B * b->nx * sizeof(MexPartial)));
-    if (!b->x_tickets) HIP_TRY(hipMalloc((void **)&b->x_tickets, B * kTicketStride * sizeof(unsigned int)));
-    WT_TRY(b->xforces.alloc(4, (size_t)b->cap, B));
+    WT_TRY(alloc_all({{(void **)&b->x_win, B * 2 * sizeof(int32_t)}, {(void **)&b->x_col, B * b->nx * sizeof(MexPartial)},
+                      {(void **)&b->x_tickets, B * kTicketStride * sizeof(unsigned int)}}, "momentum-exchange buffers"));
+    WT_TRY(b->xforces.alloc(4, (size_t)b->cap, B, "momentum-exchange history"));
     HIP_TRY(hipMemcpy(b->x_win, b->mex_win.data(), B * 2 * sizeof(int32_t), hipMemcpyHostToDevice));     // (the stream is idle)
     HIP_TRY(hipMemsetAsync(b->x_tickets, 0, B * kTicketStride * sizeof(unsigned int), b->st));
     // rows sampled before this call hold no Mz about these points; those before the first call hold nothing at all
@@ -2277,7 +2214,7 @@ extern "C" int wtp_mex(wtp_batch *b, double *fx, double *fy, double *mz, int64_t
     WT_TRY(check_mex(b));
     WT_TRY(check_ready(b));
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? launch_mex<float>(b, b->cap) : launch_mex<double>(b, b->cap));     // the scratch row
+    WT_TRY(with_dtype(b, [&](auto t) { return launch_mex<decltype(t)>(b, b->cap); }));     // the scratch row
     return read_rows(b, b->xforces, b->cap, 1, {fx, fy, mz, links});
 }
 
@@ -2289,12 +2226,11 @@ extern "C" int wtp_clamp_events(wtp_batch *b, int64_t *rho_events, int64_t *u_ev
     HIP_TRY(hipSetDevice(b->device));
     ClampPartial *dp = reinterpret_cast<ClampPartial *>(b->partials);     // (B * nb ForcePartials hold B * nb ClampPartials)
     for (int m = 0; m < b->members; m++) {
-        if (b->dtype == WT_F32)
-            hipLaunchKernelGGL(k_clamp_events<float>, dim3(b->nb), dim3(256), 0, b->st, (const float *)macro_of<float>(b, m),
+        with_dtype(b, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_clamp_events<T>, dim3(b->nb), dim3(256), 0, b->st, (const T *)macro_of<T>(b, m),
                                b->mask + (long)m * b->ms.mask, b->g, 0, b->nx, dp + (long)m * b->nb);
-        else
-            hipLaunchKernelGGL(k_clamp_events<double>, dim3(b->nb), dim3(256), 0, b->st, (const double *)macro_of<double>(b, m),
-                               b->mask + (long)m * b->ms.mask, b->g, 0, b->nx, dp + (long)m * b->nb);
+        });
         HIP_TRY(hipGetLastError());
     }
     std::vector<ClampPartial> hp((size_t)b->members * b->nb);
@@ -2333,9 +2269,9 @@ static int read_plane(wtp_batch *b, const T *src_cols, long pitch, T *host_dst)
     });
 }
 
-static int check_member(const wtp_batch *b, int member)
+static int check_readable(const wtp_batch *b, int member)
 {
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_member(b, member));
     if (!b->inited) return fail(WT_ERR_STATE, "no state to read");
     return WT_OK;
 }
@@ -2367,7 +2303,7 @@ extern "C" int wtp_read_stored(wtp_batch *b, int member, uint16_t *h)
     WT_TRY(check_batch(b));
     if (!h) return fail(WT_ERR_ARG, "h is null");
     if (b->storage != WTP_STORE_HALF) return fail(WT_ERR_STATE, "the batch stores its populations natively (wtp_create_stored)");
-    WT_TRY(check_member(b, member));
+    WT_TRY(check_readable(b, member));
     HIP_TRY(hipSetDevice(b->device));
     const size_t n = (size_t)b->nx * b->ny;
     for (int k = 0; k < 9; k++)
@@ -2379,10 +2315,10 @@ extern "C" int wtp_read_f(wtp_batch *b, int member, void *f_out)
 {
     WT_TRY(check_batch(b));
     if (!f_out) return fail(WT_ERR_ARG, "f_out is null");
-    WT_TRY(check_member(b, member));
+    WT_TRY(check_readable(b, member));
     HIP_TRY(hipSetDevice(b->device));
     if (b->storage == WTP_STORE_HALF) return read_f_half(b, member, reinterpret_cast<float *>(f_out));
-    return b->dtype == WT_F32 ? read_f_impl<float>(b, member, f_out) : read_f_impl<double>(b, member, f_out);
+    return with_dtype(b, [&](auto t) { return read_f_impl<decltype(t)>(b, member, f_out); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2434,7 +2370,7 @@ static int write_f_half(wtp_batch *b, int member, const float *in)
 // A write fills columns 0 .. NX-1 and rows 0 .. NY-1 of one lattice only: the start call has to have defined the rest.
 static int check_writable(const wtp_batch *b, int member)
 {
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_member(b, member));
     if (!b->inited) return fail(WT_ERR_STATE, "wtp_init_equilibrium has not been called: pad columns and the other lattice hold nothing defined");
     return WT_OK;
 }
@@ -2453,7 +2389,7 @@ extern "C" int wtp_write_f(wtp_batch *b, int member, const void *f_in)
     WT_TRY(check_writable(b, member));
     HIP_TRY(hipSetDevice(b->device));
     if (b->storage == WTP_STORE_HALF) WT_TRY(write_f_half(b, member, reinterpret_cast<const float *>(f_in)));
-    else WT_TRY(b->dtype == WT_F32 ? write_raw<float>(b, member, f_in) : write_raw<double>(b, member, f_in));
+    else WT_TRY(with_dtype(b, [&](auto t) { return write_raw<decltype(t)>(b, member, f_in); }));
     return after_write(b, member);
 }
 
@@ -2501,10 +2437,10 @@ static int read_macro_impl(wtp_batch *b, int member, void *rho, void *ux, void *
 extern "C" int wtp_read_macro(wtp_batch *b, int member, void *rho, void *ux, void *uy)
 {
     WT_TRY(check_batch(b));
-    WT_TRY(check_member(b, member));
+    WT_TRY(check_readable(b, member));
     WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
-    return b->dtype == WT_F32 ? read_macro_impl<float>(b, member, rho, ux, uy) : read_macro_impl<double>(b, member, rho, ux, uy);
+    return with_dtype(b, [&](auto t) { return read_macro_impl<decltype(t)>(b, member, rho, ux, uy); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2518,15 +2454,9 @@ extern "C" int wtp_enable_mean(wtp_batch *b)
         const size_t B = (size_t)b->members;
         const int pitch = (b->ny + WTP_MEAN_ROWS - 1) / WTP_MEAN_ROWS * WTP_MEAN_ROWS;
         const long stride = member_stride((size_t)kMeanPlanes * b->nx * pitch * sizeof(double), sizeof(double));
-        void *sums = nullptr, *cnt = nullptr;
-        hipError_t e = hipMalloc(&sums, B * (size_t)stride * sizeof(double));
-        if (e == hipSuccess && (e = hipMalloc(&cnt, B * sizeof(long long))) != hipSuccess) (void)hipFree(sums);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();             // (the batch goes on without the read-out: later launches must not see this error)
-            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the mean-field sums (%zu bytes) could not be allocated: %s",
-                        B * (size_t)stride * sizeof(double), hipGetErrorString(e));
-        }
-        b->m_sums = (double *)sums; b->m_cnt = (long long *)cnt; b->m_stride = stride; b->m_pitch = pitch;
+        WT_TRY(alloc_all({{(void **)&b->m_sums, B * (size_t)stride * sizeof(double)}, {(void **)&b->m_cnt, B * sizeof(long long)}},
+                         "mean-field sums"));        // (on a failure the batch goes on without the read-out)
+        b->m_stride = stride; b->m_pitch = pitch;
     }
     WT_TRY(zero_mean_sums(b, 0, b->members));
     b->mean = true;
@@ -2537,7 +2467,7 @@ extern "C" int wtp_mean_sums(wtp_batch *b, int member, int64_t *n, double *rho, 
                              double *uy2, double *uxuy)
 {
     WT_TRY(check_batch(b));
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_member(b, member));
     if (!b->mean) return fail(WT_ERR_STATE, "the mean fields are not enabled (wtp_enable_mean)");
     HIP_TRY(hipSetDevice(b->device));
     double *dst[kMeanPlanes] = {rho, ux, uy, rho2, ux2, uy2, uxuy};
@@ -2576,18 +2506,9 @@ extern "C" int wtp_enable_probes(wtp_batch *b, int npoints)
     const size_t B = (size_t)b->members, P = (size_t)npoints;
     if (npoints != b->pb_n) {                    // another count: new buffers first, so that a failure leaves the batch as it was
         void *off = nullptr, *w = nullptr, *sums = nullptr, *cnt = nullptr, *row = nullptr;
-        hipError_t e = hipMalloc(&off, B * P * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc(&w, B * 4 * P * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&sums, B * 3 * P * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&cnt, B * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc(&row, 3 * P * sizeof(double));
-        if (e == hipSuccess) e = hipStreamSynchronize(b->st);      // samples already enqueued read and write the previous buffers
-        if (e != hipSuccess) {
-            (void)hipGetLastError();             // (the batch goes on as it was: later launches must not see this error)
-            for (void *p : {off, w, sums, cnt, row}) if (p) (void)hipFree(p);
-            return fail(e == hipErrorOutOfMemory ? WT_ERR_OOM : WT_ERR_HIP, "the probe tables and sums (%zu bytes) could not be allocated: %s",
-                        B * P * 64 + B * 8 + P * 24, hipGetErrorString(e));
-        }
+        HIP_TRY(hipStreamSynchronize(b->st));    // samples already enqueued read and write the previous buffers
+        WT_TRY(alloc_all({{&off, B * P * sizeof(long long)}, {&w, B * 4 * P * sizeof(double)}, {&sums, B * 3 * P * sizeof(double)},
+                          {&cnt, B * sizeof(long long)}, {&row, 3 * P * sizeof(double)}}, "probe tables and sums"));
         free_probes(b);
         b->pb_off = (long long *)off; b->pb_w = (double *)w; b->pb_sums = (double *)sums; b->pb_cnt = (long long *)cnt; b->pb_row = (double *)row;
         b->pb_n = npoints;
@@ -2629,8 +2550,7 @@ extern "C" int wtp_set_probes(wtp_batch *b, int first, int count, const double *
 {
     WT_TRY(check_batch(b));
     if (!x || !y) return fail(WT_ERR_ARG, "x or y is null");
-    if (first < 0 || count < 1 || first + count > b->members)
-        return fail(WT_ERR_ARG, "members [%d, %d) outside the batch of %d", first, first + count, b->members);
+    WT_TRY(check_members(b, first, count));
     WT_TRY(check_probes(b));
     const size_t P = (size_t)b->pb_n;
     std::vector<long long> off((size_t)count * P);
@@ -2648,17 +2568,24 @@ extern "C" int wtp_set_probes(wtp_batch *b, int first, int count, const double *
     return zero_probe_sums(b, first, count);
 }
 
-extern "C" int wtp_probe_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy)
+// Three [P] arrays of the device, one behind the other from `src`, to the destinations that are not null.
+static int read_probe_values(const wtp_batch *b, const double *src, double *rho, double *ux, double *uy)
 {
-    WT_TRY(check_batch(b));
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
-    WT_TRY(check_probes(b));
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->st));
     const size_t P = (size_t)b->pb_n;
     double *const dst[3] = {rho, ux, uy};
     for (int a = 0; a < 3; a++)
-        if (dst[a]) HIP_TRY(hipMemcpy(dst[a], b->pb_sums + ((size_t)member * 3 + a) * P, P * sizeof(double), hipMemcpyDeviceToHost));
+        if (dst[a]) HIP_TRY(hipMemcpy(dst[a], src + (size_t)a * P, P * sizeof(double), hipMemcpyDeviceToHost));
+    return WT_OK;
+}
+
+extern "C" int wtp_probe_sums(wtp_batch *b, int member, int64_t *n, double *rho, double *ux, double *uy)
+{
+    WT_TRY(check_batch(b));
+    WT_TRY(check_member(b, member));
+    WT_TRY(check_probes(b));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    WT_TRY(read_probe_values(b, b->pb_sums + (size_t)member * 3 * b->pb_n, rho, ux, uy));
     if (n) HIP_TRY(hipMemcpy(n, b->pb_cnt + member, sizeof(int64_t), hipMemcpyDeviceToHost));
     return WT_OK;
 }
@@ -2678,16 +2605,12 @@ static int launch_probe_sample(wtp_batch *b, int member)
 extern "C" int wtp_probe_sample(wtp_batch *b, int member, double *rho, double *ux, double *uy)
 {
     WT_TRY(check_batch(b));
-    if (member < 0 || member >= b->members) return fail(WT_ERR_ARG, "member %d outside the batch of %d", member, b->members);
+    WT_TRY(check_member(b, member));
     WT_TRY(check_probes(b));
     WT_TRY(check_ready(b));
     WT_TRY(check_macro(b));
     HIP_TRY(hipSetDevice(b->device));
-    WT_TRY(b->dtype == WT_F32 ? launch_probe_sample<float>(b, member) : launch_probe_sample<double>(b, member));
+    WT_TRY(with_dtype(b, [&](auto t) { return launch_probe_sample<decltype(t)>(b, member); }));
     HIP_TRY(hipStreamSynchronize(b->st));
-    const size_t P = (size_t)b->pb_n;
-    double *const dst[3] = {rho, ux, uy};
-    for (int a = 0; a < 3; a++)
-        if (dst[a]) HIP_TRY(hipMemcpy(dst[a], b->pb_row + (size_t)a * P, P * sizeof(double), hipMemcpyDeviceToHost));
-    return WT_OK;
+    return read_probe_values(b, b->pb_row, rho, ux, uy);
 }

@@ -10,9 +10,10 @@ import pytest
 from conftest import ROOT
 
 BGK, LES, TRT, TRT_LES = range(4)       # COLL, d2q9.hpp
-HALFWAY, INTERP = range(2)              # WALL
+HALFWAY, INTERP, MOVING = range(3)      # WALL
 AXIAL, INCLINED, PROFILE = range(3)     # FAR
 _STEP = re.compile(r"^_Z\d+k_step_(half_)?batchI([fd]?)((?:L[bi]\d+E)+)E")
+_MEX = re.compile(r"^_Z\d+k_mex_batchI(f|d|DF16_)\d+Link(Halfway|Interp|Moving)I([fd])EE")
 
 
 def step_variant(name):
@@ -30,13 +31,30 @@ def step_variant(name):
 
 
 def step_variants_built():
-    """The step kernels the library is to hold, no more and no fewer: native, both dtypes, emitting and not, every collision with either wall
-    rule and every far field but the two-relaxation-time collisions with the axial one (80); half, every collision with the inclined far
-    field and the single-relaxation-time ones with the axial one too (12)."""
-    native = {("native", t, e, c, w, f) for t in "fd" for e in (0, 1) for c in range(4) for w in range(2) for f in range(3)
+    """The step kernels the library is to hold, no more and no fewer: native, both dtypes, emitting and not, every collision with each of the
+    three wall rules and every far field but the two-relaxation-time collisions with the axial one (120); half, every collision with the
+    inclined far field and the single-relaxation-time ones with the axial one too (12)."""
+    native = {("native", t, e, c, w, f) for t in "fd" for e in (0, 1) for c in range(4) for w in range(3) for f in range(3)
               if not (c >= TRT and f == AXIAL)}
     half = {("half", "f", e, c, HALFWAY, f) for e in (0, 1) for c in range(4) for f in (AXIAL, INCLINED) if not (c >= TRT and f == AXIAL)}
     return native | half
+
+
+def mex_variant(name):
+    """(E, link rule) of a mangled k_mex_batch<E, Link> symbol: E "f", "d" or "half", the rule "Halfway", "Interp" or "Moving"; None for any
+    other symbol.  The rule's own type is E, but for a half lattice, whose rule works on the loaded fp32 value."""
+    m = _MEX.match(name)
+    if not m:
+        return None
+    e = "half" if m.group(1) == "DF16_" else m.group(1)
+    assert m.group(3) == ("f" if e == "half" else e), name
+    return (e, m.group(2))
+
+
+def mex_variants_built():
+    """The momentum-exchange kernels the library is to hold: both dtypes with each of the three link rules, and the half lattice with the
+    half-way one."""
+    return {(e, r) for e in "fd" for r in ("Halfway", "Interp", "Moving")} | {("half", "Halfway")}
 
 
 def step_kernels(chk, files, select=lambda v: True):

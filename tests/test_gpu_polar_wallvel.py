@@ -1,4 +1,4 @@
-"""GPU: the wall velocity of batched sweeps (k_step_batch with WALL_MOVING, k_mex_wallvel_batch, wtp_enable_wall_velocity,
+"""GPU: the wall velocity of batched sweeps (k_step_batch with WALL_MOVING, k_mex_batch with LinkMoving, wtp_enable_wall_velocity,
 wtp_set_wall_velocity) against its definition in NumPy (tests/_wallvel_reference.py).
 
 There is no tolerance on the state: the kernel and the reference round every operation of the wall rule once, in the same order, so

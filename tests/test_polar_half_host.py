@@ -214,9 +214,9 @@ def test_half_kernels_have_their_instantiations_and_no_scratch(polar_isa):
     seen = {}
     for f in files:
         for name, r in chk.resources(f).items():
-            if name in step or "k_mex_half_batch" in name or "k_fill_half" in name:
+            if name in step or _polar_isa.mex_variant(name) == ("half", "Halfway") or "k_fill_half" in name:
                 seen[name] = r
                 assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: v.get("num_vgpr") for k, v in seen.items()})
     assert sum(n in step for n in seen) == 8, sorted(seen)
-    assert sum("k_mex_half_batch" in n for n in seen) == 1 and sum("k_fill_half" in n for n in seen) == 1, sorted(seen)
+    assert sum(_polar_isa.mex_variant(n) == ("half", "Halfway") for n in seen) == 1 and sum("k_fill_half" in n for n in seen) == 1, sorted(seen)

@@ -151,12 +151,12 @@ def test_batched_kernels_have_no_scratch_and_no_store_hazard(polar_isa):
 
 
 def test_the_step_kernels_are_exactly_the_built_variants(polar_isa):
-    """k_step_batch and k_step_half_batch hold the 80 + 12 variants that wtp_step can select, each once: no combination dropped, none added,
-    and no step kernel of another name."""
+    """k_step_batch and k_step_half_batch hold the 120 + 12 variants that wtp_step can select, each once: no combination dropped, none added,
+    and no step kernel of another name (the moving-wall variants are k_step_batch's like the rest)."""
     chk, files = polar_isa
-    names = [n for f in files for n in chk.resources(f) if "k_step" in n]
+    names = [n for f in files for n in chk.resources(f) if "k_step" in n or "k_wallvel" in n]
     variants = [_polar_isa.step_variant(n) for n in names]
     assert None not in variants, [n for n, v in zip(names, variants) if v is None]
-    assert len(variants) == len(set(variants)) == 92
+    assert len(variants) == len(set(variants)) == 132
     assert set(variants) == _polar_isa.step_variants_built()
-    assert sum(v[0] == "native" and v[5] == _polar_isa.PROFILE for v in variants) == 32
+    assert sum(v[0] == "native" and v[5] == _polar_isa.PROFILE for v in variants) == 48

@@ -223,7 +223,7 @@ def test_ibb_kernels_have_their_instantiations_and_no_scratch(polar_isa):
     chk, files = polar_isa
     family = lambda v: v[0] == "native" and v[4:] == (_polar_isa.INTERP, _polar_isa.AXIAL)      # noqa: E731
     step = {name: r for name, (_, r) in _polar_isa.step_kernels(chk, files, family).items()}
-    mex = {name: r for f in files for name, r in chk.resources(f).items() if "k_mex_ibb_batch" in name}
+    mex = {name: r for f in files for name, r in chk.resources(f).items() if _polar_isa.mex_variant(name) in (("f", "Interp"), ("d", "Interp"))}
     for name, r in {**step, **mex}.items():
         assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: v.get("num_vgpr") for k, v in {**step, **mex}.items()})

@@ -258,7 +258,21 @@ def test_mex_kernel_has_no_scratch(polar_isa):
     seen = []
     for f in files:
         for name, r in chk.resources(f).items():
-            if "k_mex_batch" in name:
+            if _polar_isa.mex_variant(name) in (("f", "Halfway"), ("d", "Halfway")):
                 seen.append(name)
                 assert r.get("private_seg_size", 0) == 0, (name, r)
     assert len(seen) == 2, seen                     # float and double
+
+
+def test_the_mex_kernels_are_exactly_the_built_variants(polar_isa):
+    """k_mex_batch<E, Link> holds the seven kernels that a sample can select, each once, and the momentum exchange has no kernel of another
+    name; the two moving-wall ones, which no other test looks at, have no scratch."""
+    chk, files = polar_isa
+    res = {n: r for f in files for n, r in chk.resources(f).items() if "k_mex" in n}
+    variants = [_polar_isa.mex_variant(n) for n in res]
+    assert None not in variants, [n for n, v in zip(res, variants) if v is None]
+    assert len(variants) == 7 and set(variants) == _polar_isa.mex_variants_built(), sorted(res)
+    moving = [n for n in res if _polar_isa.mex_variant(n)[1] == "Moving"]
+    assert len(moving) == 2
+    for n in moving:
+        assert res[n].get("private_seg_size", 0) == 0, (n, res[n])

@@ -195,11 +195,12 @@ def polar_isa():
 
 
 def test_wind_step_has_sixteen_instantiations_and_no_scratch(polar_isa):
-    """fp32 and fp64, emitting and not, BGK and Smagorinsky, half-way and interpolated walls.  No spill."""
+    """fp32 and fp64, emitting and not, BGK and Smagorinsky, half-way and interpolated walls (16), and the moving-wall variants of the same
+    (8).  No spill."""
     chk, files = polar_isa
     family = lambda v: v[0] == "native" and v[5] == _polar_isa.INCLINED and v[3] in (_polar_isa.BGK, _polar_isa.LES)      # noqa: E731
     seen = {name: r for name, (_, r) in _polar_isa.step_kernels(chk, files, family).items()}
     for name, r in seen.items():
         assert r.get("private_seg_size", 0) == 0, (name, r)
     print({k: (v.get("num_vgpr"), v.get("num_sgpr")) for k, v in seen.items()})
-    assert len(seen) == 16, sorted(seen)
+    assert len(seen) == 16 + 8, sorted(seen)

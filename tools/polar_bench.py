@@ -36,13 +36,14 @@ model is on in both variants of those protocols.
 
 The batched step with interpolated bounce-back (wtp_enable_ibb, every member with the wall distances of its own airfoil):
 the WALL_INTERP instantiation of k_step_batch with the collision the other switches select.  The line has the shape of --les's; no
-sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_ibb_batch).
+sequential leg either.  With --loads / --mex / --mean the model is on in both variants of those protocols (and --mex then times k_mex_batch with LinkInterp).
 
     python tools/polar_bench.py --wall-velocity [--les CS] [--wind] [--trt MAGIC] [--profile] [--repeats 5] [the options of the first form]
 
 The batched step with moving walls (wtp_enable_wall_velocity on top of --ibb's wall distances; every member's body turns rigidly about the
-lattice's centre, so that every link carries a term): k_wallvel_batch with the collision and the far field the other switches select.  The
-line has the shape of --les's; no sequential leg either.  Not with --storage half.  Without --wall-velocity, --lib may name a build from
+lattice's centre, so that every link carries a term): the WALL_MOVING instantiation of k_step_batch with the collision and the far field the other switches select.  The
+line has the shape of --les's; no sequential leg either.  Not with --storage half.  With --mex the model is on in both variants of that
+protocol (and --mex then times k_mex_batch with LinkMoving); not with --loads, --mean or --probes.  Without --wall-velocity, --lib may name a build from
 before the entry points existed.
 
     python tools/polar_bench.py --wind [--les CS] [--ibb] [--repeats 5] [the options of the first form]
@@ -56,7 +57,7 @@ has the shape of --les's; no sequential leg either.  With --loads / --mex / --me
 The batched step of a half batch (PolarEngine(storage="half")): k_step_half_batch, with the collision and the far field the other switches
 select, on lattices of binary16 deviations from the weights.  The line has the shape of --les's and counts 37 B per site (nine 2-byte loads,
 nine 2-byte stores and the mask byte) in place of 72; no sequential leg.  Not with --ibb.  With --loads / --mex / --mean the batch is
-a half batch in both variants of those protocols (and --mex then times k_mex_half_batch).
+a half batch in both variants of those protocols (and --mex then times k_mex_batch on half_t elements).
 
     python tools/polar_bench.py --trt MAGIC [--les CS] [--ibb] [--wind] [--storage half] [--repeats 5] [the options of the first form]
 
@@ -177,6 +178,7 @@ IBB = False     # --ibb: the sampled protocols run with interpolated bounce-back
 WIND = False    # --wind: the sampled protocols run with an inclined free stream
 STORAGE = "native"      # --storage: the sampled protocols run on a batch of this storage
 TRT = None      # --trt: the magic number the sampled protocols run the two-relaxation-time collision with (None: off)
+WALLVEL = False         # --wall-velocity: the sampled protocols run with interpolated bounce-back and a wall velocity
 
 
 def _default_rakes(nx, ny, b):
@@ -208,8 +210,10 @@ def bench_sampled(nx, ny, b, steps, warmup, masks, every, loads, repeats, mex=Fa
             eng.set_probes(*probes)
         if LES is not None:
             eng.enable_les(LES)
-        if IBB:
+        if IBB or WALLVEL:
             _interpolated_walls(eng, nx, ny, b)
+        if WALLVEL:
+            _wall_velocity(eng, nx, ny, b)
         if TRT is not None:
             eng.enable_trt(TRT)
         eng.step(warmup - warmup % every, TAU, U0)
@@ -378,15 +382,15 @@ def main():
         pkg.polar.load_polar_library(a.lib, optional=tuple(name for name, free in unused if free))
     if a.storage == "half" and (a.ibb or a.wall_velocity):
         ap.error("--storage half does not combine with --ibb or --wall-velocity")
-    if a.wall_velocity and not plain:
-        ap.error("--wall-velocity times the plain stepping form only")
+    if a.wall_velocity and (a.loads or a.mean or a.probes):
+        ap.error("--wall-velocity times the plain stepping form and --mex only")
     half = a.storage == "half"
     if half and a.profile:
         ap.error("--storage half does not combine with --profile")
     if a.profile and not plain:
         ap.error("--profile times the plain stepping form only")
-    global LES, IBB, WIND, STORAGE, TRT
-    LES, IBB, WIND, STORAGE, TRT = a.les, a.ibb, a.wind, a.storage, a.trt
+    global LES, IBB, WIND, STORAGE, TRT, WALLVEL
+    LES, IBB, WIND, STORAGE, TRT, WALLVEL = a.les, a.ibb, a.wind, a.storage, a.trt, a.wall_velocity
     if a.probes:
         return probes_cost(a)
     if a.mean:

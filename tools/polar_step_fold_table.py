@@ -19,7 +19,7 @@ import _polar_isa as P              # noqa: E402
 
 OLD = re.compile(r"^_Z\d+k_step_(|les_|ibb_|wind_|trt_|profile_|half_|trt_half_)batchI([fd]?)((?:L[bi]\d+E)+)E")
 COUNTED = re.compile(r"^(global_|buffer_|flat_|scratch_|ds_)|" + F.FP.pattern[1:])
-COLLS, WALLS, FARS = ("BGK", "LES", "TRT", "TRT+LES"), ("half-way", "interp"), ("axial", "inclined", "profile")
+COLLS, WALLS, FARS = ("BGK", "LES", "TRT", "TRT+LES"), ("half-way", "interp", "moving"), ("axial", "inclined", "profile")
 
 
 def old_variant(name):
